@@ -2,7 +2,7 @@
 """Benchmark of the UVC Stage-1 step on MI355X (BASELINE.json metric: images/sec, DeiT-Tiny,
 budget 0.5, per-GPU batch 512, bf16 MFMA compute, 1/2/4/8 GPUs weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = the full UVC-train step of joint_train.py:395-450 on one batch of synthetic
@@ -10,6 +10,10 @@ ImageNet-shaped inputs already resident in HBM: student forward + teacher forwar
 loss + student backward + gradient all-reduce + clip + AdamW + scheduler + uvc_optimizer (prox, scores,
 ranks, primal/dual update).  Rank 0 prints ONE JSON line; see DESIGN.md "Measurement" for how
 `roofline` and `cpu_baseline` are defined.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything measured beside the headline -- the all-rows
+and warm-up-phase steps, the stand-alone kernel table (`roofline`, `top_kernels`), the fp32 / bf16_f32resid legs and the CPU
+baseline -- runs only with `--full`.  `--dump-outputs DIR` writes what the last timed step returned (DIR/<name>.npy, `dump_outputs`).
 """
 import argparse
 import json
@@ -74,6 +78,10 @@ def parse():
     p.add_argument("--patch_ratio", type=float, default=0.9)
     p.add_argument("--enable_block_gating", type=int, default=1)
     p.add_argument("--full_tail", type=int, default=0, help="1: the last block computes all B*N rows like the reference (default: its token rows only; same outputs)")
+    p.add_argument("--full", action="store_true", help="also run the legs beside the headline (all-rows and warm-up-phase steps, stand-alone kernel "
+                                                       "table / roofline, fp32 and bf16_f32resid legs, CPU baseline); a plain run times the K steps only")
+    p.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned to DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     return p.parse_args()
 
 
@@ -305,6 +313,44 @@ def cpu_baseline(args):
                       f"batch 8, 3 warm-ups + {b8['steps']} timed steps, median (value); batch 64, 1 + {points[1]['steps']} steps", "points": points}
 
 
+DUMP_MAX_ELEMS = 1 << 21       # per array; a larger one is written as a seeded sample of this many indices
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out, model, path):
+    """`--dump-outputs DIR`: what a caller of the timed path receives from its LAST step -- every array of the trainer's step result
+    (loss, logits, clip norm; Stage 1 adds the reported resource, s, r and the gate logits) and the parameters the step left -- as
+    DIR/<name>.npy, float64 kept, anything else as float32.  An array of more than DUMP_MAX_ELEMS elements is written flattened at
+    the sorted indices of a fixed-seed draw, so two builds run with the same arguments can be compared array for array."""
+    import numpy as np
+    arrays = {}
+
+    def add(name, v):
+        if v is None or isinstance(v, (bool, str)):
+            return
+        if isinstance(v, (list, tuple)):
+            for i, e in enumerate(v):
+                add(f"{name}_{i}", e)
+            return
+        t = v.detach() if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.unique(np.random.default_rng(20240).integers(0, t.numel(), DUMP_MAX_ELEMS))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        arrays[name] = t.cpu().numpy()
+
+    for k, v in out.items():
+        add(k, v)
+    add("params", torch.cat([p.detach().float().reshape(-1) for p in model.parameters()]))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", 0))
@@ -413,6 +459,8 @@ def main():
         dist.destroy_process_group()
         if rank != 0:
             return
+    if args.dump_outputs and rank == 0:          # before any leg below moves the trainer on
+        dump_outputs(out, tr.model, args.dump_outputs)
     loss = float(out["loss"])
     if rank == 0:
         imgs = world * args.batch * args.steps / dt
@@ -462,7 +510,8 @@ def main():
             line.pop("step_tflops_per_gpu"); line.pop("step_frac_of_bf16_mfma_peak")
         if exposed_ms is not None:
             line["exposed_allreduce_ms_per_step"] = round(exposed_ms, 3)       # main stream stalled in reducer.finish(), event-timed
-        if args.stage == 1 and args.phase == "train" and world == 1 and not args.full_tail:
+        # what follows measures beside the headline and runs with --full only
+        if args.full and args.stage == 1 and args.phase == "train" and world == 1 and not args.full_tail:
             # the same step with every row of the last block computed, as the reference executes it (identical outputs; A/B of the
             # dead-row elimination): 5 + 30 steps
             models = [tr.model] + ([tr.teacher] if getattr(tr, "teacher", None) is not None else [])
@@ -478,7 +527,7 @@ def main():
             line["images_per_sec_all_rows_of_last_block"] = round(30 * args.batch / (time.perf_counter() - tw), 1)
             for m_ in models:
                 m_.full_tail = False
-        if args.stage == 1 and args.phase == "train" and world == 1:
+        if args.full and args.stage == 1 and args.phase == "train" and world == 1:
             # the warm-up-phase step for reference: gates fixed at .5/.5, gate logits frozen, uvc_optimizer returns early
             tr.begin_epoch(1)
             for _ in range(5):
@@ -489,7 +538,7 @@ def main():
                 tr.step(x, y)
             torch.cuda.synchronize()
             line["warmup_phase_images_per_sec"] = round(20 * args.batch / (time.perf_counter() - tw), 1)
-        if args.stage == 1 and args.precision.startswith("bf16") and args.model_type in GFLOP_PER_IMG:
+        if args.full and args.stage == 1 and args.precision.startswith("bf16") and args.model_type in GFLOP_PER_IMG:
             del tr, out
             torch.cuda.empty_cache()
             roof, top, total_ms = kernel_table(args)
@@ -497,9 +546,9 @@ def main():
             line["top_kernels"] = top
             line["kernel_ms_per_step_standalone_sum"] = total_ms
             line["in_step_top_kernel"] = in_step_top(args)
-        else:
+        elif args.full:
             line["roofline"] = None
-        if args.stage == 1 and args.phase == "train" and world == 1 and args.precision == "bf16" and not (args.no_mode_legs or args.no_cpu_baseline):
+        if args.full and args.stage == 1 and args.phase == "train" and world == 1 and args.precision == "bf16" and not (args.no_mode_legs or args.no_cpu_baseline):
             # the same step in the two parity-grade modes, outside the timed region (VERDICT r5 #4a): `fp32` is the mode the reference goldens are held to at
             # 1e-3 (exact-float32 MFMA, float32 activations), `bf16_f32resid` keeps float32 residual-stream rows under bf16 operands
             try:
@@ -530,7 +579,7 @@ def main():
             line["parity_modes_note"] = ("fp32: tests hold it to the reference goldens at 1e-3; bf16_f32resid / bf16 (the headline): 2e-2 on loss / logits, "
                                          "<= 2.5 % per gradient tensor against float32 autograd; 3 warm-up + 12 / 30 timed steps each, same batch and state")
         line["commit"] = _git_head()
-        if world == 1 and not args.no_cpu_baseline and args.stage == 1:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.stage == 1:
             line["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(line), file=_real_stdout, flush=True)
 

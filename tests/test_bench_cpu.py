@@ -76,3 +76,42 @@ def test_one_byte_gelu_grad_code_is_as_accurate_as_bf16_where_it_matters():
         e8 = float((g * (torch.clamp(torch.floor((gpa - Q8_LO) / Q8_STEP + 0.5), 0, 255) * Q8_STEP + Q8_LO) - ref).norm() / ref.norm())
         e16 = float((g * gpa.float().bfloat16().double() - ref).norm() / ref.norm())
         assert e8 <= 3e-3 and e8 <= 1.7 * e16, (sigma, e8, e16)
+
+
+def test_plain_run_defaults_and_new_switches():
+    _, a = _args()
+    assert a.full is False and a.dump_outputs is None and a.steps == 100 and a.warmup == 20
+    old = sys.argv
+    sys.argv = ["bench.py", "--steps", "7", "--full", "--dump-outputs", "out_dir"]
+    try:
+        import bench
+        b = bench.parse()
+    finally:
+        sys.argv = old
+    assert b.steps == 7 and b.full is True and b.dump_outputs == "out_dir"
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_large_ones(tmp_path):
+    """--dump-outputs: every array of a step result as <name>.npy, float64 kept and the rest float32, tuples split, flags skipped; an array
+    larger than DUMP_MAX_ELEMS written at the same fixed-seed indices every time."""
+    import numpy as np
+    bench, _ = _args()
+    torch.manual_seed(0)
+    model = torch.nn.Linear(4096, 1024)                   # 4.2 M parameters: sampled
+    logits = torch.randn(8, 10).bfloat16()
+    out = dict(loss=torch.tensor(2.5), outputs=(logits, logits), gnorm=torch.tensor(1.25, dtype=torch.float64), cur=0.75,
+               s=np.arange(6, dtype=np.float32).reshape(3, 2), g=None, stepped=True)
+    names = bench.dump_outputs(out, model, str(tmp_path / "a"))
+    assert names == ["cur", "gnorm", "loss", "outputs_0", "outputs_1", "params", "s"]
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert got["gnorm"].dtype == np.float64 and got["cur"].dtype == np.float64 and float(got["cur"]) == 0.75
+    assert all(got[n].dtype == np.float32 for n in ("loss", "outputs_0", "outputs_1", "params", "s"))
+    np.testing.assert_array_equal(got["outputs_0"], logits.float().numpy())
+    np.testing.assert_array_equal(got["s"], out["s"])
+    p = got["params"]
+    assert p.ndim == 1 and 0 < p.size <= bench.DUMP_MAX_ELEMS
+    bench.dump_outputs(out, model, str(tmp_path / "b"))
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "params.npy"), p)
+    flat = torch.cat([q.detach().reshape(-1) for q in model.parameters()]).numpy()
+    assert np.isin(p, flat).all()
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20

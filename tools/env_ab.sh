@@ -5,7 +5,7 @@ V=$1; shift
 for r in 1 2 3; do
   for v in default "$V"; do
     if [ "$v" = default ]; then E=""; else E="$v"; fi
-    env $E python bench.py --no_cpu_baseline --steps 60 "$@" 2>/dev/null | python -c "
+    env $E python bench.py --full --no_cpu_baseline --steps 60 "$@" 2>/dev/null | python -c "
 import json,sys;d=json.loads(sys.stdin.read());print('$v',d['value'],d['ms_per_step'],d['kernel_ms_per_step_standalone_sum'])"
   done
 done
