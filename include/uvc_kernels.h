@@ -101,7 +101,8 @@ int uvc_gemm_tn_workspace_bytes(int32_t M, int32_t N1, int32_t N2, int64_t* byte
 
 /* Fused softmax(q k^T * scale) v for one DeiT sequence per (batch, head)
  * (UVC/models/model_distilled.py:175-185).  qkv is the packed Linear(dim, 3*dim) output
- * [B, N, 3, H, 64]; o is [B, N, H*64]; lse/delta are float32 [B, H, N].  N <= 256, head_dim = 64. */
+ * [B, N, 3, H, 64]; o is [B, N, H*64]; lse/delta are float32 [B, H, N].  N <= 1026, head_dim = 64
+ * (N > 256: streaming kernels, K / V or Q / dO tiles through LDS; the one-pass backward, variant 2, is not among them). */
 typedef struct uvc_attn_args {
   const void* qkv;   /* T */
   void* o;           /* T  (forward output; backward input) */

@@ -1,4 +1,5 @@
-// Fused multi-head attention forward/backward for DeiT sequences (N <= 256, head_dim = 64) on gfx950.
+// Fused multi-head attention forward/backward for DeiT sequences (N <= 256, head_dim = 64) on gfx950; longer sequences
+// (N <= 1026) take the streaming kernels of the "Long sequences" section below.
 // Reference arithmetic: UVC/models/model_distilled.py:175-185  (softmax(q k^T * hd^-0.5) v, dropout p=0).
 //
 // One workgroup (4 waves) per (batch, head).  N = 197/198 means a whole head's K and V fit in LDS
@@ -1053,6 +1054,352 @@ __global__ __launch_bounds__((NT + NHW) * 64) void k_qkv_attn_fwd(Args a) {
 }
 }  // namespace qa
 
+// ------------------------------------------------------------------------------------------------
+// Long sequences (256 < N <= 1026: 384-px DeiT, N = 577 / 578; patch-8 models, N = 785).  A head's K and V no longer fit the LDS
+// whole (144 KiB in bf16 at N = 577), so these kernels stream the inner dimension through it in tiles of LK = 64 rows, double-buffered:
+// the next tile's rows are loaded into registers before the current tile is computed and written to the other buffer after it, one
+// barrier per tile.  One workgroup of 8 waves per (image, head, block of LQ = 128 rows); each wave owns one 16-row tile of the block for
+// the whole sweep, with the same operand orientation and tile body as the kernels above (keys on the MFMA rows, the query on the lane).
+//   forward: online softmax over the key tiles, a running maximum and sum per query row, rescaled at every tile (no deferred threshold:
+//            16 multiplies per lane and tile).  The first key of every tile is a real key, so the running maximum is finite from tile 0 on.
+//   dQ:      per query block, K / V tiles streamed; P recomputed from lse (no row maximum); writes delta = rowsum(dO * O).
+//   dK / dV: per key block, Q / dO tiles streamed with their lse (+inf on padded queries: p = 0) and delta.
+// No atomics: every output row is written by one wave, so results are deterministic and independent of the batch.  Rows past N are
+// zero in the LDS tiles; scores of padded keys are masked in the ragged last tile (N = 577 = 9 x 64 + 1: one valid key).
+constexpr int LQ = 128, LK = 64, LONG_MAX_N = 1026;
+template <typename T> struct LongTile {
+  static constexpr int CPR = HD / Mma<T>::CH;             // 16-byte chunks per row
+  static constexpr int NCL = LK * CPR / 512;               // chunks per thread and matrix (bf16 1, float32 2)
+  static constexpr int BYTES = LK * Geom<T>::ROWB;
+  static __device__ __forceinline__ void load(u32x4 (&v)[NCL], const T* g, size_t ld, int r0, int N) {
+    const u32x4 z = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < NCL; ++i) {
+      const int id = i * 512 + (int)threadIdx.x, row = r0 + id / CPR, c = id % CPR;
+      v[i] = row < N ? *reinterpret_cast<const u32x4*>(g + (size_t)row * ld + c * Mma<T>::CH) : z;
+    }
+  }
+  static __device__ __forceinline__ void store(char* lds, const u32x4 (&v)[NCL]) {
+#pragma unroll
+    for (int i = 0; i < NCL; ++i) {
+      const int id = i * 512 + (int)threadIdx.x;
+      *reinterpret_cast<u32x4*>(lds + (id / CPR) * Geom<T>::ROWB + (id % CPR) * 16) = v[i];
+    }
+  }
+};
+
+// zero rows [r0, r1) of one head's 64 columns (ld elements per row): skipped heads
+template <typename T> __device__ __forceinline__ void zero_rows64(T* base, size_t ld, int r0, int r1) {
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  for (int i = threadIdx.x; i < (r1 - r0) * 16; i += blockDim.x) Store4<T>::st(base + (size_t)(r0 + (i >> 4)) * ld + (i & 15) * 4, z);
+}
+
+template <typename T>
+__global__ __launch_bounds__(512) void k_attn_fwd_long(AttnArgs a) {
+  typedef Mma<T> MM;
+  typedef Geom<T> G;
+  typedef LongTile<T> LT;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int nqb = (a.N + LQ - 1) / LQ;
+  const int qblk = blockIdx.x % nqb, bh = blockIdx.x / nqb, b = bh / a.H, h = bh % a.H;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
+  const size_t ldq = (size_t)3 * a.H * HD, ldo = (size_t)a.H * HD;
+  const T* qb = reinterpret_cast<const T*>(a.qkv) + (size_t)b * a.N * ldq + h * HD;
+  const T* kb = qb + a.H * HD;
+  const T* vb = kb + a.H * HD;
+  T* ob = reinterpret_cast<T*>(a.o) + (size_t)b * a.N * ldo + h * HD;
+  if (a.head_keep && a.head_keep[h] == 0) {
+    zero_rows64<T>(ob, ldo, qblk * LQ, min(a.N, qblk * LQ + LQ));
+    return;
+  }
+  const float c2 = a.scale * 1.44269504088896340736f;
+  const int q = qblk * LQ + w * 16 + li;
+  typename MM::Frag qf[G::KS];
+#pragma unroll
+  for (int ks = 0; ks < G::KS; ++ks) qf[ks] = row_frag_global<T>(qb, ldq, q, a.N, ks * 4 + g);
+  f32x4 ot[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) ot[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m_run = -INFINITY, l_run = 0.f;
+  u32x4 pk[LT::NCL], pv[LT::NCL];
+  LT::load(pk, kb, ldq, 0, a.N);
+  LT::load(pv, vb, ldq, 0, a.N);
+  LT::store(smem, pk);
+  LT::store(smem + LT::BYTES, pv);
+  __syncthreads();
+  const int nkt = (a.N + LK - 1) / LK;
+  for (int j = 0; j < nkt; ++j) {
+    const char* sK = smem + (j & 1) * 2 * LT::BYTES;
+    const char* sV = sK + LT::BYTES;
+    if (j + 1 < nkt) {
+      LT::load(pk, kb, ldq, (j + 1) * LK, a.N);
+      LT::load(pv, vb, ldq, (j + 1) * LK, a.N);
+    }
+    const int nv = a.N - j * LK;                              // valid keys in this tile (>= 1)
+    f32x4 st[LK / 16];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < LK / 16; ++t) {
+      f32x4 c = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+      if (t * 16 < nv) {                                      // (wave-uniform) tiles of padding only: no MFMAs
+        c = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < G::KS; ++ks) c = MM::mma(row_frag_lds<T>(sK, t * 16 + li, ks * 4 + g), qf[ks], c);
+        if (t * 16 + 16 > nv) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) if (t * 16 + g * 4 + e >= nv) c[e] = -INFINITY;
+        }
+      }
+      mx = fmaxf(mx, fmaxf(fmaxf(c[0], c[1]), fmaxf(c[2], c[3])));
+      st[t] = c;
+    }
+    mx = max_rows4(mx);
+    const float m_new = fmaxf(m_run, mx);                     // finite: key j * LK of the tile is a real key
+    const float mb = m_new * c2;
+    float sum = 0.f;
+#pragma unroll
+    for (int t = 0; t < LK / 16; ++t)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { const float p = __builtin_amdgcn_exp2f(st[t][e] * c2 - mb); st[t][e] = p; sum += p; }
+    sum = sum_rows4(sum);
+    const float alpha = __builtin_amdgcn_exp2f(m_run * c2 - mb);  // 0 at j = 0 (m_run = -inf), where l_run and ot are 0
+    l_run = l_run * alpha + sum;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ot[dt][e] *= alpha;
+    m_run = m_new;
+#pragma unroll
+    for (int s = 0; s < LK / MM::KSTEP; ++s) {
+      const typename MM::Frag pf = MM::pack(st[s * G::TPS], st[s * G::TPS + G::TPS - 1]);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) ot[dt] = MM::mma(TrFrag<T>::ld(sV, G::ROWB, s * MM::KSTEP, dt * 16, lane), pf, ot[dt]);
+    }
+    if (j + 1 < nkt) {
+      char* nK = smem + ((j + 1) & 1) * 2 * LT::BYTES;       // read in tile j - 1: every wave has passed the barrier behind it
+      LT::store(nK, pk);
+      LT::store(nK + LT::BYTES, pv);
+    }
+    __syncthreads();
+  }
+  if (q < a.N) {
+    const float inv = 1.0f / l_run;
+    store_tile16<T>(ob + (size_t)q * ldo, g, ot, inv);
+    if (g == 0 && a.lse) a.lse[((size_t)b * a.H + h) * a.N + q] = m_run * a.scale + __logf(l_run);
+  }
+}
+
+// backward, dQ (and delta = rowsum(dO * O)) of one query block, K / V tiles streamed
+template <typename T>
+__global__ __launch_bounds__(512) void k_attn_bwd_dq_long(AttnArgs a) {
+  typedef Mma<T> MM;
+  typedef Geom<T> G;
+  typedef LongTile<T> LT;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int nqb = (a.N + LQ - 1) / LQ;
+  const int qblk = blockIdx.x % nqb, bh = blockIdx.x / nqb, b = bh / a.H, h = bh % a.H;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
+  const size_t ldq = (size_t)3 * a.H * HD, ldo = (size_t)a.H * HD;
+  const T* qb = reinterpret_cast<const T*>(a.qkv) + (size_t)b * a.N * ldq + h * HD;
+  const T* kb = qb + a.H * HD;
+  const T* vb = kb + a.H * HD;
+  const T* ob = reinterpret_cast<const T*>(a.o) + (size_t)b * a.N * ldo + h * HD;
+  const T* dob = reinterpret_cast<const T*>(a.dout) + (size_t)b * a.N * ldo + h * HD;
+  T* dqb = reinterpret_cast<T*>(a.dqkv) + (size_t)b * a.N * ldq + h * HD;
+  if (a.head_keep && a.head_keep[h] == 0) {                 // pruned head: dO is exactly zero, so is dq
+    zero_rows64<T>(dqb, ldq, qblk * LQ, min(a.N, qblk * LQ + LQ));
+    return;
+  }
+  const int q = qblk * LQ + w * 16 + li;
+  typename MM::Frag qf[G::KS], dof[G::KS];
+  float dl = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < G::KS; ++ks) {
+    qf[ks] = row_frag_global<T>(qb, ldq, q, a.N, ks * 4 + g);
+    dof[ks] = row_frag_global<T>(dob, ldo, q, a.N, ks * 4 + g);
+    dl += frag_dot<T>(dof[ks], row_frag_global<T>(ob, ldo, q, a.N, ks * 4 + g));
+  }
+  dl = sum_rows4(dl);
+  const float c2 = a.scale * 1.44269504088896340736f;
+  const float lse2 = (q < a.N ? a.lse[((size_t)b * a.H + h) * a.N + q] : 0.f) * 1.44269504088896340736f;
+  if (q < a.N && g == 0) a.delta[((size_t)b * a.H + h) * a.N + q] = dl;
+  f32x4 dq[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  u32x4 pk[LT::NCL], pv[LT::NCL];
+  LT::load(pk, kb, ldq, 0, a.N);
+  LT::load(pv, vb, ldq, 0, a.N);
+  LT::store(smem, pk);
+  LT::store(smem + LT::BYTES, pv);
+  __syncthreads();
+  const int nkt = (a.N + LK - 1) / LK;
+  for (int j = 0; j < nkt; ++j) {
+    const char* sK = smem + (j & 1) * 2 * LT::BYTES;
+    const char* sV = sK + LT::BYTES;
+    if (j + 1 < nkt) {
+      LT::load(pk, kb, ldq, (j + 1) * LK, a.N);
+      LT::load(pv, vb, ldq, (j + 1) * LK, a.N);
+    }
+    const int nv = a.N - j * LK;
+#pragma unroll
+    for (int s = 0; s < LK / MM::KSTEP; ++s) {
+      f32x4 ds[G::TPS];
+#pragma unroll
+      for (int u = 0; u < G::TPS; ++u) {
+        const int t = s * G::TPS + u;
+        f32x4 c = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < G::KS; ++ks) {
+          c = MM::mma(row_frag_lds<T>(sK, t * 16 + li, ks * 4 + g), qf[ks], c);
+          dp = MM::mma(row_frag_lds<T>(sV, t * 16 + li, ks * 4 + g), dof[ks], dp);
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          // padded keys (zero K / V rows) are masked: their p = exp(-lse) would only multiply zero K rows, but is unbounded
+          const float p = t * 16 + g * 4 + e < nv ? __builtin_amdgcn_exp2f(c[e] * c2 - lse2) : 0.f;
+          ds[u][e] = p * ((dp[e] - dl) * a.scale);
+        }
+      }
+      const typename MM::Frag dsf = MM::pack(ds[0], ds[G::TPS - 1]);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) dq[dt] = MM::mma(TrFrag<T>::ld(sK, G::ROWB, s * MM::KSTEP, dt * 16, lane), dsf, dq[dt]);
+    }
+    if (j + 1 < nkt) {
+      char* nK = smem + ((j + 1) & 1) * 2 * LT::BYTES;
+      LT::store(nK, pk);
+      LT::store(nK + LT::BYTES, pv);
+    }
+    __syncthreads();
+  }
+  if (q < a.N) store_tile16<T>(dqb + (size_t)q * ldq, g, dq, 1.0f);
+}
+
+// backward, dK and dV of one key block, Q / dO tiles (with lse * log2(e) and delta) streamed
+template <typename T>
+__global__ __launch_bounds__(512) void k_attn_bwd_dkv_long(AttnArgs a) {
+  typedef Mma<T> MM;
+  typedef Geom<T> G;
+  typedef LongTile<T> LT;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int BUF = 2 * LT::BYTES + 2 * LK * (int)sizeof(float);   // Q, dO, lse, delta
+  const int nkb = (a.N + LQ - 1) / LQ;
+  const int kblk = blockIdx.x % nkb, bh = blockIdx.x / nkb, b = bh / a.H, h = bh % a.H;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
+  const size_t ldq = (size_t)3 * a.H * HD, ldo = (size_t)a.H * HD;
+  const T* qb = reinterpret_cast<const T*>(a.qkv) + (size_t)b * a.N * ldq + h * HD;
+  const T* kb = qb + a.H * HD;
+  const T* vb = kb + a.H * HD;
+  const T* dob = reinterpret_cast<const T*>(a.dout) + (size_t)b * a.N * ldo + h * HD;
+  T* dkb = reinterpret_cast<T*>(a.dqkv) + (size_t)b * a.N * ldq + (a.H + h) * HD;
+  T* dvb = dkb + a.H * HD;
+  const int r1 = min(a.N, kblk * LQ + LQ);
+  if (a.head_keep && a.head_keep[h] == 0) {                 // pruned head: dk = dv = 0 exactly
+    zero_rows64<T>(dkb, ldq, kblk * LQ, r1);
+    zero_rows64<T>(dvb, ldq, kblk * LQ, r1);
+    return;
+  }
+  const float* lse = a.lse + ((size_t)b * a.H + h) * a.N;
+  const float* del = a.delta + ((size_t)b * a.H + h) * a.N;
+  const int key = kblk * LQ + w * 16 + li;
+  typename MM::Frag kf[G::KS], vf[G::KS];
+#pragma unroll
+  for (int ks = 0; ks < G::KS; ++ks) {
+    kf[ks] = row_frag_global<T>(kb, ldq, key, a.N, ks * 4 + g);
+    vf[ks] = row_frag_global<T>(vb, ldq, key, a.N, ks * 4 + g);
+  }
+  f32x4 dk[4], dv[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) { dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  const float c2 = a.scale * 1.44269504088896340736f;
+  // lse pre-multiplied by log2(e), +inf on padded queries -> p = 0; threads 0 .. LK-1 carry lse, LK .. 2 LK-1 delta
+  auto ld_row = [&](int r0) -> float {
+    const int i = r0 + ((int)threadIdx.x & (LK - 1));
+    if (threadIdx.x < LK) return i < a.N ? lse[i] * 1.44269504088896340736f : INFINITY;
+    return i < a.N ? del[i] : 0.f;
+  };
+  u32x4 pq[LT::NCL], pd[LT::NCL];
+  float pr = 0.f;
+  LT::load(pq, qb, ldq, 0, a.N);
+  LT::load(pd, dob, ldo, 0, a.N);
+  if (threadIdx.x < 2 * LK) pr = ld_row(0);
+  LT::store(smem, pq);
+  LT::store(smem + LT::BYTES, pd);
+  if (threadIdx.x < 2 * LK) reinterpret_cast<float*>(smem + 2 * LT::BYTES)[threadIdx.x] = pr;
+  __syncthreads();
+  const int nqt = (a.N + LK - 1) / LK;
+  for (int j = 0; j < nqt; ++j) {
+    const char* sQ = smem + (j & 1) * BUF;
+    const char* sDO = sQ + LT::BYTES;
+    const float* sLse = reinterpret_cast<const float*>(sQ + 2 * LT::BYTES);
+    const float* sDel = sLse + LK;
+    if (j + 1 < nqt) {
+      LT::load(pq, qb, ldq, (j + 1) * LK, a.N);
+      LT::load(pd, dob, ldo, (j + 1) * LK, a.N);
+      if (threadIdx.x < 2 * LK) pr = ld_row((j + 1) * LK);
+    }
+#pragma unroll
+    for (int s = 0; s < LK / MM::KSTEP; ++s) {
+      f32x4 pp[G::TPS], ds[G::TPS];
+#pragma unroll
+      for (int u = 0; u < G::TPS; ++u) {
+        const int t = s * G::TPS + u;
+        f32x4 c = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < G::KS; ++ks) {
+          c = MM::mma(row_frag_lds<T>(sQ, t * 16 + li, ks * 4 + g), kf[ks], c);
+          dp = MM::mma(row_frag_lds<T>(sDO, t * 16 + li, ks * 4 + g), vf[ks], dp);
+        }
+        const f32x4 l4 = *reinterpret_cast<const f32x4*>(sLse + t * 16 + g * 4);
+        const f32x4 d4 = *reinterpret_cast<const f32x4*>(sDel + t * 16 + g * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float p = __builtin_amdgcn_exp2f(c[e] * c2 - l4[e]);
+          pp[u][e] = p;
+          ds[u][e] = p * ((dp[e] - d4[e]) * a.scale);
+        }
+      }
+      const typename MM::Frag pf = MM::pack(pp[0], pp[G::TPS - 1]);
+      const typename MM::Frag dsf = MM::pack(ds[0], ds[G::TPS - 1]);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        dv[dt] = MM::mma(TrFrag<T>::ld(sDO, G::ROWB, s * MM::KSTEP, dt * 16, lane), pf, dv[dt]);
+        dk[dt] = MM::mma(TrFrag<T>::ld(sQ, G::ROWB, s * MM::KSTEP, dt * 16, lane), dsf, dk[dt]);
+      }
+    }
+    if (j + 1 < nqt) {
+      char* nQ = smem + ((j + 1) & 1) * BUF;
+      LT::store(nQ, pq);
+      LT::store(nQ + LT::BYTES, pd);
+      if (threadIdx.x < 2 * LK) reinterpret_cast<float*>(nQ + 2 * LT::BYTES)[threadIdx.x] = pr;
+    }
+    __syncthreads();
+  }
+  if (key < a.N) {
+    store_tile16<T>(dkb + (size_t)key * ldq, g, dk, 1.0f);
+    store_tile16<T>(dvb + (size_t)key * ldq, g, dv, 1.0f);
+  }
+}
+
+template <typename T> int launch_long(const AttnArgs& a, int which, hipStream_t st) {
+  const int nblk = (a.N + LQ - 1) / LQ;
+  const int64_t grid = (int64_t)a.B * a.H * nblk;
+  if (grid > 0x7fffffff) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "attention: too many workgroups");
+  constexpr int SH = 2 * 2 * LongTile<T>::BYTES;
+  if (which == 0) {
+    UVC_MAX_LDS(SH, k_attn_fwd_long<T>);
+    k_attn_fwd_long<T><<<(int)grid, 512, SH, st>>>(a);
+  } else if (which == 1) {
+    UVC_MAX_LDS(SH, k_attn_bwd_dq_long<T>);
+    k_attn_bwd_dq_long<T><<<(int)grid, 512, SH, st>>>(a);
+  } else {
+    constexpr int SHD = SH + 2 * 2 * LK * (int)sizeof(float);
+    UVC_MAX_LDS(SHD, k_attn_bwd_dkv_long<T>);
+    k_attn_bwd_dkv_long<T><<<(int)grid, 512, SHD, st>>>(a);
+  }
+  UVC_CHECK_LAUNCH();
+  return UVC_OK;
+}
+
 template <typename T, int NT16> int launch(const AttnArgs& a, int which, hipStream_t st) {
   const int NP = NT16 * 16;
   size_t sh = (size_t)2 * NP * Geom<T>::ROWB;
@@ -1090,7 +1437,8 @@ template <typename T> int dispatch(const AttnArgs& a, int which, hipStream_t st)
   if (nt <= 8) return launch<T, 8>(a, which, st);
   if (nt <= 14) return launch<T, 14>(a, which, st);
   if (nt <= 16) return launch<T, 16>(a, which, st);
-  return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "attention: sequence length > 256 not supported");
+  if (a.N <= LONG_MAX_N) return launch_long<T>(a, which, st);
+  return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "attention: sequence length > 1026 not supported");
 }
 
 int check(const uvc_attn_args* p, bool bwd) {

@@ -317,6 +317,66 @@ __global__ __launch_bounds__(256) void k_patch_topk_bwd(const float* __restrict_
   const float sdl = block_sum256(dlogp, sh);
   if (ok) dscores[(size_t)b * P + t] = dlogp - psoft[(size_t)b * P + t] * sdl;
 }
+// The same two kernels for 256 < P <= 1024 (384-px images: P = 576; patch-8 models: P = 784): one workgroup of 1024 threads per image,
+// one patch per thread, identical arithmetic (only the block reductions have 16 waves to combine).
+__device__ __forceinline__ float block_sum1024(float v, float* sh) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float r[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r[i] = (sh[4 * i] + sh[4 * i + 1]) + (sh[4 * i + 2] + sh[4 * i + 3]);
+  return (r[0] + r[1]) + (r[2] + r[3]);
+}
+__device__ __forceinline__ float block_max1024(float v, float* sh) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float r = sh[0];
+#pragma unroll
+  for (int i = 1; i < 16; ++i) r = fmaxf(r, sh[i]);
+  return r;
+}
+__global__ __launch_bounds__(1024) void k_patch_topk1024(const float* __restrict__ scores, const float* __restrict__ e, float* __restrict__ mask,
+                                                         float* __restrict__ ysoft, float* __restrict__ psoft, int P, int k, float tau) {
+  __shared__ float sh[16];
+  __shared__ float yv[1024];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const bool ok = t < P;
+  const float s = ok ? scores[(size_t)b * P + t] : -INFINITY;
+  const float m1 = block_max1024(s, sh);
+  const float z1 = block_sum1024(ok ? expf(s - m1) : 0.f, sh);
+  const float logp = (s - m1) - logf(z1);
+  const float u = ok ? (logp + (-logf(e[(size_t)b * P + t]))) / tau : -INFINITY;
+  const float m2 = block_max1024(u, sh);
+  const float ex = ok ? expf(u - m2) : 0.f;
+  const float z2 = block_sum1024(ex, sh);
+  const float y = ex / z2;
+  yv[t] = ok ? y : -1.0f;
+  __syncthreads();
+  if (ok) {
+    int rank = 0;                                   // descending order, ties -> lower index first
+    for (int j = 0; j < P; ++j) { const float o = yv[j]; rank += (o > y) || (o == y && j < t); }
+    const float hard = rank < k ? 1.0f : 0.0f;
+    mask[(size_t)b * P + t] = t == 0 ? 1.0f : (hard - y) + y;
+    ysoft[(size_t)b * P + t] = y;
+    psoft[(size_t)b * P + t] = expf(logp);
+  }
+}
+__global__ __launch_bounds__(1024) void k_patch_topk1024_bwd(const float* __restrict__ dmask, const float* __restrict__ ysoft,
+                                                             const float* __restrict__ psoft, float* __restrict__ dscores, int P, float tau) {
+  __shared__ float sh[16];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const bool ok = t < P;
+  const float y = ok ? ysoft[(size_t)b * P + t] : 0.f;
+  const float dy = (ok && t != 0) ? dmask[(size_t)b * P + t] : 0.f;
+  const float ydy = block_sum1024(y * dy, sh);
+  const float dlogp = ok ? y * (dy - ydy) / tau : 0.f;
+  const float sdl = block_sum1024(dlogp, sh);
+  if (ok) dscores[(size_t)b * P + t] = dlogp - psoft[(size_t)b * P + t] * sdl;
+}
 // X[row, :] += rw[row] * w[:]   (scorer's contribution to d(patch embedding))
 template <typename T>
 __global__ __launch_bounds__(256) void k_add_outer(T* __restrict__ X, const float* __restrict__ rw, const float* __restrict__ w, int rows, int D) {
@@ -528,16 +588,18 @@ extern "C" int uvc_patch_scores(const float* pe, const float* w, const float* bi
 }
 extern "C" int uvc_patch_topk_mask(const float* scores, const float* e, float* mask, float* ysoft, float* psoft, int32_t B, int32_t P, int32_t k,
                                    float tau, void* stream) {
-  if (!scores || !e || !mask || !ysoft || !psoft || B <= 0 || P <= 0 || P > 256 || k < 0 || tau <= 0.f)
-    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_patch_topk_mask: bad argument (P <= 256, tau > 0)");
-  k_patch_topk<<<B, 256, 0, (hipStream_t)stream>>>(scores, e, mask, ysoft, psoft, P, k, tau);
+  if (!scores || !e || !mask || !ysoft || !psoft || B <= 0 || P <= 0 || P > 1024 || k < 0 || tau <= 0.f)
+    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_patch_topk_mask: bad argument (P <= 1024, tau > 0)");
+  if (P <= 256) k_patch_topk<<<B, 256, 0, (hipStream_t)stream>>>(scores, e, mask, ysoft, psoft, P, k, tau);
+  else k_patch_topk1024<<<B, 1024, 0, (hipStream_t)stream>>>(scores, e, mask, ysoft, psoft, P, k, tau);
   UVC_CHECK_LAUNCH();
   return UVC_OK;
 }
 extern "C" int uvc_patch_topk_mask_bwd(const float* dmask, const float* ysoft, const float* psoft, float* dscores, int32_t B, int32_t P, float tau,
                                        void* stream) {
-  if (!dmask || !ysoft || !psoft || !dscores || B <= 0 || P <= 0 || P > 256 || tau <= 0.f) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_patch_topk_mask_bwd: bad argument");
-  k_patch_topk_bwd<<<B, 256, 0, (hipStream_t)stream>>>(dmask, ysoft, psoft, dscores, P, tau);
+  if (!dmask || !ysoft || !psoft || !dscores || B <= 0 || P <= 0 || P > 1024 || tau <= 0.f) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_patch_topk_mask_bwd: bad argument");
+  if (P <= 256) k_patch_topk_bwd<<<B, 256, 0, (hipStream_t)stream>>>(dmask, ysoft, psoft, dscores, P, tau);
+  else k_patch_topk1024_bwd<<<B, 1024, 0, (hipStream_t)stream>>>(dmask, ysoft, psoft, dscores, P, tau);
   UVC_CHECK_LAUNCH();
   return UVC_OK;
 }

@@ -37,7 +37,7 @@ int check_cfg(const uvc_vit_cfg* c) {
   if (c->dtype != UVC_F32 && c->dtype != UVC_BF16) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit: dtype");
   if (c->num_classes <= 0 || c->num_classes % 8) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_vit: num_classes must be a positive multiple of 8");
   const int np = (c->img_size / c->patch_size) * (c->img_size / c->patch_size);
-  if (np + c->ntok > 256) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_vit: sequence length > 256");
+  if (np > 1024) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_vit: more than 1024 patches (the attention kernels take N <= 1026)");
   return UVC_OK;
 }
 

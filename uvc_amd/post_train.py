@@ -26,6 +26,7 @@ from .joint_train import count_mask, save_model
 from .losses import DistillationLoss, SoftTargetCrossEntropy, unit_gradient
 from .model_distilled import DistilledVisionTransformer
 from .optim import clip_grad_norm_, create_optimizer
+from .pos_embed import match_pos_embed
 from .scheduler import create_scheduler
 from .stage1 import CONFIGS, Stage1Trainer
 
@@ -84,13 +85,13 @@ class Stage2Trainer:
             else:
                 teacher = DistilledVisionTransformer(enable_dist=args.enable_deit, **kw)
             if teacher_state is not None:
-                teacher.load_state_dict(teacher_state, strict=False)
+                teacher.load_state_dict(match_pos_embed(teacher_state, teacher), strict=False)
             teacher.eval()
             teacher.frozen_weights = True
         self.criterion = DistillationLoss(SoftTargetCrossEntropy(), teacher, args.distillation_type,
                                           args.distillation_alpha, args.distillation_tau)          # :668-671
         if checkpoint is not None:                                                                  # :676-683
-            model.load_state_dict(checkpoint)       # `hasattr(checkpoint, 'args')` is never true for a dict: bare state_dict
+            model.load_state_dict(match_pos_embed(checkpoint, model))       # `hasattr(checkpoint, 'args')` is never true for a dict: bare state_dict
         self.model, self.teacher = model, teacher
         self.total_param = count_mask(model)
         # structured sparsity: MLP hidden units whose fc1 row and fc2 column are masked out are skipped, not multiplied

@@ -16,6 +16,7 @@ from .joint_train import count_mask, get_uvc_layers, register_masks
 from .losses import DistillationLoss, SoftTargetCrossEntropy, unit_gradient
 from .model_distilled import DistilledVisionTransformer
 from .optim import FusedAdamW, clip_grad_norm_
+from .pos_embed import match_pos_embed
 from .scheduler import PresetLRScheduler, WarmupCosineSchedule, WarmupLinearSchedule
 from .uvc_optimizer import build_minimax_model, uvc_optimizer
 from .uvc_utils import prune_w_mask
@@ -90,7 +91,7 @@ class Stage1Trainer:
             model = DistilledVisionTransformer(enable_dist=args.enable_deit, gumbel_hard=False,
                                                enable_patch_gating=args.enable_patch_gating, **kw)      # :135-140
         if student_state is not None:
-            model.load_state_dict(student_state, strict=False)
+            model.load_state_dict(match_pos_embed(student_state, model), strict=False)
         register_masks(model)                                                                       # :169-171
         args.total_param = count_mask(model)
         teacher = None
@@ -102,7 +103,7 @@ class Stage1Trainer:
                 teacher = DistilledVisionTransformer(enable_dist=args.enable_deit, **kw)
             src = teacher_state if teacher_state is not None else {k: v for k, v in model.state_dict().items()
                                                                    if not k.endswith(".mask") and k != "patch_gating"}
-            teacher.load_state_dict(src, strict=False)
+            teacher.load_state_dict(match_pos_embed(src, teacher), strict=False)
             teacher.eval()
             teacher.frozen_weights = True
         self.model, self.teacher = model, teacher
