@@ -69,7 +69,9 @@ typedef struct uvc_gemm_nt_args {
   /* optional second output of the residual epilogues where uvc_gemm_nt_ln_supported(): ln_out[M,N] (T) = LayerNorm(C rows; ln_gamma,
    * ln_beta, ln_eps) -- norm1 of the next block on the rows fc2 + residual (+ gate mix) just produced (model_distilled.py:241-244) --
    * and its float32 statistics ln_mean / ln_rstd [M] (both or neither).  Needs alpha == 1, contiguous A / R (lda == K, ldr == N).
-   * With a bf16 C the LayerNorm is taken of the ROUNDED rows (what C holds). */
+   * With a bf16 C the LayerNorm is taken of the ROUNDED rows (what C holds).  At N = 384 the fused kernel addresses A with 32-bit
+   * offsets: uvc_gemm_nt_ln_supported() is 0 once (M + 128) * K * 2 >= 2^31, and callers run the GEMM and uvc_layernorm_fwd apart.
+   * Above that bound the rows come from another GEMM kernel and can differ from the fused form's in the last bit. */
   float ln_eps;
   const float* ln_gamma; const float* ln_beta; void* ln_out; float* ln_mean; float* ln_rstd;
 } uvc_gemm_nt_args;

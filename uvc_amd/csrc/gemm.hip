@@ -1088,10 +1088,14 @@ int launch_nt8p_bf16(const NtArgs& a, int epi, int ri, hipStream_t st);
 bool nt8p_takes(const NtArgs& a, bool a_f32);
 bool row384_fwd_ok(const NtArgs& a, int epi);
 int launch_row384_fwd(const NtArgs& a, int epi, hipStream_t st);
+// k_gemm_row384_lnbwd<.., 1> addresses A with 32-bit buffer offsets, the ragged last tile's 128 rows past M included: below 2 GB.  Shared by
+// uvc_gemm_nt_ln_supported and row384_fwd_ok, so the predicate never promises a problem the call refuses
+static bool row384_fwd_fits(int64_t M, int64_t K) { return (M + 128) * K * 2 < (1ll << 31); }
 
 extern "C" int uvc_gemm_nt_ln_supported(int32_t M, int32_t N, int32_t K, int32_t dtype, int32_t epilogue) {
   // N = 384 (r4): k_gemm_row384_lnbwd<.., 1>, bf16 C / R only; its rows are bit-identical to the unfused pair, so the row threshold does not show in results
-  if (dtype == UVC_BF16 && N == 384) return M >= 4096 && K % 64 == 0 && K >= 384 && (epilogue == UVC_EPI_BIAS_RESID || epilogue == UVC_EPI_BIAS_RESID_GATE);
+  if (dtype == UVC_BF16 && N == 384)
+    return M >= 4096 && K % 64 == 0 && K >= 384 && (epilogue == UVC_EPI_BIAS_RESID || epilogue == UVC_EPI_BIAS_RESID_GATE) && row384_fwd_fits(M, K);
   if (dtype != UVC_BF16 || N != 192 || M < 16) return 0;      // any row count from 16 up: whether norm is fused must not depend on the batch
   return ((K == 768 || K == 512 || K == 256) && (epilogue == UVC_EPI_BIAS_RESID || epilogue == UVC_EPI_BIAS_RESID_GATE)) || (K == 192 && epilogue == UVC_EPI_BIAS_RESID);
 }
@@ -2518,7 +2522,7 @@ int launch_row384_lnbwd(const LnbArgs& a, int x_lowp, hipStream_t st) {
 bool row384_fwd_ok(const NtArgs& a, int epi) {
   return a.N == R3_BN && a.K % 64 == 0 && a.K >= 128 && a.lda == a.K && a.ldb == a.K && a.ldc == R3_BN && a.ldr == R3_BN &&
          (epi == UVC_EPI_BIAS_RESID || epi == UVC_EPI_BIAS_RESID_GATE) && (((uintptr_t)a.A | (uintptr_t)a.B | (uintptr_t)a.C | (uintptr_t)a.R | (uintptr_t)a.ln_out) & 15) == 0 &&
-         (size_t)(a.M + 128) * a.K * 2 < (1ull << 31);
+         row384_fwd_fits(a.M, a.K);
 }
 int launch_row384_fwd(const NtArgs& a, int epi, hipStream_t st) {
   LnbArgs b = {};
@@ -3583,9 +3587,14 @@ extern "C" int uvc_gemm_tn(const uvc_gemm_tn_args* p, void* stream) {
   int cfg = (p->dtype == UVC_BF16 && p->lda % 8 == 0 && p->ldb % 8 == 0) ? tn_config(p->N1, p->N2) : 0;
   if (cfg == 4 && p->a_is_f32) cfg = 0;                      // the 96x192 tile exists as an LDS-DMA (bf16 operands) kernel only
   if (cfg == 5 && p->a_is_f32) cfg = (p->N1 % 192 == 0 && p->N2 % 256 == 0) ? 1 : (p->N1 % 256 == 0 && p->N2 % 192 == 0) ? 2 : 0;
-  // the 256 x 256 kernel addresses its operands with 32-bit buffer offsets: beyond 2 GB the problem goes to the generic kernel (64-bit
-  // addresses; the workspace is sized for either, see uvc_gemm_tn_workspace_bytes) -- checked on the configuration that will RUN
-  if (cfg == 5 && (size_t)(p->M + 256) * (p->lda > p->ldb ? p->lda : p->ldb) * 2 >= (1ull << 31)) cfg = 0;
+  // k_gemm_tn8p (cfgs 1, 2, 3 with bf16 A outside variant 2; cfgs 5, 6) addresses its operands with 32-bit buffer offsets and marks the
+  // columns a tile lacks with offset 0x80000000: every offset, the requests up to 256 rows past a split's end included, must stay below
+  // 2 GB.  Beyond that, cfgs 1, 2, 3 take the ring kernel k_gemm_tn_dma (64-bit offsets; same tiles, splits and k order: the same bits) and
+  // the 256 x 256 tiles the generic kernel (the workspace is sized for either, see uvc_gemm_tn_workspace_bytes) -- checked on the
+  // configuration that will RUN
+  const bool tn8p_fits = (int64_t)(p->M + 256) * (p->lda > p->ldb ? p->lda : p->ldb) * 2 < (1ll << 31);
+  if (cfg == 5 && !tn8p_fits) cfg = 0;
+  const bool tn8p = tn8p_fits && p->variant != 2;
   // variant 3 (A/B, r6): 128 x 256 tiles for the shapes that take 256 x 256 -- twice the tiles, half the splits: half the float32 partial bytes (DeiT-Base dW1: 66 -> 28 MB
   // written and read back per launch) for 25 % fewer MFMAs per fragment read.  Measured (profiles/r6n_tn_variants_base.txt, GEMM + reduce, M = 25 344): dW2 141.9 -> 168.1 us,
   // dW1 131.3 -> 154.2, dWqkv 98.4 -> 110.8, dWproj 49.4 -> 44.6: not the default
@@ -3628,8 +3637,8 @@ extern "C" int uvc_gemm_tn(const uvc_gemm_tn_args* p, void* stream) {
       // operand ring ALONE 32 us, its compute ALONE (no requests) 60 us of the 68 -- [24 transposing reads | wait | 32 MFMAs] in lock step add up to ~1 900 clocks per
       // 32-row stage where either half needs ~800; k_gemm_tn8p requests a phase's fragments inside the MFMA block of the phase before: dW2 79.4 -> 64.6 us, dW1
       // 77.4 -> 60.9 (bit-identical partial tiles).  variant 2: the ring kernel.
-      else if (p->variant != 2 && cfg == 1) { UVC_MAX_LDS(T8_LDS, k_gemm_tn8p<6, 4>); k_gemm_tn8p<6, 4><<<grid, 512, T8_LDS, st>>>(a); }
-      else if (p->variant != 2 && cfg == 2) { UVC_MAX_LDS(T8_LDS, k_gemm_tn8p<8, 3>); k_gemm_tn8p<8, 3><<<grid, 512, T8_LDS, st>>>(a); }
+      else if (tn8p && cfg == 1) { UVC_MAX_LDS(T8_LDS, k_gemm_tn8p<6, 4>); k_gemm_tn8p<6, 4><<<grid, 512, T8_LDS, st>>>(a); }
+      else if (tn8p && cfg == 2) { UVC_MAX_LDS(T8_LDS, k_gemm_tn8p<8, 3>); k_gemm_tn8p<8, 3><<<grid, 512, T8_LDS, st>>>(a); }
       else if (cfg == 1) TN_DMA_ONE(192, 256, 2, 4)
       else if (cfg == 2) TN_DMA_ONE(256, 192, 4, 2)
       else if (cfg == 4) TN_DMA_ONE(96, 192, 2, 4)
@@ -3637,8 +3646,8 @@ extern "C" int uvc_gemm_tn(const uvc_gemm_tn_args* p, void* stream) {
       else if (cfg == 6) { UVC_MAX_LDS(T8_LDS, k_gemm_tn8p<4, 4>); k_gemm_tn8p<4, 4><<<grid, 512, T8_LDS, st>>>(a); }
       // 192 x 192 tiles (dW_qkv of DeiT-Tiny / Small, every block weight of T2T-ViT-14): the two-group schedule by default -- 45.9 -> 40.9 us at
       // 100 864 x 576 x 192, 67.6 -> 55.6 at 50 432 x 1152 x 384, 44 -> 37 on T2T's three shapes; bit-identical partial tiles (variant 2: the ring kernel).
-      // The 192 x 256 / 256 x 192 tiles measured equal on both kernels and stay on the ring kernel (variant 1 moves them).
-      else if (p->variant != 2 && cfg == 3) { UVC_MAX_LDS(T8_LDS, k_gemm_tn8p<6, 3>); k_gemm_tn8p<6, 3><<<grid, 512, T8_LDS, st>>>(a); }
+      // (The 192 x 256 / 256 x 192 tiles moved to the two-group schedule in r6 too, above.)  Past the 2 GB bound all three run on the ring kernel.
+      else if (tn8p && cfg == 3) { UVC_MAX_LDS(T8_LDS, k_gemm_tn8p<6, 3>); k_gemm_tn8p<6, 3><<<grid, 512, T8_LDS, st>>>(a); }
       else TN_DMA_ONE(192, 192, 2, 4)
 #undef TN_DMA_ONE
 #undef TN_BIG
