@@ -1,0 +1,71 @@
+/* C-ABI of the image input step on MI355X (libuvc_hip.so): resampling of decoded uint8 images into a normalised
+ * [B, 3, S, S] batch.
+ *
+ * The reference feeds both stages through torchvision transforms on PIL images (UVC/utils/data_utils.py:13-105):
+ * RandomResizedCrop / Resize / CenterCrop resample with PIL's Image.resize(size, BILINEAR), an antialiased triangle
+ * filter in 8-bit fixed point, then ToTensor and Normalize.  uvc_image_prep reproduces that bit for bit:
+ *   - per axis, PIL's precompute_coeffs in float64 (scale = in / out, support = max(scale, 1), ksize = 2 ceil(support) + 1,
+ *     weights tri((x + xmin - center + 0.5) / support) divided by their sum, rounded to int32 with 22 fraction bits);
+ *   - the horizontal pass first, into a uint8 intermediate of the source rows the vertical pass reads, then the vertical pass;
+ *     each accumulates in int32 from 1 << 21 and clamps with (acc >> 22) into 0..255.  Image.resize runs the vertical pass first
+ *     (two single-axis resizes) when src_h > 100 src_w and resize_h < src_h; so does this library;
+ *   - output float32 = (u8 / 255 - mean[c]) / std[c] with correctly rounded divisions (torch's ToTensor + Normalize), or the
+ *     uint8 pixels themselves.
+ * A pass whose axis is unchanged has the identity weights (1, 0), which return the input exactly: PIL skipping such a pass
+ * and this library running it give the same bytes.
+ *
+ * Each image resamples its WHOLE source (box = (0, 0, src_w, src_h)) to resize_h x resize_w and keeps the S x S window at
+ * (win_y, win_x): a random resized crop is a host-side slice of the decoded array (only the crop is uploaded) resized to
+ * S x S with window (0, 0); Resize(256) + CenterCrop(224) is a resize to the torchvision size with the centre window.
+ * Output pixels depend only on their own coefficients, so the window equals PIL's resize followed by a crop.  flip mirrors
+ * the output columns (RandomHorizontalFlip after the crop).
+ *
+ * Conventions as in uvc_kernels.h: device pointers owned by the caller, no allocation, no host sync, `stream` is a
+ * hipStream_t, int status return (0 = ok; uvc_last_error()).
+ */
+#ifndef UVC_DATA_H
+#define UVC_DATA_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* One image of a ragged batch.  The caller fills the "in" fields; uvc_image_prep_workspace completes the "out" fields on the
+ * host copy, which is then uploaded (uvc_image_prep_args.desc). */
+typedef struct uvc_image_desc {
+  int64_t src_offset;            /* in: byte offset of the image's first pixel in the packed source (HWC uint8, rows of src_w*3 bytes) */
+  int32_t src_h, src_w;          /* in: source size, >= 1 */
+  int32_t resize_h, resize_w;    /* in: size the whole source is resampled to, >= S */
+  int32_t win_y, win_x;          /* in: top-left of the S x S output window, win_y + S <= resize_h, win_x + S <= resize_w */
+  int32_t flip;                  /* in: 1 = mirror the output columns */
+  int32_t kh, kv;                /* out: taps per output column / row (PIL's ksize) */
+  int32_t span0, span;           /* out: source rows (order 0) or columns (order 1) [span0, span0 + span) the first pass covers */
+  int32_t order;                 /* out: 0 = horizontal pass first; 1 = vertical first (Image.resize does that for sources taller
+                                    than 100 x their width that shrink vertically) */
+  int64_t ws_offset;             /* out: byte offset of the image's coefficient tables and intermediate in the workspace */
+} uvc_image_desc;
+
+enum { UVC_IMAGE_OUT_F32 = 0, UVC_IMAGE_OUT_U8 = 1 };
+
+typedef struct uvc_image_prep_args {
+  const uint8_t* src;            /* packed uint8 HWC sources of all B images */
+  int64_t src_bytes;             /* bytes of src: an image reaching past it is not read (its output is left untouched) */
+  const uvc_image_desc* desc;    /* [B] device copy of the descriptors completed by uvc_image_prep_workspace */
+  void* workspace;               /* >= the bytes uvc_image_prep_workspace returned, 16-byte aligned */
+  int64_t workspace_bytes;
+  void* out;                     /* [B, 3, S, S]: float32 (UVC_IMAGE_OUT_F32) or uint8 (UVC_IMAGE_OUT_U8) */
+  float mean[3], std[3];         /* float32 per channel (F32 output only) */
+  int32_t B, S, out_dtype, reserved;
+} uvc_image_prep_args;
+
+/* Host only (no device access): checks the B descriptors against S and src_bytes, fills kh, kv, span0, span, order and ws_offset,
+ * and writes the workspace size the batch needs to *bytes. */
+int uvc_image_prep_workspace(uvc_image_desc* desc, int32_t B, int32_t S, int64_t src_bytes, int64_t* bytes);
+
+/* Three launches whatever B is: coefficient tables, first pass, second pass + flip + normalise. */
+int uvc_image_prep(const uvc_image_prep_args* args, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -22,8 +22,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # by tests/test_kernels_gpu.py).  Plain v_fma_f32 is exact, and the kernels are HBM-bound, so all files are built this way.
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-Wno-unused-value", "-Wno-unused-result",
           "-I" + os.path.join(os.path.dirname(HERE), "include")]
-# the scalar primal-dual update must round like the reference's separate float32 ops
-PER_FILE = {"uvc_engine.hip": ["-ffp-contract=off"]}
+# the scalar primal-dual update must round like the reference's separate float32 ops; the image resampling coefficients
+# must round like PIL's float64 C (include/uvc_data.h)
+PER_FILE = {"uvc_engine.hip": ["-ffp-contract=off"], "image_prep.hip": ["-ffp-contract=off"]}
 
 
 def _sources():

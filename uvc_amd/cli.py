@@ -4,10 +4,10 @@ epoch loop :330-514) on the MI355X engine.
     python -m torch.distributed.run --nproc-per-node N -m uvc_amd.cli --model_type deit_tiny_patch16_224 \\
         --budget 0.5 --enable_pruning 1 --enable_block_gating 1 --enable_patch_gating 0 ...
 
-Flag names and defaults are the reference's.  Data: the image has no torchvision/timm, so the loop
-runs on synthetic ImageNet-shaped batches (``--synthetic 1``, the default); the (x, y_soft) contract
-after mixup is what the step consumes, so a real loader + Mixup plugs in at
-``iterate_batches``.  Checkpoints ({output_dir}/{name}/{model_type}_{epoch}.pth.tar = bare state_dict
+Flag names and defaults are the reference's.  Data: ``--synthetic 1`` (the default) runs on synthetic
+ImageNet-shaped batches; ``--synthetic 0`` reads ``--dataset`` (imagenet folders train/ and val/, or the
+CIFAR python pickles) under ``--data_dir`` with ``--num_workers`` decode threads, and resamples on the GPU
+(uvc_amd/data.py), then the same odd-trim and Mixup as the synthetic path feed the (x, y_soft) step.  Checkpoints ({output_dir}/{name}/{model_type}_{epoch}.pth.tar = bare state_dict
 incl. masks) and the s_/r_/gating_ JSON side logs keep the reference layout.
 """
 from __future__ import annotations
@@ -135,8 +135,6 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.fp16:
         raise NotImplementedError("--fp16 (apex amp) is not reproduced: bf16 MFMA with float32 master weights needs no loss scaling")
-    if not args.synthetic:
-        raise NotImplementedError("real-data loading needs torchvision/timm (absent here); plug a loader into iterate_batches")
     if args.model_type.startswith("custom"):
         if not args.model_cfg:
             raise SystemExit("--model_type custom needs --model_cfg '<json>'")
@@ -150,9 +148,18 @@ def main(argv=None):
         dist.init_process_group(backend="nccl")
     torch.manual_seed(args.seed)                      # same seed on every rank (joint_train.py:191-196,914)
     args.train_batch_size = args.train_batch_size // args.gradient_accumulation_steps
+    train_loader = test_loader = None
+    if not args.synthetic:                            # get_loader (joint_train.py:272); t_total = len(train_loader) * num_epochs (:274)
+        from .data import build_loaders
+        train_loader, test_loader = build_loaders(args, rank=rank, world=world)
+        args.steps_per_epoch = train_loader.train_steps()
     tr = Stage1Trainer(args, device=device, distributed=world > 1)
     np.random.seed(args.seed)                         # Mixup draws from numpy's global RNG (set_seed, joint_train.py:191-196)
-    mixup_fn = build_mixup(args)
+    if train_loader is None:
+        mixup_fn = build_mixup(args)
+    else:                                             # over the dataset's classes; a padded head's extra columns get zero targets
+        from .data import real_mixup
+        mixup_fn = real_mixup(args)
     if rank == 0:
         print(f"mixup active: {mixup_fn is not None}")
     out_dir = os.path.join(args.output_dir, args.name)
@@ -180,7 +187,12 @@ def main(argv=None):
             print(f"Start [Epoch {epoch}] at Stage {stage}")
             print(f"[Initial Sparsity|Epoch {epoch}] Parameter size: {remained:.2f}M / {float(args.total_param):.2f}M = {remained / float(args.total_param) * 100:.2f}%")
         t0 = time.time()
-        for step, ((x, y), next_x) in enumerate(tr.lookahead(iterate_batches(args, device, rank, mixup_fn, epoch))):
+        if train_loader is None:
+            batches = iterate_batches(args, device, rank, mixup_fn, epoch)
+        else:
+            from .data import soft_batches
+            batches = soft_batches(train_loader, epoch, mixup_fn, args.smoothing, args.data_classes, args.num_classes)
+        for step, ((x, y), next_x) in enumerate(tr.lookahead(batches)):
             out = tr.step(x, y, next_x=next_x)
             if not out["stepped"]:                      # gradient accumulation: not an optimiser step yet (:417)
                 continue
@@ -196,7 +208,7 @@ def main(argv=None):
         if rank == 0:
             print("*" * 60)
             print("Epoch finished, begin validating ...")
-        val = tr.validate(iterate_eval_batches(args, device, rank))                              # :498
+        val = tr.validate(iterate_eval_batches(args, device, rank) if test_loader is None else test_loader)   # :498
         if rank == 0:
             print(f"Validation Results\nGlobal Steps: {tr.global_step}\nValid Loss: {val['loss']:2.5f}\nValid Accuracy: {val['top1']:2.5f}")
         tr.check_replicas()                                                                      # ranks still bit-identical (raises otherwise)

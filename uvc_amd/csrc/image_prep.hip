@@ -1,0 +1,266 @@
+// Image input step (include/uvc_data.h): PIL's antialiased bilinear resample of a ragged batch of uint8 HWC images, then
+// ToTensor + Normalize, into a [B, 3, S, S] batch.  Three launches per batch:
+//   k_prep_coeffs   one thread per (image, output column or row): PIL's precompute_coeffs + normalize_coeffs_8bpc in float64
+//   k_prep_pass1    the first pass into a uint8 intermediate: horizontal, one thread per (covered source row, output column), or, for
+//                   the tall sources Image.resize shrinks vertically first, vertical, one thread per (output row, covered source column)
+//   k_prep_pass2    one thread per (image, output row, output column): the other axis, flip, normalise, NCHW store
+// Built with -ffp-contract=off (uvc_amd/build.py): the float64 coefficient arithmetic must round like the C it mirrors.
+#include "common.h"
+#include "uvc_data.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int kPrecisionBits = 22;     // PIL Resample.c PRECISION_BITS (8-bit images)
+constexpr int kMaxSide = 1 << 16;      // source and resize sides: exact as float32 box coordinates, int32 index products stay small
+constexpr int kMaxS = 4096;
+
+// precompute_coeffs, per axis, with box (0, in): in0 = 0.0 so `in0 + v` is v exactly, and in1 - in0 = in.
+struct AxisFilter {
+  double scale, support, ss;
+  int ksize;
+};
+
+__host__ __device__ inline AxisFilter axis_filter(int in_size, int out_size) {
+  AxisFilter f;
+  f.scale = (double)in_size / (double)out_size;
+  const double fs = f.scale > 1.0 ? f.scale : 1.0;
+  f.support = 1.0 * fs;                // bilinear filter support 1.0
+  f.ksize = (int)ceil(f.support) * 2 + 1;
+  f.ss = 1.0 / fs;
+  return f;
+}
+
+__host__ __device__ inline void axis_bounds(const AxisFilter& f, int in_size, int xx, double& center, int& xmin, int& n) {
+  center = ((double)xx + 0.5) * f.scale;
+  int lo = (int)(center - f.support + 0.5);
+  if (lo < 0) lo = 0;
+  int hi = (int)(center + f.support + 0.5);
+  if (hi > in_size) hi = in_size;
+  xmin = lo;
+  n = hi - lo;
+}
+
+__device__ inline double tri(double x) {
+  if (x < 0.0) x = -x;
+  if (x < 1.0) return 1.0 - x;
+  return 0.0;
+}
+
+__host__ __device__ inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+
+// per-image workspace: h bounds int32[2S] | h taps int32[S*kh] | v bounds int32[2S] | v taps int32[S*kv] | (16-aligned) uint8 span*S*3
+// (order 0: [span source rows][S columns][3]; order 1: [S rows][span source columns][3])
+struct WsLayout {
+  int64_t hb, hk, vb, vk, inter, total;
+};
+
+__host__ __device__ inline WsLayout ws_layout(int S, int kh, int kv, int span) {
+  WsLayout L;
+  L.hb = 0;
+  L.hk = L.hb + 8 * (int64_t)S;
+  L.vb = L.hk + 4 * (int64_t)S * kh;
+  L.vk = L.vb + 8 * (int64_t)S;
+  L.inter = align16(L.vk + 4 * (int64_t)S * kv);
+  L.total = align16(L.inter + (int64_t)span * S * 3);
+  return L;
+}
+
+// The device trusts nothing it did not check: an image whose descriptor does not fit the buffers it was given is skipped.
+__device__ inline bool desc_ok(const uvc_image_desc& d, const uvc_image_prep_args& a) {
+  if (d.src_h < 1 || d.src_w < 1 || d.src_h > kMaxSide || d.src_w > kMaxSide) return false;
+  if (d.resize_h < a.S || d.resize_w < a.S || d.resize_h > kMaxSide || d.resize_w > kMaxSide) return false;
+  if (d.win_y < 0 || d.win_x < 0 || d.win_y > d.resize_h - a.S || d.win_x > d.resize_w - a.S) return false;
+  if (d.kh < 1 || d.kv < 1 || d.span < 1 || d.span0 < 0 || (d.order != 0 && d.order != 1)) return false;
+  if (d.span0 > (d.order ? d.src_w : d.src_h) - d.span) return false;
+  if (d.src_offset < 0 || d.src_offset > a.src_bytes - (int64_t)d.src_h * d.src_w * 3) return false;
+  const WsLayout L = ws_layout(a.S, d.kh, d.kv, d.span);
+  if (d.ws_offset < 0 || (d.ws_offset & 15) || d.ws_offset > a.workspace_bytes - L.total) return false;
+  return true;
+}
+
+__global__ void __launch_bounds__(256) k_prep_coeffs(uvc_image_prep_args a) {
+  const int b = blockIdx.y;
+  const uvc_image_desc d = a.desc[b];
+  if (!desc_ok(d, a)) return;
+  const int S = a.S;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 2 * S) return;
+  const bool horiz = t < S;
+  const int i = horiz ? t : t - S;
+  const int in_size = horiz ? d.src_w : d.src_h;
+  const int out_size = horiz ? d.resize_w : d.resize_h;
+  const int k = horiz ? d.kh : d.kv;
+  const AxisFilter f = axis_filter(in_size, out_size);
+  double center;
+  int xmin, n;
+  axis_bounds(f, in_size, (horiz ? d.win_x : d.win_y) + i, center, xmin, n);
+  if (n > k) n = k;                    // cannot happen (n <= 2 ceil(support) + 1); keeps the writes inside the table
+  if (n < 0) n = 0;
+  const WsLayout L = ws_layout(S, d.kh, d.kv, d.span);
+  uint8_t* ws = (uint8_t*)a.workspace + d.ws_offset;
+  int32_t* bounds = (int32_t*)(ws + (horiz ? L.hb : L.vb)) + 2 * i;
+  int32_t* kk = (int32_t*)(ws + (horiz ? L.hk : L.vk)) + (int64_t)i * k;
+  double ww = 0.0;
+  for (int x = 0; x < n; ++x) ww += tri((x + xmin - center + 0.5) * f.ss);
+  for (int x = 0; x < k; ++x) {
+    int32_t q = 0;
+    if (x < n) {
+      double w = tri((x + xmin - center + 0.5) * f.ss);
+      if (ww != 0.0) w /= ww;
+      q = w < 0 ? (int32_t)(-0.5 + w * (1 << kPrecisionBits)) : (int32_t)(0.5 + w * (1 << kPrecisionBits));
+    }
+    kk[x] = q;
+  }
+  int32_t lo = xmin;
+  if (horiz == (d.order == 1)) {       // the second pass's taps index the intermediate, whose first line is source line span0
+    lo -= d.span0;
+    if (lo < 0 || lo + n > d.span) {   // cannot happen (span0 / span come from the same bounds); never read outside the intermediate
+      lo = 0;
+      n = 0;
+    }
+  }
+  bounds[0] = lo;
+  bounds[1] = n;
+}
+
+__device__ inline uint8_t clip8(int32_t v) {
+  if (v >= (1 << kPrecisionBits << 8)) return 255;
+  if (v <= 0) return 0;
+  return (uint8_t)(v >> kPrecisionBits);
+}
+
+__device__ inline void mac3(const uint8_t* s, int64_t stride, const int32_t* k, int n, uint8_t* u) {
+  int32_t a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0;
+  for (int x = 0; x < n; ++x) {
+    const int32_t w = k[x];
+    const uint8_t* q = s + (int64_t)x * stride;
+    a0 += (int32_t)q[0] * w;
+    a1 += (int32_t)q[1] * w;
+    a2 += (int32_t)q[2] * w;
+  }
+  u[0] = clip8(a0);
+  u[1] = clip8(a1);
+  u[2] = clip8(a2);
+}
+
+__global__ void __launch_bounds__(256) k_prep_pass1(uvc_image_prep_args a) {
+  const int b = blockIdx.y;
+  const uvc_image_desc d = a.desc[b];
+  if (!desc_ok(d, a)) return;
+  const int S = a.S;
+  const WsLayout L = ws_layout(S, d.kh, d.kv, d.span);
+  uint8_t* ws = (uint8_t*)a.workspace + d.ws_offset;
+  uint8_t* inter = ws + L.inter;
+  const uint8_t* src = a.src + d.src_offset;
+  const int64_t row_bytes = (int64_t)d.src_w * 3;
+  const int64_t total = (int64_t)d.span * S;
+  if (d.order == 0) {                  // horizontal: intermediate [span rows][S][3], row r = source row span0 + r
+    const int32_t* hb = (const int32_t*)(ws + L.hb);
+    const int32_t* hk = (const int32_t*)(ws + L.hk);
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
+      const int r = (int)(p / S), c = (int)(p - (int64_t)r * S);
+      mac3(src + (int64_t)(d.span0 + r) * row_bytes + (int64_t)hb[2 * c] * 3, 3, hk + (int64_t)c * d.kh, hb[2 * c + 1], inter + p * 3);
+    }
+  } else {                             // vertical: intermediate [S][span columns][3], column c = source column span0 + c
+    const int32_t* vb = (const int32_t*)(ws + L.vb);
+    const int32_t* vk = (const int32_t*)(ws + L.vk);
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
+      const int r = (int)(p / d.span), c = (int)(p - (int64_t)r * d.span);
+      mac3(src + (int64_t)vb[2 * r] * row_bytes + (int64_t)(d.span0 + c) * 3, row_bytes, vk + (int64_t)r * d.kv, vb[2 * r + 1], inter + p * 3);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) k_prep_pass2(uvc_image_prep_args a) {
+  const int b = blockIdx.y;
+  const uvc_image_desc d = a.desc[b];
+  if (!desc_ok(d, a)) return;
+  const int S = a.S;
+  const WsLayout L = ws_layout(S, d.kh, d.kv, d.span);
+  const uint8_t* ws = (const uint8_t*)a.workspace + d.ws_offset;
+  const int32_t* hb = (const int32_t*)(ws + L.hb);
+  const int32_t* hk = (const int32_t*)(ws + L.hk);
+  const int32_t* vb = (const int32_t*)(ws + L.vb);
+  const int32_t* vk = (const int32_t*)(ws + L.vk);
+  const uint8_t* inter = ws + L.inter;
+  const int64_t plane = (int64_t)S * S;
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < plane; p += (int64_t)gridDim.x * blockDim.x) {
+    const int r = (int)(p / S), c = (int)(p - (int64_t)r * S);
+    const int cc = d.flip ? S - 1 - c : c;
+    uint8_t u[3];
+    if (d.order == 0)                  // vertical down intermediate column cc
+      mac3(inter + (int64_t)vb[2 * r] * S * 3 + (int64_t)cc * 3, (int64_t)S * 3, vk + (int64_t)r * d.kv, vb[2 * r + 1], u);
+    else                               // horizontal along intermediate row r
+      mac3(inter + ((int64_t)r * d.span + hb[2 * cc]) * 3, 3, hk + (int64_t)cc * d.kh, hb[2 * cc + 1], u);
+    const int64_t base = (int64_t)b * 3 * plane + p;
+    if (a.out_dtype == UVC_IMAGE_OUT_U8) {
+      uint8_t* o = (uint8_t*)a.out + base;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) o[ch * plane] = u[ch];
+    } else {
+      float* o = (float*)a.out + base;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) o[ch * plane] = __fdiv_rn(__fdiv_rn((float)u[ch], 255.0f) - a.mean[ch], a.std[ch]);
+    }
+  }
+}
+
+// workgroups per image and pass: about one pixel per thread for the S x S output (the first pass strides over its span)
+inline int pass_blocks(int S) {
+  const int64_t g = ((int64_t)S * S + 255) / 256;
+  return (int)(g < 1 ? 1 : (g > 1024 ? 1024 : g));
+}
+
+}  // namespace
+
+extern "C" int uvc_image_prep_workspace(uvc_image_desc* desc, int32_t B, int32_t S, int64_t src_bytes, int64_t* bytes) {
+  if (!desc || !bytes || B < 1 || B > 65535 || S < 1 || S > kMaxS || src_bytes < 0)
+    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep_workspace: bad argument (1 <= B <= 65535, 1 <= S <= 4096)");
+  int64_t off = 0;
+  for (int32_t b = 0; b < B; ++b) {
+    uvc_image_desc& d = desc[b];
+    if (d.src_h < 1 || d.src_w < 1 || d.src_h > kMaxSide || d.src_w > kMaxSide)
+      return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep_workspace: source sides must lie in [1, 65536]");
+    if (d.resize_h < S || d.resize_w < S || d.resize_h > kMaxSide || d.resize_w > kMaxSide)
+      return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep_workspace: resize sides must lie in [S, 65536]");
+    if (d.win_y < 0 || d.win_x < 0 || d.win_y > d.resize_h - S || d.win_x > d.resize_w - S)
+      return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep_workspace: the S x S window leaves the resized image");
+    if (d.src_offset < 0 || d.src_offset > src_bytes - (int64_t)d.src_h * d.src_w * 3)
+      return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep_workspace: an image reaches past the source buffer");
+    const AxisFilter fh = axis_filter(d.src_w, d.resize_w), fv = axis_filter(d.src_h, d.resize_h);
+    // Image.resize: `if self.size[1] > self.size[0] * 100 and size[1] < self.size[1]` resizes vertically, then horizontally
+    d.order = (d.src_h > (int64_t)d.src_w * 100 && d.resize_h < d.src_h) ? 1 : 0;
+    const AxisFilter& f1 = d.order ? fh : fv;          // the first pass covers the lines the SECOND pass's window reads
+    const int in1 = d.order ? d.src_w : d.src_h, w1 = d.order ? d.win_x : d.win_y;
+    double c;
+    int y0, n0, y1, n1;
+    axis_bounds(f1, in1, w1, c, y0, n0);
+    axis_bounds(f1, in1, w1 + S - 1, c, y1, n1);
+    d.kh = fh.ksize;
+    d.kv = fv.ksize;
+    d.span0 = y0;
+    d.span = y1 + n1 - y0;
+    if (d.span < 1 || d.span0 + d.span > in1) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep_workspace: empty span");
+    d.ws_offset = off;
+    off += ws_layout(S, d.kh, d.kv, d.span).total;
+  }
+  *bytes = off;
+  return UVC_OK;
+}
+
+extern "C" int uvc_image_prep(const uvc_image_prep_args* a, void* stream) {
+  if (!a || !a->src || !a->desc || !a->workspace || !a->out) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep: null pointer");
+  if (a->B < 1 || a->B > 65535 || a->S < 1 || a->S > kMaxS || (a->out_dtype != UVC_IMAGE_OUT_F32 && a->out_dtype != UVC_IMAGE_OUT_U8))
+    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep: bad B, S or out_dtype");
+  if (((uintptr_t)a->workspace & 15) || a->workspace_bytes < 0 || a->src_bytes < 0)
+    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep: workspace must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const uvc_image_prep_args args = *a;
+  k_prep_coeffs<<<dim3((2 * args.S + 255) / 256, args.B), 256, 0, st>>>(args);
+  k_prep_pass1<<<dim3(pass_blocks(args.S), args.B), 256, 0, st>>>(args);
+  k_prep_pass2<<<dim3(pass_blocks(args.S), args.B), 256, 0, st>>>(args);
+  UVC_CHECK_LAUNCH();
+  return UVC_OK;
+}

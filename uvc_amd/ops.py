@@ -454,3 +454,42 @@ class KeyedExpSource:
         L.check(L.lib().uvc_exp_noise(L.ptr(out), out.numel(), self.seed, self.step, self.site, L.cur_stream()), "uvc_exp_noise")
         self.site += 1
         return out
+
+
+# ---- image input step (include/uvc_data.h)
+
+def image_desc_dtype():
+    """numpy dtype with the layout of uvc_image_desc (a batch of descriptors is one structured array)."""
+    import numpy as np
+    return np.dtype(L.uvc_image_desc)
+
+
+def image_prep_workspace(desc, S: int, src_bytes: int) -> int:
+    """Completes the host descriptors ``desc`` (numpy array of image_desc_dtype(), C-contiguous) in place and returns the workspace
+    bytes the batch needs (uvc_image_prep_workspace: host only, no device access)."""
+    if desc.dtype != image_desc_dtype() or not desc.flags.c_contiguous:
+        raise L.UvcHipError("image_prep_workspace: desc must be a C-contiguous array of image_desc_dtype()")
+    out = C.c_int64(0)
+    L.check(L.lib().uvc_image_prep_workspace(desc.ctypes.data, len(desc), int(S), int(src_bytes), C.byref(out)), "uvc_image_prep_workspace")
+    return int(out.value)
+
+
+def image_prep(src, desc_dev, workspace, out, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0)):
+    """out[B, 3, S, S] (float32: (u8 / 255 - mean) / std, or uint8) = PIL-bilinear resample of the B packed uint8 HWC images in ``src``
+    described by ``desc_dev`` (uint8 device tensor holding the descriptors image_prep_workspace completed) -- three launches."""
+    _chk(src, desc_dev, workspace, out)
+    if src.dtype != torch.uint8 or desc_dev.dtype != torch.uint8 or workspace.dtype != torch.uint8:
+        raise L.UvcHipError("image_prep: src, desc and workspace are byte tensors")
+    if out.dim() != 4 or out.shape[1] != 3 or out.shape[2] != out.shape[3] or out.dtype not in (torch.float32, torch.uint8):
+        raise L.UvcHipError("image_prep: out must be [B, 3, S, S] float32 or uint8")
+    B, S = out.shape[0], out.shape[2]
+    if desc_dev.numel() != B * C.sizeof(L.uvc_image_desc):
+        raise L.UvcHipError("image_prep: desc holds a different number of images than out")
+    a = L.uvc_image_prep_args()
+    a.src, a.src_bytes, a.desc = L.ptr(src), src.numel(), L.ptr(desc_dev)
+    a.workspace, a.workspace_bytes, a.out = L.ptr(workspace), workspace.numel(), L.ptr(out)
+    a.mean[:], a.std[:] = [float(v) for v in mean], [float(v) for v in std]
+    a.B, a.S = B, S
+    a.out_dtype = L.UVC_IMAGE_OUT_U8 if out.dtype == torch.uint8 else L.UVC_IMAGE_OUT_F32
+    L.check(L.lib().uvc_image_prep(C.byref(a), L.cur_stream()), "uvc_image_prep")
+    return out

@@ -201,8 +201,9 @@ def post_training(trainer: Stage2Trainer, batches, epochs=None, valid_fn=None, l
 
 
 def main(argv=None):
-    """Synthetic-data Stage-2 run (the image has no dataset): loads a Stage-1 checkpoint and fine-tunes it."""
-    p = argparse.ArgumentParser(description="UVC Stage-2 masked fine-tune on MI355X (synthetic data)")
+    """Stage-2 run: loads a Stage-1 checkpoint and fine-tunes it on synthetic batches (``--synthetic 1``, the default) or on
+    ``--dataset`` under ``--data_dir`` (``--synthetic 0``: uvc_amd/data.py, with the reference's Mixup / CutMix, post_train.py:614-621)."""
+    p = argparse.ArgumentParser(description="UVC Stage-2 masked fine-tune on MI355X")
     d = default_args()
     for k, v in vars(d).items():
         if v is None or isinstance(v, (list, tuple)):
@@ -214,6 +215,15 @@ def main(argv=None):
     p.add_argument("--model_cfg", type=str, default=None, help="JSON dims for a --model_type outside models/configs.py (tests)")
     p.add_argument("--eval_steps", type=int, default=2, help="synthetic validation batches per epoch (valid(), post_train.py:188-234)")
     p.add_argument("--eval_batch_size", type=int, default=64)
+    p.add_argument("--synthetic", type=int, default=1, help="synthetic batches; 0 = read --dataset under --data_dir")
+    p.add_argument("--dataset", choices=["cifar10", "cifar100", "imagenet"], default="imagenet")         # post_train.py:411-414
+    p.add_argument("--data_dir", default="/ssd1/xinyu/dataset/imagenet2012")
+    p.add_argument("--num_workers", type=int, default=8, help="decode threads (at most 16)")                   # post_train.py:417
+    # Stage-2 Mixup / CutMix and smoothing (post_train.py:502,539-550): applied on the real-data path only
+    p.add_argument("--smoothing", type=float, default=0.1)
+    p.add_argument("--mixup", type=float, default=0.8); p.add_argument("--cutmix", type=float, default=1.0)
+    p.add_argument("--cutmix-minmax", type=float, nargs="+", default=None); p.add_argument("--mixup-prob", type=float, default=0.8)
+    p.add_argument("--mixup-switch-prob", type=float, default=0.5); p.add_argument("--mixup-mode", type=str, default="batch")
     args = p.parse_args(argv)
     if args.model_cfg:
         args.model_cfg = json.loads(args.model_cfg)
@@ -225,10 +235,17 @@ def main(argv=None):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.distributed.init_process_group("nccl")
         args.local_rank = local
+    train_loader = test_loader = None
+    if not args.synthetic:
+        from .data import build_loaders
+        train_loader, test_loader = build_loaders(args, rank=rank, world=world)
+        args.steps_per_epoch = train_loader.train_steps()
     ck = torch.load(args.checkpoint_dir, map_location="cpu") if args.checkpoint_dir else None
     tr = Stage2Trainer(args, device=f"cuda:{local}", checkpoint=ck, distributed=world > 1, world_size=world)
     dev = torch.device("cuda", local)
     g = torch.Generator(device=dev).manual_seed(args.seed + rank)
+    if train_loader is not None:
+        return _main_real(args, tr, train_loader, test_loader, rank, world)
 
     def batches(epoch):
         for _ in range(args.steps):
@@ -251,6 +268,40 @@ def main(argv=None):
         from .model_distilled import drop_shared_patches
         drop_shared_patches()
         return 100.0 * (hit + 1e-3) / max(n, 1)          # + epsilon: the first epoch always beats best_acc = 0 and saves (:393-397)
+
+    best = post_training(tr, batches, epochs=args.epochs, valid_fn=valid_fn if args.eval_steps > 0 else None,
+                         log=print if rank == 0 else (lambda *_: None))
+    if rank == 0:
+        print(json.dumps(dict(steps=tr.global_step, masked_params_M=float(tr.total_param), best_acc=best)))
+    if world > 1:
+        torch.distributed.destroy_process_group()
+    return tr
+
+
+def _main_real(args, tr, train_loader, test_loader, rank, world):
+    """--synthetic 0: the loop of post_train.py:326-403 on the dataset's loaders, Mixup / CutMix as the reference builds it (:614-621)."""
+    import numpy as np
+    from .data import real_mixup, soft_batches
+    np.random.seed(args.seed)                         # Mixup draws from numpy's global RNG
+    mixup_fn = real_mixup(args)
+    if rank == 0:
+        print(f"mixup active: {mixup_fn is not None}")
+
+    def batches(epoch):
+        return soft_batches(train_loader, epoch, mixup_fn, args.smoothing, args.data_classes, args.num_classes)
+
+    @torch.no_grad()
+    def valid_fn(model):
+        """valid() of post_train.py:188-234: eval-mode logits on the whole test set, top-1 in percent."""
+        model.eval()
+        hit, n = 0, 0
+        for x, t in test_loader:
+            logits, _ = model(x)
+            hit = hit + (logits.argmax(dim=1) == t).sum()
+            n += len(t)
+        from .model_distilled import drop_shared_patches
+        drop_shared_patches()
+        return 100.0 * (int(hit) + 1e-3) / max(n, 1)     # + epsilon: the first epoch always saves, as on the synthetic path
 
     best = post_training(tr, batches, epochs=args.epochs, valid_fn=valid_fn if args.eval_steps > 0 else None,
                          log=print if rank == 0 else (lambda *_: None))
