@@ -8,7 +8,9 @@ Flag names and defaults are the reference's.  Data: ``--synthetic 1`` (the defau
 ImageNet-shaped batches; ``--synthetic 0`` reads ``--dataset`` (imagenet folders train/ and val/, or the
 CIFAR python pickles) under ``--data_dir`` with ``--num_workers`` decode threads, and resamples on the GPU
 (uvc_amd/data.py), then the same odd-trim and Mixup as the synthetic path feed the (x, y_soft) step.  Checkpoints ({output_dir}/{name}/{model_type}_{epoch}.pth.tar = bare state_dict
-incl. masks) and the s_/r_/gating_ JSON side logs keep the reference layout.
+incl. masks) and the s_/r_/gating_ JSON side logs keep the reference layout.  ``--model_path`` (with ``--pretrained 1``) loads the
+student from a pretrained checkpoint and ``--teacher-path`` (default: ``--model_path``) the ``--teacher-model`` (default: the model type)
+through uvc_amd/checkpoints.py.
 """
 from __future__ import annotations
 
@@ -79,6 +81,7 @@ def build_parser():
     a("--resume", type=str, default=None, help="engine training state written by --save_state (complete: s r y p z, AdamW, schedule)")
     a("--save_state", type=int, default=1, help="also write <name>/<model>_state_<epoch>.pth.tar (resumable) next to the reference-format checkpoint")
     a("--model_cfg", type=str, default=None, help='with --model_type custom / custom_t2t: JSON dims, e.g. {"patch_size":16,"embed_dim":128,"depth":2,"num_heads":2}')
+    a("--teacher_cfg", type=str, default=None, help="with --teacher-model custom / custom_t2t: the teacher's JSON dims (its own size)")
     a("--eval_steps", type=int, default=2, help="synthetic validation batches per epoch (valid(), joint_train.py:199-246)")
     return p
 

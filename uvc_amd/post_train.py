@@ -21,6 +21,7 @@ from argparse import Namespace
 
 import torch
 
+from .checkpoints import load_pretrained
 from .ddp import DistributedDataParallel
 from .joint_train import count_mask, save_model
 from .losses import DistillationLoss, SoftTargetCrossEntropy, unit_gradient
@@ -28,7 +29,7 @@ from .model_distilled import DistilledVisionTransformer
 from .optim import clip_grad_norm_, create_optimizer
 from .pos_embed import match_pos_embed
 from .scheduler import create_scheduler
-from .stage1 import CONFIGS, Stage1Trainer
+from .stage1 import CONFIGS, Stage1Trainer, build_teacher
 
 
 def default_args(**over) -> Namespace:
@@ -76,18 +77,11 @@ def setup(args, device="cuda", model_cfg=None):
 class Stage2Trainer:
     def __init__(self, args: Namespace, device="cuda", checkpoint=None, teacher_state=None, distributed=False, world_size=1):
         self.args = args
-        args, model, kw = setup(args, device)
-        teacher = None
+        args, model, _ = setup(args, device)
+        teacher, self.teacher_source = None, None
         if args.distillation_type != "none":                                                        # :636-666
-            if "t2t" in args.model_type:                                                            # :659-660
-                from .t2t_vit import T2T_ViT
-                teacher = T2T_ViT(**kw)
-            else:
-                teacher = DistilledVisionTransformer(enable_dist=args.enable_deit, **kw)
-            if teacher_state is not None:
-                teacher.load_state_dict(match_pos_embed(teacher_state, teacher), strict=False)
-            teacher.eval()
-            teacher.frozen_weights = True
+            # --teacher-model / --teacher-path (default: the model type / --model_path); with no weights at all it keeps its init
+            teacher, self.teacher_source = build_teacher(args, device, teacher_state, verbose=getattr(args, "local_rank", -1) in (-1, 0))
         self.criterion = DistillationLoss(SoftTargetCrossEntropy(), teacher, args.distillation_type,
                                           args.distillation_alpha, args.distillation_tau)          # :668-671
         if checkpoint is not None:                                                                  # :676-683
@@ -200,6 +194,56 @@ def post_training(trainer: Stage2Trainer, batches, epochs=None, valid_fn=None, l
     return best_acc
 
 
+def synthetic_valid_fn(args, dev):
+    @torch.no_grad()
+    def valid_fn(model):
+        """valid() of post_train.py:188-234 on synthetic (x, hard label) batches: eval-mode logits, top-1 in percent."""
+        model.eval()
+        ge = torch.Generator(device=dev).manual_seed(args.seed + 77)
+        hit = n = 0
+        for _ in range(args.eval_steps):
+            x = torch.randn(args.eval_batch_size, 3, args.img_size, args.img_size, device=dev, generator=ge)
+            t = torch.randint(0, args.num_classes, (args.eval_batch_size,), device=dev, generator=ge)
+            logits, _ = model(x)
+            hit += int((logits.argmax(dim=1) == t).sum())
+            n += len(t)
+        from .model_distilled import drop_shared_patches
+        drop_shared_patches()
+        return 100.0 * (hit + 1e-3) / max(n, 1)          # + epsilon: the first epoch always beats best_acc = 0 and saves (:393-397)
+    return valid_fn
+
+
+def loader_valid_fn(test_loader):
+    @torch.no_grad()
+    def valid_fn(model):
+        """valid() of post_train.py:188-234: eval-mode logits on the whole test set, top-1 in percent."""
+        model.eval()
+        hit, n = 0, 0
+        for x, t in test_loader:
+            logits, _ = model(x)
+            hit = hit + (logits.argmax(dim=1) == t).sum()
+            n += len(t)
+        from .model_distilled import drop_shared_patches
+        drop_shared_patches()
+        return 100.0 * (int(hit) + 1e-3) / max(n, 1)     # + epsilon: the first epoch always saves, as on the synthetic path
+    return valid_fn
+
+
+def eval_model(args, device, checkpoint=None, model_path=None):
+    """--eval_only: the Stage-2 model from a Stage-1 checkpoint (strict load) or else a pretrained file (load_pretrained), masked as
+    every Stage-2 forward is (post_train.py:343-346), in eval mode."""
+    if checkpoint is None and not model_path:
+        raise SystemExit("--eval_only 1 needs --checkpoint_dir or --model_path")
+    _, model, _ = setup(args, device)
+    if checkpoint is not None:
+        model.load_state_dict(match_pos_embed(checkpoint, model))
+    else:
+        load_pretrained(model_path, model, num_classes=args.num_classes, what="model", verbose=args.local_rank in (-1, 0))
+    model.apply_masks()
+    model.eval()
+    return model
+
+
 def main(argv=None):
     """Stage-2 run: loads a Stage-1 checkpoint and fine-tunes it on synthetic batches (``--synthetic 1``, the default) or on
     ``--dataset`` under ``--data_dir`` (``--synthetic 0``: uvc_amd/data.py, with the reference's Mixup / CutMix, post_train.py:614-621)."""
@@ -224,6 +268,12 @@ def main(argv=None):
     p.add_argument("--mixup", type=float, default=0.8); p.add_argument("--cutmix", type=float, default=1.0)
     p.add_argument("--cutmix-minmax", type=float, nargs="+", default=None); p.add_argument("--mixup-prob", type=float, default=0.8)
     p.add_argument("--mixup-switch-prob", type=float, default=0.5); p.add_argument("--mixup-mode", type=str, default="batch")
+    # pretrained weights (post_train.py:422,554-556,635-640); the reference's --model_path default is a URL, and nothing is downloaded here
+    p.add_argument("--model_path", type=str, default=None, help="pretrained checkpoint: the teacher's default source, and the model of --eval_only without --checkpoint_dir")
+    p.add_argument("--teacher-model", type=str, default="", help="teacher architecture (default: --model_type)")
+    p.add_argument("--teacher-path", type=str, default="", help="teacher checkpoint (default: --model_path)")
+    p.add_argument("--teacher_cfg", type=str, default=None, help="with --teacher-model custom / custom_t2t: the teacher's JSON dims")
+    p.add_argument("--eval_only", type=int, default=0, help="1: evaluate the model once (valid()) and print the JSON line, no training")
     args = p.parse_args(argv)
     if args.model_cfg:
         args.model_cfg = json.loads(args.model_cfg)
@@ -241,8 +291,16 @@ def main(argv=None):
         train_loader, test_loader = build_loaders(args, rank=rank, world=world)
         args.steps_per_epoch = train_loader.train_steps()
     ck = torch.load(args.checkpoint_dir, map_location="cpu") if args.checkpoint_dir else None
-    tr = Stage2Trainer(args, device=f"cuda:{local}", checkpoint=ck, distributed=world > 1, world_size=world)
     dev = torch.device("cuda", local)
+    if args.eval_only:
+        model = eval_model(args, dev, ck, args.model_path)
+        acc = (loader_valid_fn(test_loader) if test_loader is not None else synthetic_valid_fn(args, dev))(model)
+        if rank == 0:
+            print(json.dumps(dict(steps=0, masked_params_M=float(count_mask(model)), best_acc=acc)))
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return model
+    tr = Stage2Trainer(args, device=f"cuda:{local}", checkpoint=ck, distributed=world > 1, world_size=world)
     g = torch.Generator(device=dev).manual_seed(args.seed + rank)
     if train_loader is not None:
         return _main_real(args, tr, train_loader, test_loader, rank, world)
@@ -253,22 +311,7 @@ def main(argv=None):
             y = torch.softmax(torch.randn(args.train_batch_size, args.num_classes, device=dev, generator=g), -1)
             yield x, y
 
-    @torch.no_grad()
-    def valid_fn(model):
-        """valid() of post_train.py:188-234 on synthetic (x, hard label) batches: eval-mode logits, top-1 in percent."""
-        model.eval()
-        ge = torch.Generator(device=dev).manual_seed(args.seed + 77)
-        hit = n = 0
-        for _ in range(args.eval_steps):
-            x = torch.randn(args.eval_batch_size, 3, args.img_size, args.img_size, device=dev, generator=ge)
-            t = torch.randint(0, args.num_classes, (args.eval_batch_size,), device=dev, generator=ge)
-            logits, _ = model(x)
-            hit += int((logits.argmax(dim=1) == t).sum())
-            n += len(t)
-        from .model_distilled import drop_shared_patches
-        drop_shared_patches()
-        return 100.0 * (hit + 1e-3) / max(n, 1)          # + epsilon: the first epoch always beats best_acc = 0 and saves (:393-397)
-
+    valid_fn = synthetic_valid_fn(args, dev)
     best = post_training(tr, batches, epochs=args.epochs, valid_fn=valid_fn if args.eval_steps > 0 else None,
                          log=print if rank == 0 else (lambda *_: None))
     if rank == 0:
@@ -290,19 +333,7 @@ def _main_real(args, tr, train_loader, test_loader, rank, world):
     def batches(epoch):
         return soft_batches(train_loader, epoch, mixup_fn, args.smoothing, args.data_classes, args.num_classes)
 
-    @torch.no_grad()
-    def valid_fn(model):
-        """valid() of post_train.py:188-234: eval-mode logits on the whole test set, top-1 in percent."""
-        model.eval()
-        hit, n = 0, 0
-        for x, t in test_loader:
-            logits, _ = model(x)
-            hit = hit + (logits.argmax(dim=1) == t).sum()
-            n += len(t)
-        from .model_distilled import drop_shared_patches
-        drop_shared_patches()
-        return 100.0 * (int(hit) + 1e-3) / max(n, 1)     # + epsilon: the first epoch always saves, as on the synthetic path
-
+    valid_fn = loader_valid_fn(test_loader)
     best = post_training(tr, batches, epochs=args.epochs, valid_fn=valid_fn if args.eval_steps > 0 else None,
                          log=print if rank == 0 else (lambda *_: None))
     if rank == 0:

@@ -5,12 +5,14 @@ build_minimax_model / uvc_optimizer, DDP) exactly in the reference's order.
 """
 from __future__ import annotations
 
+import json
 from argparse import Namespace
 from typing import Optional
 
 import torch
 
 from . import _lib as L
+from .checkpoints import load_pretrained
 from .ddp import DistributedDataParallel
 from .joint_train import count_mask, get_uvc_layers, register_masks
 from .losses import DistillationLoss, SoftTargetCrossEntropy, unit_gradient
@@ -49,6 +51,67 @@ def default_args(**over) -> Namespace:
     return Namespace(**a)
 
 
+def model_config(name, custom_cfg=None):
+    """(is_t2t, dims) of a --model_type / --teacher-model: its CONFIGS / T2T_CONFIGS entry, else ``custom_cfg`` (custom, custom_t2t:
+    a dict or its JSON)."""
+    t2t = "t2t" in name
+    table = T2T_CONFIGS if t2t else CONFIGS
+    if name in table:
+        return t2t, dict(table[name])
+    if not custom_cfg:
+        raise ValueError(f"model type {name!r} is not in this engine's configs; custom / custom_t2t take their dims as JSON")
+    return t2t, dict(json.loads(custom_cfg) if isinstance(custom_cfg, str) else custom_cfg)
+
+
+def model_kwargs(t2t, cfg, args, device):
+    """Constructor keywords of DistilledVisionTransformer / T2T_ViT for the dims ``cfg`` at the run's img_size, classes and precision."""
+    if t2t:
+        return dict(embed_dim=cfg["embed_dim"], depth=cfg["depth"], num_heads=cfg["num_heads"], mlp_ratio=cfg.get("mlp_ratio", 3.0),
+                    img_size=args.img_size, num_classes=args.num_classes, precision=args.precision, device=device)
+    return dict(patch_size=cfg["patch_size"], embed_dim=cfg["embed_dim"], depth=cfg["depth"], num_heads=cfg["num_heads"],
+                mlp_ratio=cfg.get("mlp_ratio", 4), qkv_bias=True, drop_rate=0, img_size=args.img_size,
+                num_classes=args.num_classes, precision=args.precision, device=device)
+
+
+def build_teacher(args, device, state=None, verbose=True):
+    """The frozen teacher of both stages -> (model, source).  Architecture: ``--teacher-model``'s own config (default: the student's;
+    custom / custom_t2t read ``--teacher_cfg``).  Weights: ``state`` if given (strict=False, as before), else ``--teacher-path``,
+    which defaults to ``--model_path`` (joint_train.py:946-981, post_train.py:637-666), through ``load_pretrained``.  With neither,
+    the model keeps its init (Stage 1 then copies the student into it), which needs the student's architecture.  Refused: a teacher
+    whose img_size or logit width differs from the student's (the loss compares their logits on the same images), and a teacher
+    file whose head has another class count (its logits would come from a random head)."""
+    name = getattr(args, "teacher_model", None) or args.model_type
+    path = getattr(args, "teacher_path", None) or getattr(args, "model_path", None) or None
+    tcfg = getattr(args, "teacher_cfg", None)
+    if tcfg and not name.startswith("custom"):
+        raise ValueError(f"--teacher_cfg goes with --teacher-model custom / custom_t2t, not {name}")
+    student = model_config(args.model_type, getattr(args, "model_cfg", None))
+    t2t, cfg = model_config(name, tcfg or (getattr(args, "model_cfg", None) if name == args.model_type else None))
+    img, ncls = cfg.pop("img_size", args.img_size), cfg.pop("num_classes", args.num_classes)
+    if (img, ncls) != (args.img_size, args.num_classes):
+        raise ValueError(f"teacher {name}: img_size {img} with {ncls} logits, the student {args.img_size} with {args.num_classes}: "
+                         f"the distillation loss needs both models' logits for the same images")
+    if state is None and path is None and (t2t, cfg) != student:
+        raise ValueError(f"teacher {name} differs from the student ({args.model_type}) and has no weights: pass --teacher-path")
+    kw = model_kwargs(t2t, cfg, args, device)
+    if t2t:
+        from .t2t_vit import T2T_ViT
+        teacher = T2T_ViT(**kw)                                                                     # joint_train.py:963-964
+    else:
+        teacher = DistilledVisionTransformer(enable_dist=args.enable_deit, **kw)                    # :957-958
+    if state is not None:
+        teacher.load_state_dict(match_pos_embed(state, teacher), strict=False)
+        path = None
+    elif path is not None:
+        rep = load_pretrained(path, teacher, num_classes=args.num_classes, what="teacher", verbose=verbose)
+        if rep.dropped:
+            raise ValueError(f"teacher: the head of {path} is not {args.num_classes} classes wide, so its logits would come from a random "
+                             f"head: pass a --teacher-path trained for these classes, or --distillation-type none")
+    teacher.eval()
+    teacher.frozen_weights = True
+    return teacher, dict(model=name, path=path)
+
+
 def _bits_fingerprint(t, chunk=1 << 22):
     """64-bit hash of a float32 tensor's bit pattern: sum_i (i mod 65521 + 1) * bits_i in wrapping int64 arithmetic, chunked so that
     the temporaries stay at 2 x chunk x 8 bytes whatever the model size."""
@@ -66,11 +129,7 @@ class Stage1Trainer:
         if not args.enable_pruning:
             raise TypeError("enable_pruning=0 raises in the reference (uvc_optimizer_gating signature, SURVEY.md Q7)")
         self.args = args
-        t2t = "t2t" in args.model_type                                      # joint_train.py:143-145
-        if t2t:
-            cfg = dict(T2T_CONFIGS[args.model_type]) if args.model_type in T2T_CONFIGS else dict(args.model_cfg)
-        else:
-            cfg = dict(CONFIGS[args.model_type]) if args.model_type in CONFIGS else dict(args.model_cfg)
+        t2t, cfg = model_config(args.model_type, getattr(args, "model_cfg", None))      # joint_train.py:143-145
         args.head_size = cfg["embed_dim"] // cfg["num_heads"]              # joint_train.py:883-885
         args.num_heads = cfg["num_heads"]
         args.budget = float(args.budget)
@@ -81,31 +140,25 @@ class Stage1Trainer:
             if args.enable_deit or args.enable_patch_gating == 1:
                 raise NotImplementedError("T2T-ViT has no distillation token and no patch-gating mode 1 (t2t_vit.py:168-200); "
                                           "enable_patch_gating=2 is defined in uvc_amd/t2t_vit.py")
-            kw = dict(embed_dim=cfg["embed_dim"], depth=cfg["depth"], num_heads=cfg["num_heads"], mlp_ratio=cfg.get("mlp_ratio", 3.0),
-                      img_size=args.img_size, num_classes=args.num_classes, precision=args.precision, device=device)
-            model = T2T_ViT(gumbel_hard=False, enable_patch_gating=args.enable_patch_gating, **kw)
+            model = T2T_ViT(gumbel_hard=False, enable_patch_gating=args.enable_patch_gating, **model_kwargs(t2t, cfg, args, device))
         else:
-            kw = dict(patch_size=cfg["patch_size"], embed_dim=cfg["embed_dim"], depth=cfg["depth"], num_heads=cfg["num_heads"],
-                      mlp_ratio=cfg.get("mlp_ratio", 4), qkv_bias=True, drop_rate=0, img_size=args.img_size,
-                      num_classes=args.num_classes, precision=args.precision, device=device)
             model = DistilledVisionTransformer(enable_dist=args.enable_deit, gumbel_hard=False,
-                                               enable_patch_gating=args.enable_patch_gating, **kw)      # :135-140
+                                               enable_patch_gating=args.enable_patch_gating,
+                                               **model_kwargs(t2t, cfg, args, device))                   # :135-140
+        verbose = getattr(args, "local_rank", -1) in (-1, 0)
         if student_state is not None:
             model.load_state_dict(match_pos_embed(student_state, model), strict=False)
+        elif getattr(args, "pretrained", 1) and getattr(args, "model_path", None):                  # :152-166
+            load_pretrained(args.model_path, model, num_classes=args.num_classes, what="student", verbose=verbose)
         register_masks(model)                                                                       # :169-171
         args.total_param = count_mask(model)
-        teacher = None
+        teacher, self.teacher_source = None, None
         if args.distillation_type != "none":                                                        # :948-981
-            if t2t:
-                from .t2t_vit import T2T_ViT
-                teacher = T2T_ViT(**kw)                                                             # :963-964
-            else:
-                teacher = DistilledVisionTransformer(enable_dist=args.enable_deit, **kw)
-            src = teacher_state if teacher_state is not None else {k: v for k, v in model.state_dict().items()
-                                                                   if not k.endswith(".mask") and k != "patch_gating"}
-            teacher.load_state_dict(match_pos_embed(src, teacher), strict=False)
-            teacher.eval()
-            teacher.frozen_weights = True
+            teacher, self.teacher_source = build_teacher(args, device, teacher_state, verbose)
+            if teacher_state is None and self.teacher_source["path"] is None:
+                # no teacher weights anywhere: the teacher is a copy of the student's initial weights
+                teacher.load_state_dict(match_pos_embed({k: v for k, v in model.state_dict().items()
+                                                         if not k.endswith(".mask") and k != "patch_gating"}, teacher), strict=False)
         self.model, self.teacher = model, teacher
         self.criterion = DistillationLoss(SoftTargetCrossEntropy(), teacher, args.distillation_type,
                                           args.distillation_alpha, args.distillation_tau)          # :986-988
@@ -305,12 +358,28 @@ class Stage1Trainer:
             # Gumbel / mixup draws continue where they stopped: torch CPU + this device's generator, numpy's global RNG
             rng=dict(torch_cpu=torch.get_rng_state(), torch_cuda=torch.cuda.get_rng_state(self.model._flat.device),
                      numpy=_np_rng_state()),
+            # the teacher's weights are not saved: --resume rebuilds it from its path, and load_state_dict checks it is the same one
+            teacher=self._teacher_record(),
         )
+
+    def _teacher_record(self):
+        if self.teacher is None:
+            return None
+        src = self.teacher_source
+        return dict(model=src["model"], path=src["path"], fingerprint=int(_bits_fingerprint(self.teacher._flat)))
 
     def load_state_dict(self, sd):
         if sd.get("format") != "uvc_amd.stage1.v1":
             raise ValueError("not a uvc_amd Stage-1 training state (the reference's checkpoint is the bare model state_dict: "
                              "load that with model.load_state_dict)")
+        if "teacher" in sd:
+            want, have = sd["teacher"], self._teacher_record()
+            if (want is None) != (have is None) or (want is not None and want["fingerprint"] != have["fingerprint"]):
+                def desc(t):
+                    return "none" if t is None else (f"{t['model']} from {t['path'] or 'weights not read from a file'} "
+                                                      f"(weights fingerprint {t['fingerprint'] & (2 ** 64 - 1):016x})")
+                raise ValueError(f"the training state was made with teacher {desc(want)}, this run's teacher is {desc(have)}: the run "
+                                 f"cannot continue bit for bit; resume with that teacher's --teacher-model / --teacher-path")
         mm, opt = self.minimax, self.optimizer
         self.model.load_state_dict(sd["model"])
         u = sd["uvc"]
