@@ -125,6 +125,9 @@ typedef struct uvc_attn_args {
                         k_attn_bwd_one, otherwise the dq + dk/dv pair); 1 = the pair; 2 = the one-pass kernel or UVC_ERR_UNSUPPORTED */
   int32_t grid;      /* backward, one-pass kernel: 0 = one persistent workgroup per CU; > 0 = that many (tests: several heads per workgroup
                         at small B * H) */
+  int32_t v_dim;     /* forward only.  0: the layout above.  16 / 32 / 48 / 64: a compact model's value head dim -- qkv rows [B, N, H*64 (q) | H*64 (k) |
+                        H*v_dim (v)], o [B, N, H*v_dim], lse as above; q / k keep 64 dims.  64 is the layout above and runs its kernels.  Other values:
+                        UVC_ERR_ARG; with uvc_attention_bwd or head_keep: UVC_ERR_UNSUPPORTED */
 } uvc_attn_args;
 int uvc_attention_fwd(const uvc_attn_args* args, void* stream);
 int uvc_attention_bwd(const uvc_attn_args* args, void* stream);

@@ -154,6 +154,29 @@ typedef struct uvc_vit_io {
 int uvc_vit_forward(const uvc_vit_cfg* cfg, const uvc_vit_io* io, void* stream);
 int uvc_vit_backward(const uvc_vit_cfg* cfg, const uvc_vit_io* io, void* stream);
 
+/* ---- compact models (uvc_amd/compact.py): a pruned DeiT exported at its kept widths, no-grad forward only ----
+ * Block k of the export (one per block of the source model that runs) keeps `heads` heads with q / k of 64 dims and `v_dim` value dims each
+ * (16, 32, 48 or 64; 0 when heads == 0), and `hidden` MLP units (a multiple of 16; may be 0).  The embedding, final norm and heads keep
+ * the shapes of the dense model described by `cfg` (embed_dim, patch, classes, ntok, dtype, ln_eps; cfg.depth, num_heads and hidden
+ * are those of the source model and bound the blocks: nblocks <= depth, heads <= num_heads, hidden <= cfg.hidden).
+ * Per block: qkv.w [heads * (128 + v_dim), D] with rows [q heads*64 | k heads*64 | v heads*v_dim], qkv.b likewise; proj.w
+ * [D, heads * v_dim]; fc1.w [hidden, D]; fc2.w [D, hidden]; the LayerNorms and biases of D as in the dense model.  A block with
+ * heads == 0 adds proj.b to its rows, one with hidden == 0 adds fc2.b. */
+typedef struct uvc_compact_block { int32_t heads, v_dim, hidden, reserved; } uvc_compact_block;
+/* The flat float32 parameter layout (off: blk[k] for k < nblocks in the slot order of uvc_vit_offsets, cls / dist / pos / patch / norm /
+ * heads and patch_gating as uvc_vit_layout; gate, gumbel and skip slots -1) and the bf16 shadow layout (soff: blk_w[k][0..3] = qkv, proj,
+ * fc1, fc2 [out, in]; no transposed copies, blk_wt = -1).  Every tensor 16-byte aligned.  Either pointer may be NULL. */
+int uvc_vit_compact_layout(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, uvc_vit_offsets* off,
+                           uvc_vit_shadow_offsets* soff);
+int64_t uvc_vit_compact_workspace_bytes(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int32_t batch);
+/* refresh the bf16 shadows (the [out, in] GEMM operands) from the float32 parameters; a no-op in float32 mode */
+int uvc_vit_compact_update_shadows(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const float* params, void* shadow,
+                                   void* stream);
+/* eval forward (model_distilled.py:429-531 in eval mode, every block of the export runs): logits and, with ntok == 2, logits_dist.
+ * Reads io->params, shadow (bf16), workspace, x, logits, logits_dist, patch_mask (optional device [B, P]), patches_in (optional), batch;
+ * the other members are ignored.  cfg.dtype UVC_F32 or UVC_BF16 (cfg.resid_f32 = 0). */
+int uvc_vit_compact_forward(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,7 +57,12 @@ class uvc_gemm_tn_args(C.Structure):
 class uvc_attn_args(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("qkv", "o", "lse", "dout", "dqkv", "delta")] + \
                [(n, C.c_int32) for n in ("B", "N", "H", "head_dim", "dtype")] + [("scale", C.c_float), ("head_keep", C.c_void_p),
-                                                                                ("variant", C.c_int32), ("grid", C.c_int32)]
+                                                                                ("variant", C.c_int32), ("grid", C.c_int32),
+                                                                                ("v_dim", C.c_int32)]
+
+
+class uvc_compact_block(C.Structure):          # include/uvc_vit.h
+    _fields_ = [(n, C.c_int32) for n in ("heads", "v_dim", "hidden", "reserved")]
 
 
 class uvc_qkv_attn_args(C.Structure):
@@ -230,7 +235,8 @@ _SIGNATURES = {
 
 # include/uvc_vit.h (bound in uvc_amd/model_distilled.py next to its ctypes structures)
 VIT_SYMBOLS = ["uvc_vit_layout", "uvc_vit_workspace_bytes", "uvc_vit_ws_offsets", "uvc_vit_update_shadows", "uvc_vit_forward",
-               "uvc_vit_backward"]
+               "uvc_vit_backward", "uvc_vit_compact_layout", "uvc_vit_compact_workspace_bytes", "uvc_vit_compact_update_shadows",
+               "uvc_vit_compact_forward"]   # (the compact-model entry points: bound in uvc_amd/compact.py)
 
 
 def side_stream(device, priority_class=None):

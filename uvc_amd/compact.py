@@ -1,0 +1,511 @@
+"""Compact models: a pruned DeiT exported at its kept widths, and an inference module that runs it on MI355X.
+
+UVC's masks define a smaller network than the dense model that carries them (uvc_utils.py:409-471): heads removed, value dims
+removed inside the kept heads, MLP units removed, blocks skipped.  Every removed term meets only exact zeros of the masked
+weights, so dropping it changes nothing but the summation order:
+
+- value dim c of a block: its ``attn.proj`` mask column c is all zero -> v-row ``2D + c`` of ``attn.qkv`` and proj column c go;
+- head h: all 64 of its proj mask columns are zero -> its q, k, v rows and proj columns go (q and k of kept heads keep 64 dims);
+- MLP unit j: the ``mlp.fc2`` mask column j is all zero -> fc1 row j, ``b1[j]`` and fc2 column j go;
+- block i: skipped where the Stage-2 eval skips it (``block_skip_gating[i][1] <= [i][0]``, model_distilled.py:496-500).
+
+Padding is exact too: a block's value width ``v_dim`` is the largest kept-dim count of its kept heads rounded up to 16 (heads
+with fewer dims get zero v-rows and zero proj columns); the MLP width is rounded up to ``mlp_multiple`` with zero fc1 rows,
+zero ``b1`` and zero fc2 columns (GELU(0) = 0 meets a zero column).
+
+    python -m uvc_amd.compact export --model_type ... --checkpoint_dir CK --output model.compact.pt
+    python -m uvc_amd.compact eval --compact model.compact.pt [--synthetic 0 --dataset ... --data_dir ...]
+
+``reference_forward`` is the written spec of the format (plain PyTorch, CPU or GPU, any dtype); ``CompactVisionTransformer``
+runs it through ``uvc_vit_compact_forward`` (include/uvc_vit.h).
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import math
+from typing import Dict, List, Mapping, Optional
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+FORMAT, VERSION = "uvc-compact-vit", 1
+HEAD_DIM = 64
+# MLP widths are rounded up to this multiple (zero padding is exact).  64 keeps the padding small; see DESIGN.md section 8 for
+# which GEMM kernel each compact width selects.
+MLP_MULTIPLE = 64
+
+
+def _state_of(model):
+    """(state dict, patch_hard) of a dense model or of a state dict (its ``*.mask`` entries included)."""
+    if isinstance(model, Mapping):
+        sd, hard = dict(model), False
+    else:
+        if type(model).__name__ == "T2T_ViT" or hasattr(model, "tokens_to_token"):
+            raise NotImplementedError("compact export of T2T-ViT models (their tokens-to-token front end) is not supported")
+        sd, hard = model.state_dict(), bool(getattr(model, "patch_hard", False))
+    if any(k.startswith("tokens_to_token.") for k in sd):
+        raise NotImplementedError("compact export of T2T-ViT models (their tokens-to-token front end) is not supported")
+    return {k: v.detach().float().cpu() for k, v in sd.items()}, hard
+
+
+def _cfg_of(sd, patch_hard):
+    D = sd["cls_token"].shape[-1]
+    pw = sd["patch_embed.proj.weight"]
+    ntok = 2 if "dist_token" in sd else 1
+    npatch = sd["pos_embed"].shape[1] - ntok
+    side = int(round(math.sqrt(npatch)))
+    depth = sd["block_skip_gating"].shape[0]
+    if D % HEAD_DIM:
+        raise ValueError("compact models need head_dim 64 (embed_dim % 64 == 0)")
+    return dict(img_size=side * pw.shape[-1], patch_size=pw.shape[-1], in_chans=pw.shape[1], num_classes=sd["head.weight"].shape[0],
+                embed_dim=D, depth=depth, num_heads=D // HEAD_DIM, hidden=sd["blocks.0.mlp.fc1.weight"].shape[0], enable_dist=int(ntok == 2),
+                patch_gating=int("patch_gating" in sd), patch_hard=int(bool(patch_hard)), ln_eps=1e-6)
+
+
+def _masked(sd, name):
+    """``weight * mask`` (post_train.py:343-346) of a module's weight; other tensors as they are."""
+    t = sd[name]
+    if name.endswith(".weight"):
+        m = sd.get(name[: -len("weight")] + "mask")
+        if m is not None:
+            t = t * m
+    return t
+
+
+def _round_up(n, m):
+    return -(-n // m) * m
+
+
+def compact_plan(model, mlp_multiple: int = MLP_MULTIPLE) -> dict:
+    """The compact model the masks of a dense model imply (after ``apply_masks()``).  ``model``: a DistilledVisionTransformer, or a
+    state dict with its ``*.mask`` buffers.  Per source block: whether it runs, the kept heads, each kept head's kept value dims, the
+    padded value width ``v_dim`` (16 / 32 / 48 / 64, 0 without heads), the kept MLP units and the padded hidden width."""
+    sd, hard = _state_of(model)
+    cfg = _cfg_of(sd, hard)
+    cfg["mlp_multiple"] = int(mlp_multiple)
+    D, H, Fh = cfg["embed_dim"], cfg["num_heads"], cfg["hidden"]
+    blocks = []
+    for i in range(cfg["depth"]):
+        p = f"blocks.{i}."
+        g = sd["block_skip_gating"][i]
+        mp = sd.get(p + "attn.proj.mask")
+        cols = torch.ones(D, dtype=torch.bool) if mp is None else (mp != 0).any(dim=0)
+        heads, v_index = [], []
+        for h in range(H):
+            dims = torch.nonzero(cols[h * HEAD_DIM:(h + 1) * HEAD_DIM]).flatten().tolist()
+            if dims:
+                heads.append(h)
+                v_index.append(dims)
+        v_dim = _round_up(max(len(v) for v in v_index), 16) if heads else 0
+        m2 = sd.get(p + "mlp.fc2.mask")
+        units = torch.ones(Fh, dtype=torch.bool) if m2 is None else (m2 != 0).any(dim=0)
+        hidden_index = torch.nonzero(units).flatten().tolist()
+        hidden = min(Fh, _round_up(len(hidden_index), mlp_multiple)) if hidden_index else 0
+        blocks.append(dict(source=i, runs=bool(g[1] > g[0]), heads=heads, v_index=v_index, v_dim=v_dim, hidden_index=hidden_index,
+                           hidden=hidden))
+    return dict(cfg=cfg, blocks=blocks)
+
+
+def export_compact(model, plan: Optional[dict] = None) -> dict:
+    """The self-describing compact file (``torch.save`` it): ``{"format", "version", "cfg", "blocks", "state_dict"}``.  state_dict
+    names as the dense model's, blocks renumbered over the blocks that run, compact shapes, masks applied; no masks, gate logits or
+    ``gumbel.*``; ``patch_gating`` kept when patch-gating mode 1 is on."""
+    sd, _ = _state_of(model)
+    plan = plan or compact_plan(model)
+    cfg = dict(plan["cfg"])
+    D = cfg["embed_dim"]
+    out: Dict[str, torch.Tensor] = {}
+    for k in ("cls_token", "dist_token", "pos_embed", "patch_gating", "patch_embed.proj.weight", "patch_embed.proj.bias", "norm.weight",
+              "norm.bias", "head.weight", "head.bias", "head_dist.weight", "head_dist.bias"):
+        if k in sd:
+            out[k] = _masked(sd, k).clone()
+    blocks = []
+    for b in plan["blocks"]:
+        if not b["runs"]:
+            continue
+        k, p = len(blocks), f"blocks.{b['source']}."
+        q = f"blocks.{k}."
+        for n in ("norm1.weight", "norm1.bias", "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc2.bias"):
+            out[q + n] = _masked(sd, p + n).clone()
+        wq, bq, wp = _masked(sd, p + "attn.qkv.weight"), sd[p + "attn.qkv.bias"], _masked(sd, p + "attn.proj.weight")
+        hs, dv = b["heads"], b["v_dim"]
+        nh = len(hs)
+        qkv_w, qkv_b = torch.zeros(nh * (128 + dv), D), torch.zeros(nh * (128 + dv))
+        proj_w = torch.zeros(D, nh * dv)
+        for j, (h, dims) in enumerate(zip(hs, b["v_index"])):
+            for s in (0, 1):                                   # q, k: all 64 dims
+                qkv_w[s * nh * 64 + j * 64:s * nh * 64 + (j + 1) * 64] = wq[s * D + h * 64:s * D + (h + 1) * 64]
+                qkv_b[s * nh * 64 + j * 64:s * nh * 64 + (j + 1) * 64] = bq[s * D + h * 64:s * D + (h + 1) * 64]
+            src = torch.tensor([2 * D + h * 64 + c for c in dims], dtype=torch.long)
+            dst = 2 * nh * 64 + j * dv + torch.arange(len(dims))
+            qkv_w[dst], qkv_b[dst] = wq[src], bq[src]
+            proj_w[:, j * dv + torch.arange(len(dims))] = wp[:, torch.tensor([h * 64 + c for c in dims], dtype=torch.long)]
+        out[q + "attn.qkv.weight"], out[q + "attn.qkv.bias"], out[q + "attn.proj.weight"] = qkv_w, qkv_b, proj_w
+        idx = torch.tensor(b["hidden_index"], dtype=torch.long)
+        Fk = b["hidden"]
+        w1, b1, w2 = torch.zeros(Fk, D), torch.zeros(Fk), torch.zeros(D, Fk)
+        if len(idx):
+            w1[:len(idx)] = _masked(sd, p + "mlp.fc1.weight")[idx]
+            b1[:len(idx)] = sd[p + "mlp.fc1.bias"][idx]
+            w2[:, :len(idx)] = _masked(sd, p + "mlp.fc2.weight")[:, idx]
+        out[q + "mlp.fc1.weight"], out[q + "mlp.fc1.bias"], out[q + "mlp.fc2.weight"] = w1, b1, w2
+        blocks.append(dict(source=b["source"], heads=list(hs), v_index=[list(v) for v in b["v_index"]], v_dim=dv,
+                           hidden_index=list(b["hidden_index"]), hidden=Fk))
+    return dict(format=FORMAT, version=VERSION, cfg=cfg, blocks=blocks, state_dict=out)
+
+
+def check_export(export: dict) -> dict:
+    if not isinstance(export, dict) or export.get("format") != FORMAT:
+        raise ValueError(f"not a {FORMAT} file")
+    if export.get("version") != VERSION:
+        raise ValueError(f"{FORMAT} version {export.get('version')} is not supported (this build reads version {VERSION})")
+    return export
+
+
+def load_compact(path) -> dict:
+    return check_export(torch.load(path, map_location="cpu"))
+
+
+def reference_forward(export: dict, x: torch.Tensor) -> torch.Tensor:
+    """Eval logits of a compact model in plain PyTorch, in x's dtype and on x's device: the written spec of the format (the Stage-2 eval
+    forward of model_distilled.py:429-531 at the kept widths; ``(x + x_dist) / 2`` with the distillation token)."""
+    check_export(export)
+    cfg = export["cfg"]
+    P = {k: v.to(device=x.device, dtype=x.dtype) for k, v in export["state_dict"].items()}
+    B, D, eps = x.shape[0], cfg["embed_dim"], cfg["ln_eps"]
+    t = F.conv2d(x, P["patch_embed.proj.weight"], P["patch_embed.proj.bias"], stride=cfg["patch_size"]).flatten(2).transpose(1, 2)
+    if cfg["patch_gating"]:                                               # mode 1 (:434-444)
+        pg = torch.sigmoid(P["patch_gating"])
+        if cfg["patch_hard"]:
+            m = (pg >= 0.5).to(t.dtype).clone()
+            m[:, 0] = 1
+            t = t * m
+        else:
+            t = t * pg
+    toks = [P["cls_token"].expand(B, -1, -1)] + ([P["dist_token"].expand(B, -1, -1)] if cfg["enable_dist"] else [])
+    h = torch.cat(toks + [t], dim=1) + P["pos_embed"]
+    N = h.shape[1]
+    for k, b in enumerate(export["blocks"]):
+        p = f"blocks.{k}."
+        nh, dv = len(b["heads"]), b["v_dim"]
+        if nh:
+            a = F.layer_norm(h, (D,), P[p + "norm1.weight"], P[p + "norm1.bias"], eps)
+            qkv = F.linear(a, P[p + "attn.qkv.weight"], P[p + "attn.qkv.bias"])
+            q = qkv[..., :nh * 64].reshape(B, N, nh, 64).transpose(1, 2)
+            kk = qkv[..., nh * 64:2 * nh * 64].reshape(B, N, nh, 64).transpose(1, 2)
+            v = qkv[..., 2 * nh * 64:].reshape(B, N, nh, dv).transpose(1, 2)
+            att = ((q @ kk.transpose(-2, -1)) * HEAD_DIM ** -0.5).softmax(dim=-1)
+            o = (att @ v).transpose(1, 2).reshape(B, N, nh * dv)
+            h = h + F.linear(o, P[p + "attn.proj.weight"], P[p + "attn.proj.bias"])
+        else:                                                             # no kept head: the branch is proj.bias
+            h = h + P[p + "attn.proj.bias"]
+        if b["hidden"]:
+            m = F.layer_norm(h, (D,), P[p + "norm2.weight"], P[p + "norm2.bias"], eps)
+            m = F.gelu(F.linear(m, P[p + "mlp.fc1.weight"], P[p + "mlp.fc1.bias"]))
+            h = h + F.linear(m, P[p + "mlp.fc2.weight"], P[p + "mlp.fc2.bias"])
+        else:                                                             # no kept unit: the branch is fc2.bias
+            h = h + P[p + "mlp.fc2.bias"]
+    h = F.layer_norm(h, (D,), P["norm.weight"], P["norm.bias"], eps)
+    o = F.linear(h[:, 0], P["head.weight"], P["head.bias"])
+    od = F.linear(h[:, 1], P["head_dist.weight"], P["head_dist.bias"]) if cfg["enable_dist"] else o
+    return (o + od) / 2
+
+
+# ---- MAC bookkeeping (oracle/vit.py:mac_table with per-block widths) ------------------------------------------------------------
+def _seq(cfg):
+    return (cfg["img_size"] // cfg["patch_size"]) ** 2 + (2 if cfg["enable_dist"] else 1)
+
+
+def _block_macs(cfg, B, H, v_cols, F_):
+    """qkv, q k^T, p v, proj, fc1, fc2 of one block: H heads of 64 q / k dims, v_cols value columns in all, F_ units."""
+    N, D = _seq(cfg), cfg["embed_dim"]
+    return [B * N * D * (2 * H * 64 + v_cols), N * B * H * N * 64, N * B * N * v_cols, B * N * D * v_cols, F_ * B * N * D, D * B * N * F_]
+
+
+def embed_macs(cfg, B=1):
+    P = (cfg["img_size"] // cfg["patch_size"]) ** 2
+    return B * P * cfg["embed_dim"] * cfg["patch_size"] ** 2 * cfg["in_chans"]
+
+
+def full_macs(cfg, B=1) -> int:
+    """The dense model's MACs (every block runs)."""
+    D, H = cfg["embed_dim"], cfg["num_heads"]
+    return embed_macs(cfg, B) + cfg["depth"] * sum(_block_macs(cfg, B, H, D, cfg["hidden"]))
+
+
+def compact_macs(export_or_plan: dict, B=1, padded=True) -> int:
+    """MACs of the compact model: with ``padded`` the widths it runs (H_l heads of v_dim value dims, the padded hidden width), else
+    the widths the masks imply (every kept head's own kept dims, the kept units) -- comparable to Stage 1's "Real FLOPs"."""
+    cfg = export_or_plan["cfg"]
+    total = embed_macs(cfg, B)
+    for b in export_or_plan["blocks"]:
+        if not b.get("runs", True):
+            continue
+        H = len(b["heads"])
+        v = H * b["v_dim"] if padded else sum(len(d) for d in b["v_index"])
+        f = b["hidden"] if padded else len(b["hidden_index"])
+        total += sum(_block_macs(cfg, B, H, v, f))
+    return int(total)
+
+
+# ---- seeded synthetic masks (tests and tools/compact_eval_time.py) ----------------------------------------------------------------
+def synthetic_masks(depth, embed_dim, hidden, seed=0, keep=0.5):
+    """A mask set that keeps about ``keep`` of a DeiT's block MACs and produces every case of the format: pruned heads, partial value
+    dims (v_dim 16 / 32 / 48 across blocks), pruned MLP units (kept widths off the multiple) and two skipped blocks (depth >= 6).
+    Returns {state_dict key: tensor} for ``attn.proj.mask``, ``mlp.fc1.mask``, ``mlp.fc2.mask`` and ``block_skip_gating``."""
+    g = torch.Generator().manual_seed(seed)
+    H, D = embed_dim // HEAD_DIM, embed_dim
+    out = {}
+    gate = torch.tensor([-1.0, 1.0]).repeat(depth, 1)
+    skipped = {depth // 3, (2 * depth) // 3} if depth >= 6 else set()
+    for i in skipped:
+        gate[i] = torch.tensor([1.0, -1.0])
+    out["block_skip_gating"] = gate
+    dv_cycle = [48, 32, 16, 64]
+    for i in range(depth):
+        p = f"blocks.{i}."
+        pm = torch.zeros(D, D)
+        nkeep = max(1, H - max(1, H // 4)) if H > 1 else 1
+        heads = sorted(torch.randperm(H, generator=g)[:nkeep].tolist())
+        dv = dv_cycle[i % len(dv_cycle)]
+        for j, h in enumerate(heads):
+            nd = dv - (j % 2) * 5 if dv > 16 else dv - (j % 2) * 3     # kept dims below the padded width for some heads
+            dims = torch.randperm(64, generator=g)[:nd]
+            pm[:, h * 64 + dims] = 1.0
+        out[p + "attn.proj.mask"] = pm
+        nunit = max(1, int(round(hidden * keep)) - 37 * (i % 2))
+        units = torch.randperm(hidden, generator=g)[:nunit]
+        m2 = torch.zeros(D, hidden)
+        m2[:, units] = 1.0
+        out[p + "mlp.fc2.mask"] = m2
+        out[p + "mlp.fc1.mask"] = torch.ones(hidden, D)                   # live fc1 rows: the unit still goes (fc2 column decides)
+    return out
+
+
+def apply_synthetic_masks(model, masks):
+    """Load ``masks`` into a dense model's mask buffers (registering them where missing) and its gate logits, then apply them."""
+    from .post_train import register_masks
+    register_masks(model)
+    sd = model.state_dict()
+    for k, v in masks.items():
+        sd[k] = v.to(sd[k].dtype)
+    model.load_state_dict(sd)
+    model.apply_masks()
+    return model
+
+
+# ---- the MI355X module ----------------------------------------------------------------------------------------------------------
+_BOUND = False
+
+
+def _bind():
+    global _BOUND
+    from . import _lib as L
+    from .model_distilled import uvc_vit_cfg, uvc_vit_io, uvc_vit_offsets, uvc_vit_shadow_offsets
+    lib = L.lib()
+    if not _BOUND:
+        B = C.POINTER(L.uvc_compact_block)
+        lib.uvc_vit_compact_layout.argtypes = [C.POINTER(uvc_vit_cfg), B, C.c_int32, C.POINTER(uvc_vit_offsets), C.POINTER(uvc_vit_shadow_offsets)]
+        lib.uvc_vit_compact_workspace_bytes.argtypes = [C.POINTER(uvc_vit_cfg), B, C.c_int32, C.c_int32]
+        lib.uvc_vit_compact_workspace_bytes.restype = C.c_int64
+        lib.uvc_vit_compact_update_shadows.argtypes = [C.POINTER(uvc_vit_cfg), B, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.uvc_vit_compact_forward.argtypes = [C.POINTER(uvc_vit_cfg), B, C.c_int32, C.POINTER(uvc_vit_io), C.c_void_p]
+        for n in ("uvc_vit_compact_layout", "uvc_vit_compact_update_shadows", "uvc_vit_compact_forward"):
+            getattr(lib, n).restype = C.c_int
+        _BOUND = True
+    return lib
+
+
+class CompactVisionTransformer(nn.Module):
+    """Inference-only compact DeiT over ONE flat float32 parameter buffer (uvc_vit_compact_layout).  ``forward(x)`` returns the eval
+    logits (``(x + x_dist) / 2`` with the distillation token) and the compact model's MACs, as the dense model's eval forward does."""
+
+    def __init__(self, export: dict, precision: str = "bf16", device=None):
+        super().__init__()
+        from . import _lib as L
+        from . import ops
+        from .model_distilled import uvc_vit_cfg, uvc_vit_offsets, uvc_vit_shadow_offsets
+        check_export(export)
+        if precision == "bf16_f32resid":
+            raise NotImplementedError("compact models run in 'bf16' or 'fp32'")
+        if precision not in ("bf16", "fp32"):
+            raise ValueError("precision must be 'bf16' or 'fp32'")
+        dev = torch.device(device if device is not None else "cuda")
+        if dev.type != "cuda":
+            raise L.UvcHipError("uvc_amd models run on MI355X only (no CPU fallback)")
+        self.export, self.precision = export, precision
+        c = export["cfg"]
+        self.num_tokens = 2 if c["enable_dist"] else 1
+        self._cfg = uvc_vit_cfg(c["img_size"], c["patch_size"], c["in_chans"], c["num_classes"], c["embed_dim"], c["depth"], c["num_heads"],
+                                c["hidden"], self.num_tokens, ops.UVC_F32 if precision == "fp32" else ops.UVC_BF16)
+        self._cfg.ln_eps = float(c["ln_eps"])
+        nb = len(export["blocks"])
+        self._blocks = (L.uvc_compact_block * max(1, nb))()
+        for k, b in enumerate(export["blocks"]):
+            self._blocks[k].heads, self._blocks[k].v_dim, self._blocks[k].hidden = len(b["heads"]), b["v_dim"], b["hidden"]
+        self._nb = nb
+        self._off, self._soff = uvc_vit_offsets(), uvc_vit_shadow_offsets()
+        lib = _bind()
+        L.check(lib.uvc_vit_compact_layout(C.byref(self._cfg), self._blocks, nb, C.byref(self._off), C.byref(self._soff)), "uvc_vit_compact_layout")
+        flat = torch.zeros(self._off.n_total, dtype=torch.float32)
+        for name, t in export["state_dict"].items():
+            o = self._offset(name)
+            flat[o:o + t.numel()] = t.reshape(-1).float()
+        self._flat = flat.to(dev)
+        self._shadow = torch.empty(max(1, self._soff.n_total) if precision == "bf16" else 1, dtype=torch.bfloat16, device=dev)
+        with torch.cuda.device(dev):
+            L.check(lib.uvc_vit_compact_update_shadows(C.byref(self._cfg), self._blocks, nb, L.ptr(self._flat), L.ptr(self._shadow), L.cur_stream()),
+                    "uvc_vit_compact_update_shadows")
+        self._ws = {}
+        self.eval()
+
+    def _offset(self, name):
+        o = self._off
+        if name.startswith("blocks."):
+            _, k, rest = name.split(".", 2)
+            slots = ["norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias", "norm2.weight",
+                     "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias"]
+            return o.blk[int(k)][slots.index(rest)]
+        return dict(cls_token=o.cls_token, dist_token=o.dist_token, pos_embed=o.pos_embed, patch_gating=o.patch_gating,
+                    **{"patch_embed.proj.weight": o.patch_w, "patch_embed.proj.bias": o.patch_b, "norm.weight": o.norm_w, "norm.bias": o.norm_b,
+                       "head.weight": o.head_w, "head.bias": o.head_b, "head_dist.weight": o.headd_w, "head_dist.bias": o.headd_b})[name]
+
+    def num_params(self) -> int:
+        return sum(int(t.numel()) for k, t in self.export["state_dict"].items() if k != "patch_gating")
+
+    def macs(self, B=1) -> int:
+        return compact_macs(self.export, B, padded=True)
+
+    @torch.no_grad()
+    def forward(self, x):
+        from . import _lib as L
+        from . import ops
+        from .model_distilled import uvc_vit_io
+        L.require_cuda(x)
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            x = x.contiguous().float()
+        c, B = self.export["cfg"], x.shape[0]
+        if tuple(x.shape[1:]) != (c["in_chans"], c["img_size"], c["img_size"]):
+            raise AssertionError(f"Input image size ({x.shape[2]}*{x.shape[3]}) doesn't match model ({c['img_size']}*{c['img_size']}).")
+        lib = _bind()
+        dev = self._flat.device
+        stream = L.cur_stream()
+        if B not in self._ws:
+            n = lib.uvc_vit_compact_workspace_bytes(C.byref(self._cfg), self._blocks, self._nb, B)
+            if n < 0:
+                L.check(-1, "uvc_vit_compact_workspace_bytes")
+            self._ws = {B: torch.empty(n, dtype=torch.uint8, device=dev)}
+        ws = self._ws[B]
+        logits = torch.empty(B, c["num_classes"], device=dev)
+        logits_dist = torch.empty(B, c["num_classes"], device=dev) if self.num_tokens == 2 else None
+        mask = None
+        if c["patch_gating"]:
+            P = (c["img_size"] // c["patch_size"]) ** 2
+            mask = torch.empty(B, P, device=dev)
+            o = self._off.patch_gating
+            ops.patch_gate_sigmoid(self._flat[o:o + P], mask, B, P, bool(c["patch_hard"]))
+        io = uvc_vit_io()
+        io.params, io.shadow, io.workspace, io.workspace_bytes = L.ptr(self._flat), L.ptr(self._shadow), L.ptr(ws), ws.numel()
+        io.x, io.logits, io.logits_dist, io.patch_mask, io.batch = L.ptr(x), L.ptr(logits), L.ptr(logits_dist), L.ptr(mask), B
+        L.check(lib.uvc_vit_compact_forward(C.byref(self._cfg), self._blocks, self._nb, C.byref(io), stream), "uvc_vit_compact_forward")
+        out = logits if logits_dist is None else (logits + logits_dist) / 2
+        return out, self.macs(B)
+
+
+# ---- command line -------------------------------------------------------------------------------------------------------------
+def _parser():
+    p = argparse.ArgumentParser(prog="python -m uvc_amd.compact", description="Export a pruned DeiT as a compact model, or evaluate one")
+    sub = p.add_subparsers(dest="cmd", required=True)
+    for name in ("export", "eval"):
+        s = sub.add_parser(name)
+        s.add_argument("--model_type", default="deit_tiny_patch16_224")
+        s.add_argument("--model_cfg", default=None, help="JSON dims for a --model_type outside models/configs.py")
+        s.add_argument("--enable_deit", type=int, default=0)
+        s.add_argument("--enable_patch_gating", type=int, default=0, help="1: the sigmoid token mask (mode 1) is part of the model")
+        s.add_argument("--patch_hard", type=int, default=0)
+        s.add_argument("--img_size", type=int, default=224)
+        s.add_argument("--num_classes", type=int, default=1000)
+        s.add_argument("--checkpoint_dir", default=None, help="Stage-1 / Stage-2 checkpoint (bare state_dict with masks)")
+        s.add_argument("--model_path", default=None, help="pretrained checkpoint, when there is no --checkpoint_dir")
+        s.add_argument("--mlp_multiple", type=int, default=MLP_MULTIPLE)
+        s.add_argument("--precision", default="bf16")
+        s.add_argument("--seed", type=int, default=42)
+    sub.choices["export"].add_argument("--output", required=True)
+    e = sub.choices["eval"]
+    e.add_argument("--compact", default=None, help="an exported compact file (else the dense flags are exported on the fly)")
+    e.add_argument("--eval_batch_size", type=int, default=64)
+    e.add_argument("--eval_steps", type=int, default=2, help="synthetic validation batches")
+    e.add_argument("--synthetic", type=int, default=1, help="synthetic batches; 0 = read --dataset under --data_dir")
+    e.add_argument("--dataset", choices=["cifar10", "cifar100", "imagenet"], default="imagenet")
+    e.add_argument("--data_dir", default="/ssd1/xinyu/dataset/imagenet2012")
+    e.add_argument("--num_workers", type=int, default=8)
+    return p
+
+
+def _dense_model(args, dev):
+    """The Stage-2 eval model of post_train.eval_model, with patch-gating mode 1 when asked for."""
+    from .checkpoints import load_pretrained
+    from .model_distilled import DistilledVisionTransformer
+    from .pos_embed import match_pos_embed
+    from .post_train import register_masks
+    from .stage1 import CONFIGS
+    if "t2t" in args.model_type:
+        raise NotImplementedError("compact export of T2T-ViT models (their tokens-to-token front end) is not supported")
+    if not args.checkpoint_dir and not args.model_path:
+        raise SystemExit("need --checkpoint_dir or --model_path")
+    cfg = dict(CONFIGS[args.model_type]) if args.model_type in CONFIGS else dict(json.loads(args.model_cfg))
+    model = DistilledVisionTransformer(enable_dist=args.enable_deit, enable_patch_gating=args.enable_patch_gating, patch_hard=bool(args.patch_hard),
+                                       gumbel_hard=True, patch_size=cfg["patch_size"], embed_dim=cfg["embed_dim"], depth=cfg["depth"],
+                                       num_heads=cfg["num_heads"], mlp_ratio=cfg.get("mlp_ratio", 4), img_size=args.img_size,
+                                       num_classes=args.num_classes, precision=args.precision, device=dev)
+    register_masks(model)
+    if args.checkpoint_dir:
+        model.load_state_dict(match_pos_embed(torch.load(args.checkpoint_dir, map_location="cpu"), model))
+    else:
+        load_pretrained(args.model_path, model, num_classes=args.num_classes, what="model")
+    model.apply_masks()
+    model.eval()
+    return model
+
+
+def _report(export, B=1):
+    cfg = export["cfg"]
+    return dict(blocks=[dict(source=b["source"], heads=len(b["heads"]), v_dim=b["v_dim"], hidden=b["hidden"]) for b in export["blocks"]],
+                params=sum(int(t.numel()) for k, t in export["state_dict"].items() if k != "patch_gating"),
+                macs_full=full_macs(cfg, B), macs_compact=compact_macs(export, B, padded=False), macs_compact_padded=compact_macs(export, B, padded=True))
+
+
+def main(argv=None):
+    args = _parser().parse_args(argv)
+    dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    if args.cmd == "export" or not args.compact:
+        model = _dense_model(args, dev)
+        export = export_compact(model, compact_plan(model, args.mlp_multiple))
+        del model
+    else:
+        export = load_compact(args.compact)
+    if args.cmd == "export":
+        torch.save(export, args.output)
+        print(json.dumps(dict(output=args.output, **_report(export))))
+        return export
+    from .post_train import default_args, loader_valid_fn, synthetic_valid_fn
+    cm = CompactVisionTransformer(export, precision=args.precision, device=dev)
+    vargs = default_args(img_size=export["cfg"]["img_size"], num_classes=export["cfg"]["num_classes"], seed=args.seed)
+    for k in ("eval_batch_size", "eval_steps", "dataset", "data_dir", "num_workers"):
+        setattr(vargs, k, getattr(args, k))
+    if args.synthetic:
+        acc = synthetic_valid_fn(vargs, dev)(cm)
+    else:
+        from .data import build_loaders
+        vargs.train_batch_size = args.eval_batch_size
+        _, test_loader = build_loaders(vargs, rank=0, world=1)
+        acc = loader_valid_fn(test_loader)(cm)
+    print(json.dumps(dict(top1=acc, **_report(export))))
+    return acc
+
+
+if __name__ == "__main__":
+    main()

@@ -76,13 +76,19 @@ template <typename T> struct Geom {
   static constexpr int KS = HD / Mma<T>::KSTEP;              // MFMA k-steps across head_dim
   static constexpr int TPS = Mma<T>::KSTEP / 16;             // 16-row tiles consumed per "pair" step (2 bf16, 1 f32)
 };
+// LDS row stride (bytes) of the V image of a compact layout with DV < 64 value columns per head (uvc_attn_args.v_dim).  The transposed
+// reads of a 32-lane half take 8 rows x 32 bytes (bf16) or 2 x 16 rows x 4 bytes at rows 4 apart (float32); these strides put the 8 pieces on
+// disjoint banks: bf16 96 B for DV = 16 / 32, 160 B for DV = 48 (128 would be 2-way), float32 DV * 4 + 16.
+template <typename T, int DV> struct VGeom {
+  static constexpr int ROWB = DV == HD ? Geom<T>::ROWB : sizeof(T) == 2 ? (DV == 48 ? 160 : 96) : DV * 4 + 16;
+};
 
 // stage `rows` rows of 64 T (row stride ld_g elements) into LDS rows of ROWB bytes; rows >= nvalid zero.
 // All global loads of a batch are issued before the first LDS write so their latencies overlap
 // (a load->store loop exposes one HBM round trip per iteration: 7 trips per matrix at N = 197).
-template <typename T>
+template <typename T, int COLS = HD, int RB = Geom<T>::ROWB>
 __device__ __forceinline__ void stage_rows(char* lds, const T* g, size_t ld_g, int nvalid, int nrows_pad) {
-  constexpr int CPR = HD / Mma<T>::CH;                        // chunks per row
+  constexpr int CPR = COLS / Mma<T>::CH;                      // chunks per row
   constexpr int BATCH = 8;
   const u32x4 z = {0u, 0u, 0u, 0u};
   const int total = nrows_pad * CPR;
@@ -97,7 +103,7 @@ __device__ __forceinline__ void stage_rows(char* lds, const T* g, size_t ld_g, i
 #pragma unroll
     for (int i = 0; i < BATCH; ++i) {
       const int id = base + i * (int)blockDim.x + (int)threadIdx.x;
-      if (id < total) *reinterpret_cast<u32x4*>(lds + (id / CPR) * Geom<T>::ROWB + (id % CPR) * 16) = v[i];
+      if (id < total) *reinterpret_cast<u32x4*>(lds + (id / CPR) * RB + (id % CPR) * 16) = v[i];
     }
   }
 }
@@ -212,6 +218,37 @@ __device__ __forceinline__ void store_tile16_half(bf16_t* rowp, int g, const f32
   *reinterpret_cast<u32x4*>(rowp + (g & 1) * 16 + (g >> 1) * 8) = o;
 }
 
+// a 16 x (16 NDT) result tile (compact value width DV = 16 NDT < 64): column blocks in pairs as store_tile16 does (16 bytes per lane), an odd
+// last block (DV = 16, 48) as 4 columns per lane
+template <typename T, int NDT> __device__ __forceinline__ void store_tile_dv(T* rowp, int g, const f32x4 (&t)[NDT], float mul) {
+  if constexpr (sizeof(T) == 2) {
+#pragma unroll
+    for (int h = 0; h < NDT / 2; ++h) {
+      u32x2 x, y;
+      x[0] = pack_bf16x2(t[2 * h][0] * mul, t[2 * h][1] * mul); x[1] = pack_bf16x2(t[2 * h][2] * mul, t[2 * h][3] * mul);
+      y[0] = pack_bf16x2(t[2 * h + 1][0] * mul, t[2 * h + 1][1] * mul); y[1] = pack_bf16x2(t[2 * h + 1][2] * mul, t[2 * h + 1][3] * mul);
+      u32x4 o;
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const auto r = __builtin_amdgcn_permlane16_swap(x[e], y[e], false, false);
+        o[e] = r[0]; o[2 + e] = r[1];
+      }
+      *reinterpret_cast<u32x4*>(rowp + (2 * h + (g & 1)) * 16 + (g >> 1) * 8) = o;
+    }
+  }
+#pragma unroll
+  for (int dt = sizeof(T) == 2 ? NDT - NDT % 2 : 0; dt < NDT; ++dt) {
+    f32x4 v = t[dt];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] *= mul;
+    Store4<T>::st(rowp + dt * 16 + g * 4, v);
+  }
+}
+template <typename T, int DV> __device__ __forceinline__ void store_out(T* rowp, int g, const f32x4 (&t)[DV / 16], float mul) {
+  if constexpr (DV == HD) store_tile16<T>(rowp, g, t, mul);
+  else store_tile_dv<T, DV / 16>(rowp, g, t, mul);
+}
+
 struct AttnArgs {
   const void* qkv;   // [B, N, 3, H, 64]
   void* o;           // [B, N, H, 64]
@@ -222,6 +259,7 @@ struct AttnArgs {
   int B, N, H;
   float scale;
   const int* head_keep;
+  int v_dim;         // forward: 0 = [B, N, 3, H, 64]; 16 / 32 / 48 = compact rows [q H*64 | k H*64 | v H*v_dim], o [B, N, H*v_dim]
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -234,9 +272,9 @@ struct AttnArgs {
 // at run time (NFULL = -1) hipcc if-converts the wave-uniform "last tile?" test and EVERY tile pays 8 v_cndmask plus the v_readlane
 // reloads of their spilled SGPR masks, and consumes its scores straight behind the two MFMAs that produce them (s_nop 6-7):
 // 180 of the ~600 VALU instructions of a query tile.
-template <typename T, int T0, int NTB, int NFULL>
+template <typename T, int T0, int NTB, int NFULL, int DV>
 __device__ __forceinline__ void attn_key_block(const char* sK, const char* sV, const typename Mma<T>::Frag (&qf)[Geom<T>::KS], int N, float c2, int lane, int g, int li,
-                                               float& m_run, float& l_run, f32x4 (&ot)[4]) {
+                                               float& m_run, float& l_run, f32x4 (&ot)[DV / 16]) {
   typedef Mma<T> MM;
   typedef Geom<T> G;
   __builtin_amdgcn_sched_barrier(0);              // keep the next block's fragment reads from being hoisted over this one (VGPRs)
@@ -272,7 +310,7 @@ __device__ __forceinline__ void attn_key_block(const char* sK, const char* sV, c
     const float alpha = __builtin_amdgcn_exp2f(m_run * c2 - mb);
     l_run = l_run * alpha + sum;
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
+    for (int dt = 0; dt < DV / 16; ++dt)
 #pragma unroll
       for (int e = 0; e < 4; ++e) ot[dt][e] *= alpha;
   } else {
@@ -283,50 +321,61 @@ __device__ __forceinline__ void attn_key_block(const char* sK, const char* sV, c
   for (int s = 0; s < NTB / G::TPS; ++s) {
     const typename MM::Frag pf = MM::pack(st[s * G::TPS], st[s * G::TPS + G::TPS - 1]);
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) ot[dt] = MM::mma(TrFrag<T>::ld(sV, G::ROWB, (T0 / G::TPS + s) * MM::KSTEP, dt * 16, lane), pf, ot[dt]);
+    for (int dt = 0; dt < DV / 16; ++dt) ot[dt] = MM::mma(TrFrag<T>::ld(sV, VGeom<T, DV>::ROWB, (T0 / G::TPS + s) * MM::KSTEP, dt * 16, lane), pf, ot[dt]);
   }
 }
 
-template <typename T, int T0, int NT16, int ATT_BT, int NFULL>
+template <typename T, int T0, int NT16, int ATT_BT, int NFULL, int DV>
 __device__ __forceinline__ void attn_key_blocks(const char* sK, const char* sV, const typename Mma<T>::Frag (&qf)[Geom<T>::KS], int N, float c2, int lane, int g, int li,
-                                                float& m_run, float& l_run, f32x4 (&ot)[4]) {
+                                                float& m_run, float& l_run, f32x4 (&ot)[DV / 16]) {
   if constexpr (T0 < NT16) {
     constexpr int NTB = (NT16 - T0) < ATT_BT ? (NT16 - T0) : ATT_BT;
-    attn_key_block<T, T0, NTB, NFULL>(sK, sV, qf, N, c2, lane, g, li, m_run, l_run, ot);
-    attn_key_blocks<T, T0 + NTB, NT16, ATT_BT, NFULL>(sK, sV, qf, N, c2, lane, g, li, m_run, l_run, ot);
+    attn_key_block<T, T0, NTB, NFULL, DV>(sK, sV, qf, N, c2, lane, g, li, m_run, l_run, ot);
+    attn_key_blocks<T, T0 + NTB, NT16, ATT_BT, NFULL, DV>(sK, sV, qf, N, c2, lane, g, li, m_run, l_run, ot);
   }
 }
 
 // bf16: persistent workgroups (two per CU) walk (image, head) pairs; the K / V rows of the NEXT pair are fetched into registers
 // (4 + 4 chunks per thread) before the tiles of the current one are computed and written to LDS after them, so the HBM latency
 // of the staging -- a third of a head's time when it ran ahead of the tile loop -- hides under the MFMA / exp work.
-template <typename T, int NT16, int ATT_BT = 8, int NFULL = -1>
+// DV < 64: the compact layout (uvc_attn_args.v_dim): qkv rows [q H*64 | k H*64 | v H*DV], o rows H*DV; the V image has DV columns.
+template <typename T, int NT16, int ATT_BT = 8, int NFULL = -1, int DV = HD>
 __global__ __launch_bounds__(sizeof(T) == 2 ? 512 : 256, sizeof(T) == 2 ? 4 : 1) void k_attn_fwd(AttnArgs a) {
   typedef Mma<T> MM;
   typedef Geom<T> G;
+  constexpr int VROWB = VGeom<T, DV>::ROWB;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NP = NT16 * 16;
   constexpr bool PF = sizeof(T) == 2;                    // register prefetch of the next head (512 threads)
-  constexpr int CPR = HD / MM::CH;
+  constexpr int CPR = HD / MM::CH, CPRV = DV / MM::CH;
   constexpr int NCH = PF ? (NP * CPR + 511) / 512 : 1;
+  constexpr int NCHV = PF ? (NP * CPRV + 511) / 512 : 1;
   char* sK = smem;
   char* sV = smem + NP * G::ROWB;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6, g = lane >> 4, li = lane & 15;
-  const size_t ldq = (size_t)3 * a.H * HD;
+  const size_t ldq = (size_t)a.H * (2 * HD + DV), ldo = (size_t)a.H * DV;
   const int nbh = a.B * a.H;
   const int nqt = (a.N + 15) / 16;
   const float c2 = a.scale * 1.44269504088896340736f;
-  u32x4 pk[NCH], pv[NCH];
+  u32x4 pk[NCH], pv[NCHV];
   auto pf_load = [&](int bh2) {
-    const T* kb2 = reinterpret_cast<const T*>(a.qkv) + (size_t)(bh2 / a.H) * a.N * ldq + (bh2 % a.H) * HD + a.H * HD;
-    const T* vb2 = kb2 + a.H * HD;
+    const T* rb2 = reinterpret_cast<const T*>(a.qkv) + (size_t)(bh2 / a.H) * a.N * ldq;
+    const T* kb2 = rb2 + a.H * HD + (bh2 % a.H) * HD;
+    const T* vb2 = rb2 + 2 * a.H * HD + (bh2 % a.H) * DV;
     const u32x4 z = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       const int id = i * 512 + (int)threadIdx.x, row = id / CPR, c = id % CPR;
       const bool ok = id < NP * CPR && row < a.N;
       pk[i] = ok ? *reinterpret_cast<const u32x4*>(kb2 + (size_t)row * ldq + c * MM::CH) : z;
-      pv[i] = ok ? *reinterpret_cast<const u32x4*>(vb2 + (size_t)row * ldq + c * MM::CH) : z;
+      if constexpr (DV == HD) pv[i] = ok ? *reinterpret_cast<const u32x4*>(vb2 + (size_t)row * ldq + c * MM::CH) : z;
+    }
+    if constexpr (DV != HD) {
+#pragma unroll
+      for (int i = 0; i < NCHV; ++i) {
+        const int id = i * 512 + (int)threadIdx.x, row = id / CPRV, c = id % CPRV;
+        pv[i] = id < NP * CPRV && row < a.N ? *reinterpret_cast<const u32x4*>(vb2 + (size_t)row * ldq + c * MM::CH) : z;
+      }
     }
   };
   auto pf_store = [&]() {
@@ -335,7 +384,14 @@ __global__ __launch_bounds__(sizeof(T) == 2 ? 512 : 256, sizeof(T) == 2 ? 4 : 1)
       const int id = i * 512 + (int)threadIdx.x;
       if (id < NP * CPR) {
         *reinterpret_cast<u32x4*>(sK + (id / CPR) * G::ROWB + (id % CPR) * 16) = pk[i];
-        *reinterpret_cast<u32x4*>(sV + (id / CPR) * G::ROWB + (id % CPR) * 16) = pv[i];
+        if constexpr (DV == HD) *reinterpret_cast<u32x4*>(sV + (id / CPR) * G::ROWB + (id % CPR) * 16) = pv[i];
+      }
+    }
+    if constexpr (DV != HD) {
+#pragma unroll
+      for (int i = 0; i < NCHV; ++i) {
+        const int id = i * 512 + (int)threadIdx.x;
+        if (id < NP * CPRV) *reinterpret_cast<u32x4*>(sV + (id / CPRV) * VROWB + (id % CPRV) * 16) = pv[i];
       }
     }
   };
@@ -345,8 +401,14 @@ __global__ __launch_bounds__(sizeof(T) == 2 ? 512 : 256, sizeof(T) == 2 ? 4 : 1)
     pf_load(bh);
     pf_store();
   } else {
-    const T* kb = reinterpret_cast<const T*>(a.qkv) + (size_t)(bh / a.H) * a.N * ldq + (bh % a.H) * HD + a.H * HD;
-    stage_rows2<T>(sK, kb, ldq, sV, kb + a.H * HD, ldq, a.N, NP);
+    const T* rb = reinterpret_cast<const T*>(a.qkv) + (size_t)(bh / a.H) * a.N * ldq;
+    const T* kb = rb + a.H * HD + (bh % a.H) * HD;
+    if constexpr (DV == HD) {
+      stage_rows2<T>(sK, kb, ldq, sV, kb + a.H * HD, ldq, a.N, NP);
+    } else {
+      stage_rows<T>(sK, kb, ldq, a.N, NP);
+      stage_rows<T, DV, VROWB>(sV, rb + 2 * a.H * HD + (bh % a.H) * DV, ldq, a.N, NP);
+    }
   }
   __syncthreads();
   for (; bh < nbh; bh += gridDim.x) {
@@ -354,8 +416,8 @@ __global__ __launch_bounds__(sizeof(T) == 2 ? 512 : 256, sizeof(T) == 2 ? 4 : 1)
     const int nxt = bh + (int)gridDim.x;
     if (PF && nxt < nbh) pf_load(nxt);
     const T* qb = reinterpret_cast<const T*>(a.qkv) + (size_t)b * a.N * ldq + h * HD;
-    T* ob = reinterpret_cast<T*>(a.o) + (size_t)b * a.N * a.H * HD + h * HD;
-    if (a.head_keep && a.head_keep[h] == 0) {               // pruned head (inference): its output slice is zeros
+    T* ob = reinterpret_cast<T*>(a.o) + (size_t)b * a.N * ldo + h * DV;
+    if (DV == HD && a.head_keep && a.head_keep[h] == 0) {   // pruned head (inference): its output slice is zeros
       const f32x4 z = {0.f, 0.f, 0.f, 0.f};
       for (int i = threadIdx.x; i < a.N * 16; i += blockDim.x) Store4<T>::st(ob + (size_t)(i >> 4) * a.H * HD + (i & 15) * 4, z);
     } else {
@@ -363,15 +425,15 @@ __global__ __launch_bounds__(sizeof(T) == 2 ? 512 : 256, sizeof(T) == 2 ? 4 : 1)
         typename MM::Frag qf[G::KS];
 #pragma unroll
         for (int ks = 0; ks < G::KS; ++ks) qf[ks] = row_frag_global<T>(qb, ldq, qt * 16 + li, a.N, ks * 4 + g);
-        f32x4 ot[4];
+        f32x4 ot[DV / 16];
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) ot[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int dt = 0; dt < DV / 16; ++dt) ot[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
         float m_run = -INFINITY, l_run = 0.f;
-        attn_key_blocks<T, 0, NT16, ATT_BT, NFULL>(sK, sV, qf, a.N, c2, lane, g, li, m_run, l_run, ot);
+        attn_key_blocks<T, 0, NT16, ATT_BT, NFULL, DV>(sK, sV, qf, a.N, c2, lane, g, li, m_run, l_run, ot);
         const int q = qt * 16 + li;
         if (q < a.N) {
           const float inv = 1.0f / l_run;
-          store_tile16<T>(ob + (size_t)q * a.H * HD, g, ot, inv);
+          store_out<T, DV>(ob + (size_t)q * ldo, g, ot, inv);
           if (g == 0 && a.lse) a.lse[((size_t)b * a.H + h) * a.N + q] = m_run * a.scale + __logf(l_run);
         }
       }
@@ -1028,7 +1090,7 @@ __global__ __launch_bounds__((NT + NHW) * 64) void k_qkv_attn_fwd(Args a) {
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) ot[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
         float m_run = -INFINITY, l_run = 0.f;
-        attn_key_blocks<T, 0, 14, 8, NFULL>(sK, sV, qf, a.N, c2, lane, g, li, m_run, l_run, ot);
+        attn_key_blocks<T, 0, 14, 8, NFULL, HD>(sK, sV, qf, a.N, c2, lane, g, li, m_run, l_run, ot);
         {
           // o leaves the same way, through this wave's rows of the Q image (dead since qf was read; only this wave ever reads them)
           const float inv = 1.0f / l_run;
@@ -1067,23 +1129,26 @@ __global__ __launch_bounds__((NT + NHW) * 64) void k_qkv_attn_fwd(Args a) {
 // No atomics: every output row is written by one wave, so results are deterministic and independent of the batch.  Rows past N are
 // zero in the LDS tiles; scores of padded keys are masked in the ragged last tile (N = 577 = 9 x 64 + 1: one valid key).
 constexpr int LQ = 128, LK = 64, LONG_MAX_N = 1026;
-template <typename T> struct LongTile {
-  static constexpr int CPR = HD / Mma<T>::CH;             // 16-byte chunks per row
-  static constexpr int NCL = LK * CPR / 512;               // chunks per thread and matrix (bf16 1, float32 2)
-  static constexpr int BYTES = LK * Geom<T>::ROWB;
+// COLS < 64: the V tile of the compact layout (fewer chunks than threads for bf16 DV <= 48: the threads past them load nothing)
+template <typename T, int COLS = HD> struct LongTile {
+  static constexpr int CPR = COLS / Mma<T>::CH;           // 16-byte chunks per row
+  static constexpr int NCL = (LK * CPR + 511) / 512;       // chunks per thread and matrix (bf16 1, float32 2 at COLS = 64)
+  static constexpr bool EVEN = LK * CPR % 512 == 0;
+  static constexpr int RB = VGeom<T, COLS>::ROWB;
+  static constexpr int BYTES = LK * RB;
   static __device__ __forceinline__ void load(u32x4 (&v)[NCL], const T* g, size_t ld, int r0, int N) {
     const u32x4 z = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int i = 0; i < NCL; ++i) {
       const int id = i * 512 + (int)threadIdx.x, row = r0 + id / CPR, c = id % CPR;
-      v[i] = row < N ? *reinterpret_cast<const u32x4*>(g + (size_t)row * ld + c * Mma<T>::CH) : z;
+      v[i] = (EVEN || id < LK * CPR) && row < N ? *reinterpret_cast<const u32x4*>(g + (size_t)row * ld + c * Mma<T>::CH) : z;
     }
   }
   static __device__ __forceinline__ void store(char* lds, const u32x4 (&v)[NCL]) {
 #pragma unroll
     for (int i = 0; i < NCL; ++i) {
       const int id = i * 512 + (int)threadIdx.x;
-      *reinterpret_cast<u32x4*>(lds + (id / CPR) * Geom<T>::ROWB + (id % CPR) * 16) = v[i];
+      if (EVEN || id < LK * CPR) *reinterpret_cast<u32x4*>(lds + (id / CPR) * RB + (id % CPR) * 16) = v[i];
     }
   }
 };
@@ -1094,21 +1159,24 @@ template <typename T> __device__ __forceinline__ void zero_rows64(T* base, size_
   for (int i = threadIdx.x; i < (r1 - r0) * 16; i += blockDim.x) Store4<T>::st(base + (size_t)(r0 + (i >> 4)) * ld + (i & 15) * 4, z);
 }
 
-template <typename T>
+// DV < 64: the compact layout, as k_attn_fwd
+template <typename T, int DV = HD>
 __global__ __launch_bounds__(512) void k_attn_fwd_long(AttnArgs a) {
   typedef Mma<T> MM;
   typedef Geom<T> G;
   typedef LongTile<T> LT;
+  typedef LongTile<T, DV> LTV;
+  constexpr int BUF = LT::BYTES + LTV::BYTES;                 // one K tile + one V tile
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int nqb = (a.N + LQ - 1) / LQ;
   const int qblk = blockIdx.x % nqb, bh = blockIdx.x / nqb, b = bh / a.H, h = bh % a.H;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
-  const size_t ldq = (size_t)3 * a.H * HD, ldo = (size_t)a.H * HD;
+  const size_t ldq = (size_t)a.H * (2 * HD + DV), ldo = (size_t)a.H * DV;
   const T* qb = reinterpret_cast<const T*>(a.qkv) + (size_t)b * a.N * ldq + h * HD;
   const T* kb = qb + a.H * HD;
-  const T* vb = kb + a.H * HD;
-  T* ob = reinterpret_cast<T*>(a.o) + (size_t)b * a.N * ldo + h * HD;
-  if (a.head_keep && a.head_keep[h] == 0) {
+  const T* vb = reinterpret_cast<const T*>(a.qkv) + (size_t)b * a.N * ldq + 2 * a.H * HD + h * DV;
+  T* ob = reinterpret_cast<T*>(a.o) + (size_t)b * a.N * ldo + h * DV;
+  if (DV == HD && a.head_keep && a.head_keep[h] == 0) {
     zero_rows64<T>(ob, ldo, qblk * LQ, min(a.N, qblk * LQ + LQ));
     return;
   }
@@ -1117,23 +1185,23 @@ __global__ __launch_bounds__(512) void k_attn_fwd_long(AttnArgs a) {
   typename MM::Frag qf[G::KS];
 #pragma unroll
   for (int ks = 0; ks < G::KS; ++ks) qf[ks] = row_frag_global<T>(qb, ldq, q, a.N, ks * 4 + g);
-  f32x4 ot[4];
+  f32x4 ot[DV / 16];
 #pragma unroll
-  for (int dt = 0; dt < 4; ++dt) ot[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int dt = 0; dt < DV / 16; ++dt) ot[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m_run = -INFINITY, l_run = 0.f;
-  u32x4 pk[LT::NCL], pv[LT::NCL];
+  u32x4 pk[LT::NCL], pv[LTV::NCL];
   LT::load(pk, kb, ldq, 0, a.N);
-  LT::load(pv, vb, ldq, 0, a.N);
+  LTV::load(pv, vb, ldq, 0, a.N);
   LT::store(smem, pk);
-  LT::store(smem + LT::BYTES, pv);
+  LTV::store(smem + LT::BYTES, pv);
   __syncthreads();
   const int nkt = (a.N + LK - 1) / LK;
   for (int j = 0; j < nkt; ++j) {
-    const char* sK = smem + (j & 1) * 2 * LT::BYTES;
+    const char* sK = smem + (j & 1) * BUF;
     const char* sV = sK + LT::BYTES;
     if (j + 1 < nkt) {
       LT::load(pk, kb, ldq, (j + 1) * LK, a.N);
-      LT::load(pv, vb, ldq, (j + 1) * LK, a.N);
+      LTV::load(pv, vb, ldq, (j + 1) * LK, a.N);
     }
     const int nv = a.N - j * LK;                              // valid keys in this tile (>= 1)
     f32x4 st[LK / 16];
@@ -1165,7 +1233,7 @@ __global__ __launch_bounds__(512) void k_attn_fwd_long(AttnArgs a) {
     const float alpha = __builtin_amdgcn_exp2f(m_run * c2 - mb);  // 0 at j = 0 (m_run = -inf), where l_run and ot are 0
     l_run = l_run * alpha + sum;
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
+    for (int dt = 0; dt < DV / 16; ++dt)
 #pragma unroll
       for (int e = 0; e < 4; ++e) ot[dt][e] *= alpha;
     m_run = m_new;
@@ -1173,18 +1241,18 @@ __global__ __launch_bounds__(512) void k_attn_fwd_long(AttnArgs a) {
     for (int s = 0; s < LK / MM::KSTEP; ++s) {
       const typename MM::Frag pf = MM::pack(st[s * G::TPS], st[s * G::TPS + G::TPS - 1]);
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) ot[dt] = MM::mma(TrFrag<T>::ld(sV, G::ROWB, s * MM::KSTEP, dt * 16, lane), pf, ot[dt]);
+      for (int dt = 0; dt < DV / 16; ++dt) ot[dt] = MM::mma(TrFrag<T>::ld(sV, LTV::RB, s * MM::KSTEP, dt * 16, lane), pf, ot[dt]);
     }
     if (j + 1 < nkt) {
-      char* nK = smem + ((j + 1) & 1) * 2 * LT::BYTES;       // read in tile j - 1: every wave has passed the barrier behind it
+      char* nK = smem + ((j + 1) & 1) * BUF;                 // read in tile j - 1: every wave has passed the barrier behind it
       LT::store(nK, pk);
-      LT::store(nK + LT::BYTES, pv);
+      LTV::store(nK + LT::BYTES, pv);
     }
     __syncthreads();
   }
   if (q < a.N) {
     const float inv = 1.0f / l_run;
-    store_tile16<T>(ob + (size_t)q * ldo, g, ot, inv);
+    store_out<T, DV>(ob + (size_t)q * ldo, g, ot, inv);
     if (g == 0 && a.lse) a.lse[((size_t)b * a.H + h) * a.N + q] = m_run * a.scale + __logf(l_run);
   }
 }
@@ -1380,29 +1448,32 @@ __global__ __launch_bounds__(512) void k_attn_bwd_dkv_long(AttnArgs a) {
   }
 }
 
-template <typename T> int launch_long(const AttnArgs& a, int which, hipStream_t st) {
+template <typename T, int DV = HD> int launch_long(const AttnArgs& a, int which, hipStream_t st) {
   const int nblk = (a.N + LQ - 1) / LQ;
   const int64_t grid = (int64_t)a.B * a.H * nblk;
   if (grid > 0x7fffffff) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "attention: too many workgroups");
   constexpr int SH = 2 * 2 * LongTile<T>::BYTES;
   if (which == 0) {
-    UVC_MAX_LDS(SH, k_attn_fwd_long<T>);
-    k_attn_fwd_long<T><<<(int)grid, 512, SH, st>>>(a);
-  } else if (which == 1) {
-    UVC_MAX_LDS(SH, k_attn_bwd_dq_long<T>);
-    k_attn_bwd_dq_long<T><<<(int)grid, 512, SH, st>>>(a);
-  } else {
-    constexpr int SHD = SH + 2 * 2 * LK * (int)sizeof(float);
-    UVC_MAX_LDS(SHD, k_attn_bwd_dkv_long<T>);
-    k_attn_bwd_dkv_long<T><<<(int)grid, 512, SHD, st>>>(a);
+    constexpr int SHF = 2 * (LongTile<T>::BYTES + LongTile<T, DV>::BYTES);
+    UVC_MAX_LDS(SHF, k_attn_fwd_long<T, DV>);
+    k_attn_fwd_long<T, DV><<<(int)grid, 512, SHF, st>>>(a);
+  } else if constexpr (DV == HD) {
+    if (which == 1) {
+      UVC_MAX_LDS(SH, k_attn_bwd_dq_long<T>);
+      k_attn_bwd_dq_long<T><<<(int)grid, 512, SH, st>>>(a);
+    } else {
+      constexpr int SHD = SH + 2 * 2 * LK * (int)sizeof(float);
+      UVC_MAX_LDS(SHD, k_attn_bwd_dkv_long<T>);
+      k_attn_bwd_dkv_long<T><<<(int)grid, 512, SHD, st>>>(a);
+    }
   }
   UVC_CHECK_LAUNCH();
   return UVC_OK;
 }
 
-template <typename T, int NT16> int launch(const AttnArgs& a, int which, hipStream_t st) {
+template <typename T, int NT16, int DV = HD> int launch(const AttnArgs& a, int which, hipStream_t st) {
   const int NP = NT16 * 16;
-  size_t sh = (size_t)2 * NP * Geom<T>::ROWB;
+  size_t sh = (size_t)NP * (Geom<T>::ROWB + VGeom<T, DV>::ROWB);     // K and V images
   const int grid = a.B * a.H;
   // forward: 4 waves per (image, head); backward: 8 (two workgroups per CU either way -- the LDS image is the limit --
   // so backward runs 4 waves per SIMD, which hides its longer dependent MFMA -> exp -> MFMA chains: 153 -> 135 us)
@@ -1412,32 +1483,34 @@ template <typename T, int NT16> int launch(const AttnArgs& a, int which, hipStre
     // DeiT's N = 197 / 198: twelve full key tiles, a partial one and a tile of padding -- known at compile time (see attn_key_block)
     constexpr int NF = NT16 == 14 ? 12 : -1;
     if (NF >= 0 && a.N / 16 == NF) {
-      UVC_MAX_LDS(sh, k_attn_fwd<T, NT16, 8, NF>);      // sh is a function of the instantiation
-      k_attn_fwd<T, NT16, 8, NF><<<fgrid, sizeof(T) == 2 ? 512 : 256, sh, st>>>(a);
+      UVC_MAX_LDS(sh, k_attn_fwd<T, NT16, 8, NF, DV>);      // sh is a function of the instantiation
+      k_attn_fwd<T, NT16, 8, NF, DV><<<fgrid, sizeof(T) == 2 ? 512 : 256, sh, st>>>(a);
     } else {
-      UVC_MAX_LDS(sh, k_attn_fwd<T, NT16>);
-      k_attn_fwd<T, NT16><<<fgrid, sizeof(T) == 2 ? 512 : 256, sh, st>>>(a);
+      UVC_MAX_LDS(sh, k_attn_fwd<T, NT16, 8, -1, DV>);
+      k_attn_fwd<T, NT16, 8, -1, DV><<<fgrid, sizeof(T) == 2 ? 512 : 256, sh, st>>>(a);
     }
-  } else if (which == 1) {
-    UVC_MAX_LDS(sh, k_attn_bwd_dq<T, NT16>);
-    k_attn_bwd_dq<T, NT16><<<grid, threads, sh, st>>>(a);
-  } else {
-    sh += (size_t)2 * NP * sizeof(float);
-    UVC_MAX_LDS(sh, k_attn_bwd_dkv<T, NT16>);
-    k_attn_bwd_dkv<T, NT16><<<grid, threads, sh, st>>>(a);
+  } else if constexpr (DV == HD) {
+    if (which == 1) {
+      UVC_MAX_LDS(sh, k_attn_bwd_dq<T, NT16>);
+      k_attn_bwd_dq<T, NT16><<<grid, threads, sh, st>>>(a);
+    } else {
+      sh += (size_t)2 * NP * sizeof(float);
+      UVC_MAX_LDS(sh, k_attn_bwd_dkv<T, NT16>);
+      k_attn_bwd_dkv<T, NT16><<<grid, threads, sh, st>>>(a);
+    }
   }
   UVC_CHECK_LAUNCH();
   return UVC_OK;
 }
 
-template <typename T> int dispatch(const AttnArgs& a, int which, hipStream_t st) {
+template <typename T, int DV = HD> int dispatch(const AttnArgs& a, int which, hipStream_t st) {
   const int nt = (a.N + 15) / 16;
-  if (nt <= 2) return launch<T, 2>(a, which, st);
-  if (nt <= 4) return launch<T, 4>(a, which, st);
-  if (nt <= 8) return launch<T, 8>(a, which, st);
-  if (nt <= 14) return launch<T, 14>(a, which, st);
-  if (nt <= 16) return launch<T, 16>(a, which, st);
-  if (a.N <= LONG_MAX_N) return launch_long<T>(a, which, st);
+  if (nt <= 2) return launch<T, 2, DV>(a, which, st);
+  if (nt <= 4) return launch<T, 4, DV>(a, which, st);
+  if (nt <= 8) return launch<T, 8, DV>(a, which, st);
+  if (nt <= 14) return launch<T, 14, DV>(a, which, st);
+  if (nt <= 16) return launch<T, 16, DV>(a, which, st);
+  if (a.N <= LONG_MAX_N) return launch_long<T, DV>(a, which, st);
   return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "attention: sequence length > 1026 not supported");
 }
 
@@ -1447,6 +1520,9 @@ int check(const uvc_attn_args* p, bool bwd) {
   if (p->head_dim != HD) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "attention: head_dim must be 64");
   if (p->B <= 0 || p->N <= 0 || p->H <= 0) return uvc_set_error_msg(UVC_ERR_ARG, "attention: empty problem");
   if (p->dtype != UVC_F32 && p->dtype != UVC_BF16) return uvc_set_error_msg(UVC_ERR_ARG, "attention: bad dtype");
+  if (p->v_dim != 0 && p->v_dim != 16 && p->v_dim != 32 && p->v_dim != 48 && p->v_dim != 64)
+    return uvc_set_error_msg(UVC_ERR_ARG, "attention: v_dim must be 0, 16, 32, 48 or 64");
+  if (p->v_dim != 0 && (bwd || p->head_keep)) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "attention: v_dim is forward-only and takes no head_keep");
   return UVC_OK;
 }
 
@@ -1484,6 +1560,7 @@ AttnArgs conv(const uvc_attn_args* p) {
   AttnArgs a;
   a.qkv = p->qkv; a.o = p->o; a.lse = p->lse; a.dout = p->dout; a.dqkv = p->dqkv; a.delta = p->delta;
   a.B = p->B; a.N = p->N; a.H = p->H; a.scale = p->scale; a.head_keep = p->head_keep;
+  a.v_dim = p->v_dim;
   return a;
 }
 
@@ -1515,10 +1592,19 @@ extern "C" int uvc_qkv_attention_fwd(const uvc_qkv_attn_args* p, void* stream) {
   return UVC_OK;
 }
 
+template <typename T> int dispatch_fwd(const AttnArgs& a, hipStream_t st) {
+  switch (a.v_dim) {              // (64: the compact rows are [B, N, 3, H, 64] -- today's kernels)
+    case 16: return dispatch<T, 16>(a, 0, st);
+    case 32: return dispatch<T, 32>(a, 0, st);
+    case 48: return dispatch<T, 48>(a, 0, st);
+    default: return dispatch<T>(a, 0, st);
+  }
+}
+
 extern "C" int uvc_attention_fwd(const uvc_attn_args* p, void* stream) {
   if (int e = check(p, false)) return e;
   const AttnArgs a = conv(p);
-  return p->dtype == UVC_F32 ? dispatch<float>(a, 0, (hipStream_t)stream) : dispatch<bf16_t>(a, 0, (hipStream_t)stream);
+  return p->dtype == UVC_F32 ? dispatch_fwd<float>(a, (hipStream_t)stream) : dispatch_fwd<bf16_t>(a, (hipStream_t)stream);
 }
 
 extern "C" int uvc_attention_bwd(const uvc_attn_args* p, void* stream) {
