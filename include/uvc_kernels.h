@@ -125,12 +125,17 @@ typedef struct uvc_attn_args {
                         k_attn_bwd_one, otherwise the dq + dk/dv pair); 1 = the pair; 2 = the one-pass kernel or UVC_ERR_UNSUPPORTED */
   int32_t grid;      /* backward, one-pass kernel: 0 = one persistent workgroup per CU; > 0 = that many (tests: several heads per workgroup
                         at small B * H) */
-  int32_t v_dim;     /* forward only.  0: the layout above.  16 / 32 / 48 / 64: a compact model's value head dim -- qkv rows [B, N, H*64 (q) | H*64 (k) |
+  int32_t v_dim;     /* uvc_attention_fwd (and uvc_attention_bwd_vdim below) only.  0: the layout above.  16 / 32 / 48 / 64: a compact model's value head dim -- qkv rows [B, N, H*64 (q) | H*64 (k) |
                         H*v_dim (v)], o [B, N, H*v_dim], lse as above; q / k keep 64 dims.  64 is the layout above and runs its kernels.  Other values:
                         UVC_ERR_ARG; with uvc_attention_bwd or head_keep: UVC_ERR_UNSUPPORTED */
 } uvc_attn_args;
 int uvc_attention_fwd(const uvc_attn_args* args, void* stream);
 int uvc_attention_bwd(const uvc_attn_args* args, void* stream);
+/* The backward of uvc_attention_fwd at a value width (training a compact model): v_dim must be 16, 32, 48 or 64, the layout is the forward's --
+ * qkv and dqkv rows [q H*64 | k H*64 | v H*v_dim], o and dout [B, N, H*v_dim], lse / delta [B, H, N].  Always the dq + dk/dv kernel pair
+ * (variant and grid are not read), deterministic, no atomics; every element of dqkv and delta is written.  At v_dim = 64 it launches the
+ * kernels uvc_attention_bwd(variant = 1) launches.  head_keep set, or N > 256 (whatever v_dim): UVC_ERR_UNSUPPORTED. */
+int uvc_attention_bwd_vdim(const uvc_attn_args* args, void* stream);
 
 /* The qkv Linear and the attention forward of a block as ONE kernel (UVC/models/model_distilled.py:175-185: `self.qkv(x)` ... `attn @ v`):
  * h [B*N, D] (the LayerNorm-1 rows) and the qkv weight [3D, D] in, o [B,N,H*64] and lse out; qkv [B,N,3,H,64] is written only when the

@@ -154,7 +154,8 @@ typedef struct uvc_vit_io {
 int uvc_vit_forward(const uvc_vit_cfg* cfg, const uvc_vit_io* io, void* stream);
 int uvc_vit_backward(const uvc_vit_cfg* cfg, const uvc_vit_io* io, void* stream);
 
-/* ---- compact models (uvc_amd/compact.py): a pruned DeiT exported at its kept widths, no-grad forward only ----
+/* ---- compact models (uvc_amd/compact.py): a pruned DeiT exported at its kept widths; the four entry points below are the no-grad forward,
+ * uvc_vit_compact_train_* / uvc_vit_compact_backward further down train the same network ----
  * Block k of the export (one per block of the source model that runs) keeps `heads` heads with q / k of 64 dims and `v_dim` value dims each
  * (16, 32, 48 or 64; 0 when heads == 0), and `hidden` MLP units (a multiple of 16; may be 0).  The embedding, final norm and heads keep
  * the shapes of the dense model described by `cfg` (embed_dim, patch, classes, ntok, dtype, ln_eps; cfg.depth, num_heads and hidden
@@ -176,6 +177,34 @@ int uvc_vit_compact_update_shadows(const uvc_vit_cfg* cfg, const uvc_compact_blo
  * Reads io->params, shadow (bf16), workspace, x, logits, logits_dist, patch_mask (optional device [B, P]), patches_in (optional), batch;
  * the other members are ignored.  cfg.dtype UVC_F32 or UVC_BF16 (cfg.resid_f32 = 0). */
 int uvc_vit_compact_forward(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* stream);
+
+/* ---- fine-tuning a compact model at its kept widths (uvc_amd/compact_train.py) ----
+ * One flat float32 parameter buffer serves eval and training, and a gradient buffer congruent with it: `off` is uvc_vit_compact_layout's.
+ * The training shadow layout keeps that layout's [out, in] offsets (blk_w, head_w, headd_w, patch_w: uvc_vit_compact_forward runs on a
+ * training shadow buffer) and appends the transposed copies the dgrads read (blk_wt[k][0..3], head_wt, headd_wt; units of T, T = float
+ * in UVC_F32 mode, where only the transposed copies are written).  cfg.dtype UVC_F32 or UVC_BF16 with cfg.resid_f32 = 0; sequences of at
+ * most 256 tokens (uvc_attention_bwd_vdim): every entry point below refuses longer ones with UVC_ERR_UNSUPPORTED (the workspace query
+ * with -1), so nothing is half run. */
+int uvc_vit_compact_train_layout(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, uvc_vit_offsets* off,
+                                 uvc_vit_shadow_offsets* soff);
+int64_t uvc_vit_compact_train_workspace_bytes(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int32_t batch);
+int uvc_vit_compact_train_update_shadows(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const float* params, void* shadow,
+                                         void* stream);
+/* Parameters no forward reads, as (element offset, count) pairs into the flat buffers: norm1 (and the empty qkv / proj.weight) of a block
+ * without heads, norm2 (and the empty fc1 / fc2.weight) of a block without units.  Autograd gives them no gradient, so an optimiser must
+ * leave them alone (no update, no decay); uvc_vit_compact_backward writes zeros into their gradient slots.  ranges: [2 * cap]; *count
+ * receives the number of pairs (UVC_ERR_ARG when it exceeds cap). */
+int uvc_vit_compact_frozen_ranges(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int64_t* ranges, int32_t cap,
+                                  int32_t* count);
+/* Training forward: uvc_vit_compact_forward's network, leaving in the workspace what the backward reads -- per block the LayerNorm
+ * outputs and statistics, qkv, the attention output and lse, x1, GELU(a) and GELU'(a) (UVC_EPI_BIAS_GELU_GRAD).  io as for
+ * uvc_vit_compact_forward (workspace of uvc_vit_compact_train_workspace_bytes, the training shadow); io->accumulate must be 0. */
+int uvc_vit_compact_train_forward(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* stream);
+/* Backward of the last uvc_vit_compact_train_forward on the same workspace, batch, patch_mask and patches_in: reads io->d_logits (and
+ * d_logits_dist with ntok == 2), overwrites every gradient in io->grads[0, n_main) (frozen ranges: zeros).  One stream, existing kernels
+ * in reverse order of the forward plus uvc_attention_bwd_vdim; deterministic.  A block without heads contributes colsum(dL/dx) to
+ * proj.bias, one without units to fc2.bias.  The mode-1 token mask (io->patch_mask) is a constant: patch_gating gets no gradient. */
+int uvc_vit_compact_backward(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* stream);
 
 #ifdef __cplusplus
 }

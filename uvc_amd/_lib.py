@@ -176,6 +176,7 @@ _SIGNATURES = {
     "uvc_gemm_tn_workspace_bytes": [I32, I32, I32, C.POINTER(I64), C.POINTER(I32)],
     "uvc_attention_fwd": [C.POINTER(uvc_attn_args), VP],
     "uvc_attention_bwd": [C.POINTER(uvc_attn_args), VP],
+    "uvc_attention_bwd_vdim": [C.POINTER(uvc_attn_args), VP],
     "uvc_qkv_attention_supported": [I32, I32, I32, I32, I32],
     "uvc_qkv_attention_fwd": [C.POINTER(uvc_qkv_attn_args), VP],
     "uvc_attention_tok_fwd": [C.POINTER(uvc_attn_tok_args), VP],
@@ -236,7 +237,9 @@ _SIGNATURES = {
 # include/uvc_vit.h (bound in uvc_amd/model_distilled.py next to its ctypes structures)
 VIT_SYMBOLS = ["uvc_vit_layout", "uvc_vit_workspace_bytes", "uvc_vit_ws_offsets", "uvc_vit_update_shadows", "uvc_vit_forward",
                "uvc_vit_backward", "uvc_vit_compact_layout", "uvc_vit_compact_workspace_bytes", "uvc_vit_compact_update_shadows",
-               "uvc_vit_compact_forward"]   # (the compact-model entry points: bound in uvc_amd/compact.py)
+               "uvc_vit_compact_forward",   # (the compact-model entry points: bound in uvc_amd/compact.py)
+               "uvc_vit_compact_train_layout", "uvc_vit_compact_train_workspace_bytes", "uvc_vit_compact_train_update_shadows",
+               "uvc_vit_compact_frozen_ranges", "uvc_vit_compact_train_forward", "uvc_vit_compact_backward"]   # (uvc_amd/compact_train.py)
 
 
 def side_stream(device, priority_class=None):

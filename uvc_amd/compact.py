@@ -15,9 +15,11 @@ zero ``b1`` and zero fc2 columns (GELU(0) = 0 meets a zero column).
 
     python -m uvc_amd.compact export --model_type ... --checkpoint_dir CK --output model.compact.pt
     python -m uvc_amd.compact eval --compact model.compact.pt [--synthetic 0 --dataset ... --data_dir ...]
+    python -m uvc_amd.compact finetune --compact model.compact.pt --output tuned.compact.pt [Stage 2's flags]
 
 ``reference_forward`` is the written spec of the format (plain PyTorch, CPU or GPU, any dtype); ``CompactVisionTransformer``
-runs it through ``uvc_vit_compact_forward`` (include/uvc_vit.h).
+runs it through ``uvc_vit_compact_forward`` (include/uvc_vit.h).  ``reference_logits`` is the same network with the two heads kept
+apart: the function ``compact_train.CompactTrainer`` fine-tunes (a fine-tuned file is an ordinary version-1 compact file).
 """
 from __future__ import annotations
 
@@ -172,6 +174,14 @@ def load_compact(path) -> dict:
 def reference_forward(export: dict, x: torch.Tensor) -> torch.Tensor:
     """Eval logits of a compact model in plain PyTorch, in x's dtype and on x's device: the written spec of the format (the Stage-2 eval
     forward of model_distilled.py:429-531 at the kept widths; ``(x + x_dist) / 2`` with the distillation token)."""
+    o, od = reference_logits(export, x)
+    return (o + od) / 2
+
+
+def reference_logits(export: dict, x: torch.Tensor):
+    """``(logits, logits_dist)`` of a compact model in plain PyTorch -- the two heads kept apart, as a training loss takes them
+    (``logits_dist is logits`` without the distillation token).  Differentiable: state_dict tensors that already have x's dtype and
+    device enter the graph as they are, so leaves with ``requires_grad`` receive the compact model's gradients."""
     check_export(export)
     cfg = export["cfg"]
     P = {k: v.to(device=x.device, dtype=x.dtype) for k, v in export["state_dict"].items()}
@@ -211,7 +221,7 @@ def reference_forward(export: dict, x: torch.Tensor) -> torch.Tensor:
     h = F.layer_norm(h, (D,), P["norm.weight"], P["norm.bias"], eps)
     o = F.linear(h[:, 0], P["head.weight"], P["head.bias"])
     od = F.linear(h[:, 1], P["head_dist.weight"], P["head_dist.bias"]) if cfg["enable_dist"] else o
-    return (o + od) / 2
+    return o, od
 
 
 # ---- MAC bookkeeping (oracle/vit.py:mac_table with per-block widths) ------------------------------------------------------------
@@ -442,6 +452,12 @@ def _parser():
     e.add_argument("--dataset", choices=["cifar10", "cifar100", "imagenet"], default="imagenet")
     e.add_argument("--data_dir", default="/ssd1/xinyu/dataset/imagenet2012")
     e.add_argument("--num_workers", type=int, default=8)
+    # fine-tune a compact file at its kept widths: Stage 2's training, distillation, teacher, data and Mixup flags (post_train's names and defaults)
+    from .post_train import add_stage2_flags
+    f = sub.add_parser("finetune")
+    f.add_argument("--compact", required=True, help="the compact file to fine-tune")
+    f.add_argument("--output", required=True, help="where the best model (validation top-1) is written, a version-1 compact file")
+    add_stage2_flags(f, skip=("checkpoint_dir", "eval_only"))
     return p
 
 
@@ -478,9 +494,66 @@ def _report(export, B=1):
                 macs_full=full_macs(cfg, B), macs_compact=compact_macs(export, B, padded=False), macs_compact_padded=compact_macs(export, B, padded=True))
 
 
+def finetune(args, dev):
+    """``finetune``: Stage 2's epoch loop (post_train.py:326-403) on a compact file; the model with the best validation top-1 is saved."""
+    import numpy as np
+    from .compact_train import CompactTrainer
+    from .post_train import loader_valid_fn, synthetic_valid_fn
+    from .stage1 import Stage1Trainer
+    export = load_compact(args.compact)
+    c = export["cfg"]
+    args.img_size, args.num_classes, args.enable_deit = c["img_size"], c["num_classes"], c["enable_dist"]
+    train_loader = test_loader = None
+    if not args.synthetic:
+        from .data import build_loaders, real_mixup, soft_batches
+        train_loader, test_loader = build_loaders(args, rank=0, world=1)
+        args.steps_per_epoch = train_loader.train_steps()
+        np.random.seed(args.seed)                         # Mixup draws from numpy's global RNG
+        mixup_fn = real_mixup(args)
+    tr = CompactTrainer(args, export, device=dev)
+    g = torch.Generator(device=dev).manual_seed(args.seed)
+
+    def batches(epoch):
+        if train_loader is not None:
+            yield from soft_batches(train_loader, epoch, mixup_fn, args.smoothing, args.data_classes, args.num_classes)
+            return
+        for _ in range(args.steps):
+            x = torch.randn(args.train_batch_size, 3, args.img_size, args.img_size, device=dev, generator=g)
+            yield x, torch.softmax(torch.randn(args.train_batch_size, args.num_classes, device=dev, generator=g), -1)
+
+    def trimmed(epoch):
+        for x, y in batches(epoch):
+            yield (x[:-1], y[:-1]) if len(x) % 2 else (x, y)                                       # post_train.py:348-350
+
+    valid_fn = None
+    if args.eval_steps > 0:
+        valid_fn = loader_valid_fn(test_loader) if test_loader is not None else synthetic_valid_fn(args, dev)
+    before = valid_fn(tr.model) if valid_fn else None
+    best = 0.0
+    for epoch in range(args.epochs):
+        tr.begin_epoch(epoch)
+        last = None
+        for (x, y), next_x in Stage1Trainer.lookahead(trimmed(epoch)):
+            last = tr.step(x, y, next_x=next_x)
+        if last is not None:
+            print(f"[compact finetune] epoch {epoch} steps {tr.global_step} lr {tr.scheduler.get_epoch_values(epoch)[0]:.6g} loss {float(last['loss']):.4f}")
+        if valid_fn is not None:
+            acc = valid_fn(tr.model)
+            if best < acc:                                                                          # save-best (:393-399)
+                torch.save(tr.export(), args.output)
+                best = acc
+    if valid_fn is None:
+        torch.save(tr.export(), args.output)
+    print(json.dumps(dict(output=args.output, top1_before=before, top1_after=best if valid_fn else None, epochs=args.epochs, steps=tr.global_step,
+                          **_report(export))))
+    return tr
+
+
 def main(argv=None):
     args = _parser().parse_args(argv)
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    if args.cmd == "finetune":
+        return finetune(args, dev)
     if args.cmd == "export" or not args.compact:
         model = _dense_model(args, dev)
         export = export_compact(model, compact_plan(model, args.mlp_multiple))

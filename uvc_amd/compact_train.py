@@ -1,0 +1,435 @@
+"""Fine-tuning a compact model at its kept widths on MI355X.
+
+``CompactTrainableViT`` is the trainable twin of ``compact.CompactVisionTransformer``: the same flat float32 parameter buffer
+(uvc_vit_compact_layout), parameters exposed under the compact state_dict names as views into it, a training forward and backward
+through ``uvc_vit_compact_train_forward`` / ``uvc_vit_compact_backward`` (include/uvc_vit.h) and, in eval mode, the kernels and the
+bits of ``CompactVisionTransformer``.  The function being trained is ``compact.reference_logits``.
+
+``CompactTrainer`` is ``post_train.Stage2Trainer``'s step on that module: DistillationLoss against any dense teacher, global-norm
+clip, AdamW with timm's decay groups, ``lr = learning_rate * batch / 512``, the per-epoch cosine schedule.  What differs from the
+masked dense Stage 2 on purpose: the clip norm is the norm of the compact gradients.
+
+Padding entries (zero v-rows / proj columns, zero fc1 rows, b1 entries and fc2 columns) receive exactly zero gradients, so AdamW
+leaves them exactly zero; parameters no forward reads (norm1 of a block without heads, norm2 of one without units) are frozen, as
+torch leaves a parameter whose ``.grad`` is None.  ``patch_gating``, when the file has it, is used and frozen.
+"""
+from __future__ import annotations
+
+import copy
+import ctypes as C
+from argparse import Namespace
+
+import torch
+import torch.nn as nn
+
+from . import _lib as L
+from . import compact as CP
+
+MAX_TOKENS = 256
+_SLOTS = ["norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias", "norm2.weight",
+          "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias"]
+
+
+def _bind():
+    from .model_distilled import uvc_vit_cfg, uvc_vit_io, uvc_vit_offsets, uvc_vit_shadow_offsets
+    lib = CP._bind()
+    if not getattr(lib, "_compact_train_bound", False):
+        B = C.POINTER(L.uvc_compact_block)
+        cfgp = C.POINTER(uvc_vit_cfg)
+        lib.uvc_vit_compact_train_layout.argtypes = [cfgp, B, C.c_int32, C.POINTER(uvc_vit_offsets), C.POINTER(uvc_vit_shadow_offsets)]
+        lib.uvc_vit_compact_train_workspace_bytes.argtypes = [cfgp, B, C.c_int32, C.c_int32]
+        lib.uvc_vit_compact_train_workspace_bytes.restype = C.c_int64
+        lib.uvc_vit_compact_train_update_shadows.argtypes = [cfgp, B, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.uvc_vit_compact_frozen_ranges.argtypes = [cfgp, B, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]
+        for n in ("uvc_vit_compact_train_forward", "uvc_vit_compact_backward"):
+            getattr(lib, n).argtypes = [cfgp, B, C.c_int32, C.POINTER(uvc_vit_io), C.c_void_p]
+        for n in ("uvc_vit_compact_train_layout", "uvc_vit_compact_train_update_shadows", "uvc_vit_compact_frozen_ranges",
+                  "uvc_vit_compact_train_forward", "uvc_vit_compact_backward"):
+            getattr(lib, n).restype = C.c_int
+        lib._compact_train_bound = True
+    return lib
+
+
+def seq_len(cfg) -> int:
+    return (cfg["img_size"] // cfg["patch_size"]) ** 2 + (2 if cfg["enable_dist"] else 1)
+
+
+def unread_parameters(export: dict):
+    """Names of the state_dict tensors no forward reads: autograd through ``compact.reference_logits`` leaves their ``.grad`` None."""
+    out = []
+    for k, b in enumerate(export["blocks"]):
+        if not b["heads"]:
+            out += [f"blocks.{k}.{n}" for n in ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight")]
+        if not b["hidden"]:
+            out += [f"blocks.{k}.{n}" for n in ("norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight")]
+    if "patch_gating" in export["state_dict"]:
+        out.append("patch_gating")
+    return out
+
+
+def padding_masks(export: dict):
+    """{name: bool tensor} marking the padding entries of the restructured tensors (True = padding, exactly zero in a compact file)."""
+    out = {}
+    D = export["cfg"]["embed_dim"]
+    for k, b in enumerate(export["blocks"]):
+        p = f"blocks.{k}."
+        nh, dv, Fk = len(b["heads"]), b["v_dim"], b["hidden"]
+        rows = torch.zeros(nh * (128 + dv), dtype=torch.bool)
+        cols = torch.zeros(nh * dv, dtype=torch.bool)
+        for j, dims in enumerate(b["v_index"]):
+            rows[2 * nh * 64 + j * dv + len(dims):2 * nh * 64 + (j + 1) * dv] = True
+            cols[j * dv + len(dims):(j + 1) * dv] = True
+        out[p + "attn.qkv.weight"] = rows[:, None].expand(-1, D).clone()
+        out[p + "attn.qkv.bias"] = rows
+        out[p + "attn.proj.weight"] = cols[None, :].expand(D, -1).clone()
+        units = torch.zeros(Fk, dtype=torch.bool)
+        units[len(b["hidden_index"]):] = True
+        out[p + "mlp.fc1.weight"] = units[:, None].expand(-1, D).clone()
+        out[p + "mlp.fc1.bias"] = units
+        out[p + "mlp.fc2.weight"] = units[None, :].expand(D, -1).clone()
+    return out
+
+
+def with_state(export: dict, state_dict) -> dict:
+    """A version-1 compact dict with the source file's ``cfg`` / ``blocks`` and the given weights (float32, CPU)."""
+    CP.check_export(export)
+    sd = {k: state_dict[k].detach().to(device="cpu", dtype=torch.float32).reshape(v.shape).clone() for k, v in export["state_dict"].items()}
+    return dict(format=CP.FORMAT, version=CP.VERSION, cfg=copy.deepcopy(export["cfg"]), blocks=copy.deepcopy(export["blocks"]), state_dict=sd)
+
+
+class _CompactFunction(torch.autograd.Function):
+    """One autograd node for the whole model, as model_distilled._VitFunction: the HIP backward writes every gradient into the flat
+    gradient buffer (the ``.grad`` views); nothing flows back through autograd."""
+
+    @staticmethod
+    def forward(ctx, model, x, anchor):
+        logits, logits_dist = model._train_forward(x)
+        ctx.model = model
+        ctx.two = logits_dist is not None
+        return (logits, logits_dist) if ctx.two else logits
+
+    @staticmethod
+    def backward(ctx, *grads):
+        ctx.model._train_backward(grads[0], grads[1] if ctx.two else None)
+        return None, None, None
+
+
+class CompactTrainableViT(nn.Module):
+    """``model(x)`` in train mode returns ``((logits, logits_dist), macs)`` (``logits_dist is logits`` without the distillation
+    token), in eval mode what ``CompactVisionTransformer`` returns -- same kernels, same bits."""
+
+    def __init__(self, export: dict, precision: str = "bf16", device=None):
+        super().__init__()
+        from . import ops
+        from .model_distilled import uvc_vit_cfg, uvc_vit_offsets, uvc_vit_shadow_offsets
+        CP.check_export(export)
+        if precision == "bf16_f32resid":
+            raise NotImplementedError("compact models train in 'bf16' or 'fp32' (the float32 residual rows of 'bf16_f32resid' are a dense-model mode)")
+        if precision not in ("bf16", "fp32"):
+            raise ValueError("precision must be 'bf16' or 'fp32'")
+        dev = torch.device(device if device is not None else "cuda")
+        if dev.type != "cuda":
+            raise L.UvcHipError("uvc_amd models run on MI355X only (no CPU fallback)")
+        c = export["cfg"]
+        if seq_len(c) > MAX_TOKENS:
+            raise NotImplementedError(f"fine-tuning a compact model with {seq_len(c)} tokens: the attention backward at a value width takes at most "
+                                      f"{MAX_TOKENS} (384-px and patch-8 files can be evaluated, not trained)")
+        self._export, self.precision = export, precision
+        self.num_tokens = 2 if c["enable_dist"] else 1
+        self._cfg = uvc_vit_cfg(c["img_size"], c["patch_size"], c["in_chans"], c["num_classes"], c["embed_dim"], c["depth"], c["num_heads"],
+                                c["hidden"], self.num_tokens, ops.UVC_F32 if precision == "fp32" else ops.UVC_BF16)
+        self._cfg.ln_eps = float(c["ln_eps"])
+        nb = len(export["blocks"])
+        self._blocks = (L.uvc_compact_block * max(1, nb))()
+        for k, b in enumerate(export["blocks"]):
+            self._blocks[k].heads, self._blocks[k].v_dim, self._blocks[k].hidden = len(b["heads"]), b["v_dim"], b["hidden"]
+        self._nb = nb
+        self._off, self._soff = uvc_vit_offsets(), uvc_vit_shadow_offsets()
+        lib = _bind()
+        L.check(lib.uvc_vit_compact_train_layout(C.byref(self._cfg), self._blocks, nb, C.byref(self._off), C.byref(self._soff)),
+                "uvc_vit_compact_train_layout")
+        n = self._off.n_total
+        flat = torch.zeros(n, dtype=torch.float32)
+        for name, t in export["state_dict"].items():
+            o = self._offset(name)
+            flat[o:o + t.numel()] = t.reshape(-1).float()
+        self._flat = flat.to(dev)
+        self._flat_grad = torch.zeros(n, dtype=torch.float32, device=dev)
+        tsz = 4 if precision == "fp32" else 2
+        self._shadow = torch.zeros(max(1, self._soff.n_total) * tsz, dtype=torch.uint8, device=dev)
+        self._shadow_fresh = False
+        self._names = []
+        self._by_name = {}
+        for name, t in export["state_dict"].items():
+            o = self._offset(name)
+            p = nn.Parameter(self._flat[o:o + t.numel()].view(t.shape), requires_grad=name != "patch_gating")
+            self._by_name[name] = p
+            self._names.append(name)
+            self.register_parameter(name.replace(".", "__"), p)
+        cnt = C.c_int32()
+        ranges = (C.c_int64 * (4 * max(1, nb)))()
+        L.check(lib.uvc_vit_compact_frozen_ranges(C.byref(self._cfg), self._blocks, nb, ranges, 2 * max(1, nb), C.byref(cnt)),
+                "uvc_vit_compact_frozen_ranges")
+        self._frozen = [(int(ranges[2 * i]), int(ranges[2 * i + 1])) for i in range(cnt.value)]
+        self._unread = set(unread_parameters(export))
+        self._ws = {}
+        self._last = None
+        self.grad_accumulate = False
+        self.train()
+
+    # -- what FusedAdamW / clip_grad_norm_ read of a model -----------------------------------------------------------------------
+    @property
+    def n_flat(self):
+        return self._off.n_total
+
+    def _check_flat(self):
+        pass
+
+    def _extra_live_segments(self):
+        return []
+
+    def skipped_block_ranges(self):
+        return []
+
+    def _frozen_ranges(self):
+        """Parameters no forward reads (uvc_vit_compact_frozen_ranges); patch_gating lies behind n_main, where no optimiser step reaches."""
+        return list(self._frozen)
+
+    def _optim_small_tensors(self):
+        return []
+
+    def _slots(self):
+        return [(self._by_name[n], self._offset(n)) for n in self._names]
+
+    def named_parameters(self, *a, **k):
+        for n in self._names:
+            yield n, self._by_name[n]
+
+    def parameters(self, recurse=True):
+        for n in self._names:
+            yield self._by_name[n]
+
+    def no_weight_decay(self):
+        return {"pos_embed", "cls_token", "dist_token"}
+
+    def mark_weights_changed(self):
+        self._shadow_fresh = False
+
+    def state_dict(self, *a, **k):
+        return {n: self._by_name[n].detach().clone() for n in self._names}
+
+    def load_state_dict(self, sd, strict=True):
+        missing = [n for n in self._names if n not in sd]
+        extra = [n for n in sd if n not in self._by_name]
+        if strict and (missing or extra):
+            raise RuntimeError(f"compact state_dict mismatch: missing {missing}, unexpected {extra}")
+        with torch.no_grad():
+            for n in self._names:
+                if n in sd:
+                    self._by_name[n].copy_(sd[n].to(self._flat.device).reshape(self._by_name[n].shape))
+        self.mark_weights_changed()
+
+    def _offset(self, name):
+        o = self._off
+        if name.startswith("blocks."):
+            _, k, rest = name.split(".", 2)
+            return o.blk[int(k)][_SLOTS.index(rest)]
+        return dict(cls_token=o.cls_token, dist_token=o.dist_token, pos_embed=o.pos_embed, patch_gating=o.patch_gating,
+                    **{"patch_embed.proj.weight": o.patch_w, "patch_embed.proj.bias": o.patch_b, "norm.weight": o.norm_w, "norm.bias": o.norm_b,
+                       "head.weight": o.head_w, "head.bias": o.head_b, "head_dist.weight": o.headd_w, "head_dist.bias": o.headd_b})[name]
+
+    def grad_views(self):
+        """Point ``.grad`` of every parameter a forward reads at its slice of the flat gradient buffer; the others keep None."""
+        base = self._flat_grad.data_ptr()
+        for n in self._names:
+            p = self._by_name[n]
+            if n in self._unread:
+                p.grad = None
+                continue
+            off = self._offset(n)
+            if p.grad is None or p.grad.data_ptr() != base + 4 * off:
+                p.grad = self._flat_grad[off:off + p.numel()].view(p.shape)
+
+    # -- reference-style API ---------------------------------------------------------------------------------------------------------
+    def num_params(self) -> int:
+        return sum(int(self._by_name[n].numel()) for n in self._names if n != "patch_gating")
+
+    def macs(self, B=1) -> int:
+        return CP.compact_macs(self._export, B, padded=True)
+
+    def export(self) -> dict:
+        """A version-1 compact dict with the current weights and the source file's ``cfg`` / ``blocks``."""
+        return with_state(self._export, self.state_dict())
+
+    def _refresh_shadows(self):
+        if not self._shadow_fresh:
+            L.check(_bind().uvc_vit_compact_train_update_shadows(C.byref(self._cfg), self._blocks, self._nb, L.ptr(self._flat), L.ptr(self._shadow),
+                                                                 L.cur_stream()), "uvc_vit_compact_train_update_shadows")
+            self._shadow_fresh = True
+
+    def _prep(self, x):
+        L.require_cuda(x)
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            x = x.contiguous().float()
+        c = self._export["cfg"]
+        if tuple(x.shape[1:]) != (c["in_chans"], c["img_size"], c["img_size"]):
+            raise AssertionError(f"Input image size ({x.shape[2]}*{x.shape[3]}) doesn't match model ({c['img_size']}*{c['img_size']}).")
+        return x
+
+    def _workspace(self, B, training):
+        key = (B, bool(training))
+        if key not in self._ws:
+            lib = _bind()
+            fn = lib.uvc_vit_compact_train_workspace_bytes if training else lib.uvc_vit_compact_workspace_bytes
+            n = fn(C.byref(self._cfg), self._blocks, self._nb, B)
+            if n < 0:
+                raise L.UvcHipError(f"compact workspace query failed: {L.lib().uvc_last_error().decode()}")
+            self._ws = {k: v for k, v in self._ws.items() if k[1] != bool(training)}
+            self._ws[key] = torch.empty(n, dtype=torch.uint8, device=self._flat.device)
+        return self._ws[key]
+
+    def _io(self, x, B, training):
+        from . import ops
+        from .model_distilled import uvc_vit_io
+        c, dev = self._export["cfg"], self._flat.device
+        ws = self._workspace(B, training)
+        mask = None
+        if c["patch_gating"]:
+            P = (c["img_size"] // c["patch_size"]) ** 2
+            mask = torch.empty(B, P, device=dev)
+            o = self._off.patch_gating
+            ops.patch_gate_sigmoid(self._flat[o:o + P], mask, B, P, bool(c["patch_hard"]))
+        io = uvc_vit_io()
+        io.params, io.shadow, io.grads = L.ptr(self._flat), L.ptr(self._shadow), L.ptr(self._flat_grad)
+        io.workspace, io.workspace_bytes = L.ptr(ws), ws.numel()
+        io.x, io.patch_mask, io.batch, io.training = L.ptr(x), L.ptr(mask), B, int(training)
+        return io, mask
+
+    def _run(self, x, training):
+        x = self._prep(x)
+        B = x.shape[0]
+        self._refresh_shadows()
+        dev = self._flat.device
+        io, mask = self._io(x, B, training)
+        nc = self._export["cfg"]["num_classes"]
+        logits = torch.empty(B, nc, device=dev)
+        logits_dist = torch.empty(B, nc, device=dev) if self.num_tokens == 2 else None
+        io.logits, io.logits_dist = L.ptr(logits), L.ptr(logits_dist)
+        lib = _bind()
+        fn, what = (lib.uvc_vit_compact_train_forward, "uvc_vit_compact_train_forward") if training else (lib.uvc_vit_compact_forward, "uvc_vit_compact_forward")
+        L.check(fn(C.byref(self._cfg), self._blocks, self._nb, C.byref(io), L.cur_stream()), what)
+        self._last = dict(x=x, B=B, mask=mask) if training else self._last
+        return logits, logits_dist
+
+    def _train_forward(self, x):
+        return self._run(x, True)
+
+    def _train_backward(self, d_logits, d_logits_dist):
+        st = self._last
+        if st is None:
+            raise RuntimeError("backward without a training forward")
+        self.grad_views()
+        io, _ = self._io(st["x"], st["B"], True)
+        io.patch_mask = L.ptr(st["mask"])
+        d_logits = d_logits.contiguous()
+        io.d_logits = L.ptr(d_logits)
+        if self.num_tokens == 2:
+            d_logits_dist = d_logits_dist.contiguous()
+            io.d_logits_dist = L.ptr(d_logits_dist)
+        L.check(_bind().uvc_vit_compact_backward(C.byref(self._cfg), self._blocks, self._nb, C.byref(io), L.cur_stream()), "uvc_vit_compact_backward")
+
+    def forward(self, x):
+        macs = self.macs(x.shape[0])
+        if self.training and torch.is_grad_enabled():
+            out = _CompactFunction.apply(self, x, self._by_name["cls_token"])
+            return (out if self.num_tokens == 2 else (out, out)), macs
+        with torch.no_grad():
+            o, od = self._run(x, False)
+        if self.training:
+            return (o, o if od is None else od), macs
+        return (o if od is None else (o + od) / 2), macs
+
+
+def _refuse(args, precision):
+    if int(getattr(args, "gradient_accumulation_steps", 1)) > 1:
+        raise NotImplementedError("compact fine-tuning runs one micro-batch per step (gradient_accumulation_steps > 1 is not supported)")
+    if int(getattr(args, "local_rank", -1)) != -1:
+        raise NotImplementedError("compact fine-tuning is single-GPU (data-parallel runs, --local_rank, are not supported)")
+    if precision == "bf16_f32resid":
+        raise NotImplementedError("compact models train in 'bf16' or 'fp32' (the float32 residual rows of 'bf16_f32resid' are a dense-model mode)")
+
+
+class CompactTrainer:
+    """``Stage2Trainer``'s surface on a compact model: ``begin_epoch``, ``step(x, y, next_x=None)`` -> loss, outputs, gnorm;
+    ``state_dict`` / ``load_state_dict`` resume bit for bit."""
+
+    def __init__(self, args: Namespace, export: dict, device="cuda", teacher_state=None):
+        from .losses import DistillationLoss, SoftTargetCrossEntropy
+        from .optim import create_optimizer
+        from .scheduler import create_scheduler
+        from .stage1 import build_teacher
+        CP.check_export(export)
+        _refuse(args, args.precision)
+        self.args = args
+        c = export["cfg"]
+        if seq_len(c) > MAX_TOKENS:
+            raise NotImplementedError(f"fine-tuning a compact model with {seq_len(c)} tokens: the attention backward at a value width takes at most "
+                                      f"{MAX_TOKENS} (384-px and patch-8 files can be evaluated, not trained)")
+        self.model = CompactTrainableViT(export, precision=args.precision, device=device)
+        teacher, self.teacher_source = None, None
+        if args.distillation_type != "none":
+            # the teacher is a dense model: by default the architecture the compact file was pruned from, at the file's image size and classes
+            ta = copy.copy(args)
+            ta.model_type, ta.img_size, ta.num_classes, ta.enable_deit = "custom", c["img_size"], c["num_classes"], c["enable_dist"]
+            ta.model_cfg = dict(patch_size=c["patch_size"], embed_dim=c["embed_dim"], depth=c["depth"], num_heads=c["num_heads"],
+                                mlp_ratio=c["hidden"] / c["embed_dim"])
+            teacher, self.teacher_source = build_teacher(ta, device, teacher_state, verbose=True)
+        self.teacher = teacher
+        self.criterion = DistillationLoss(SoftTargetCrossEntropy(), teacher, args.distillation_type, args.distillation_alpha, args.distillation_tau)
+        args.lr = args.learning_rate * args.train_batch_size / 512.0
+        self.optimizer = create_optimizer(args, self.model)
+        self.scheduler, self.num_epochs = create_scheduler(args, self.optimizer)
+        self.model.train()
+        self.global_step = 0
+        self.epoch = 0
+
+    def begin_epoch(self, epoch: int):
+        self.epoch = epoch
+        self.model.train()
+        self.scheduler.step(epoch)
+
+    def step(self, x, y, zero_grad=True, next_x=None):
+        from .losses import unit_gradient
+        from .optim import clip_grad_norm_
+        a = self.args
+        overlap = bool(getattr(a, "overlap_teacher", 1))
+        if overlap and not self.criterion.has_prefetch(x):
+            self.criterion.prefetch(x)
+        outputs, _ = self.model(x)
+        loss = self.criterion(x, outputs, y)
+        loss.backward(unit_gradient(loss.device))
+        if overlap and next_x is not None:
+            self.criterion.prefetch(next_x)
+        gnorm = clip_grad_norm_(self.model, a.max_grad_norm)
+        self.optimizer.step()
+        self.global_step += 1
+        if zero_grad:
+            self.optimizer.zero_grad()
+        return dict(loss=loss.detach(), outputs=outputs, gnorm=gnorm, stepped=True)
+
+    def export(self) -> dict:
+        return self.model.export()
+
+    def state_dict(self):
+        o = self.optimizer
+        return dict(format="uvc_amd.compact_train.v1", model=self.model.state_dict(),
+                    adamw=dict(exp_avg=o.exp_avg.clone(), exp_avg_sq=o.exp_avg_sq.clone(), steps=dict(o.steps), lr=o.param_groups[0]["lr"]),
+                    progress=dict(global_step=self.global_step, epoch=self.epoch))
+
+    def load_state_dict(self, sd):
+        if sd.get("format") != "uvc_amd.compact_train.v1":
+            raise ValueError("not a uvc_amd compact training state")
+        self.model.load_state_dict(sd["model"])
+        a, o = sd["adamw"], self.optimizer
+        o.exp_avg.copy_(a["exp_avg"]); o.exp_avg_sq.copy_(a["exp_avg_sq"]); o.steps = dict(a["steps"]); o.param_groups[0]["lr"] = a["lr"]
+        self.global_step, self.epoch = int(sd["progress"]["global_step"]), int(sd["progress"]["epoch"])

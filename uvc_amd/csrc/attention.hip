@@ -135,9 +135,9 @@ __device__ __forceinline__ void stage_rows2(char* lds0, const T* g0, size_t ld0,
   }
 }
 
-template <typename T>
+template <typename T, int RB = Geom<T>::ROWB>
 __device__ __forceinline__ typename Mma<T>::Frag row_frag_lds(const char* lds, int row, int chunk) {
-  return *reinterpret_cast<const typename Mma<T>::Frag*>(lds + row * Geom<T>::ROWB + chunk * 16);
+  return *reinterpret_cast<const typename Mma<T>::Frag*>(lds + row * RB + chunk * 16);
 }
 template <typename T>
 __device__ __forceinline__ typename Mma<T>::Frag row_frag_global(const T* g, size_t ld_g, int row, int nvalid, int chunk) {
@@ -148,6 +148,24 @@ __device__ __forceinline__ typename Mma<T>::Frag row_frag_global(const T* g, siz
   const u32x4 z = {0u, 0u, 0u, 0u};
   return __builtin_bit_cast(typename Mma<T>::Frag, z);
 }
+// Row fragments of a DV-wide value-side operand (V, dO, O rows of a compact layout, uvc_attn_args.v_dim): DV / KSTEP k-steps rounded up; in bf16
+// DV = 16 and 48 end on half a 32-wide step, whose missing chunks (ks * 4 + g >= DV / CH) are zeros in BOTH operands -- the LDS bytes behind a
+// row's DV columns are never written.  DV = 64: every chunk exists and the tests fold away.
+template <typename T, int DV> struct VFrag {
+  static constexpr int KS = (DV + Mma<T>::KSTEP - 1) / Mma<T>::KSTEP, NCH = DV / Mma<T>::CH;
+  static __device__ __forceinline__ typename Mma<T>::Frag zero() {
+    const u32x4 z = {0u, 0u, 0u, 0u};
+    return __builtin_bit_cast(typename Mma<T>::Frag, z);
+  }
+  static __device__ __forceinline__ typename Mma<T>::Frag lds(const char* img, int row, int chunk) {
+    if (DV % Mma<T>::KSTEP != 0 && chunk >= NCH) return zero();
+    return row_frag_lds<T, VGeom<T, DV>::ROWB>(img, row, chunk);
+  }
+  static __device__ __forceinline__ typename Mma<T>::Frag global(const T* g, size_t ld_g, int row, int nvalid, int chunk) {
+    if (DV % Mma<T>::KSTEP != 0 && chunk >= NCH) return zero();
+    return row_frag_global<T>(g, ld_g, row, nvalid, chunk);
+  }
+};
 template <typename T> __device__ __forceinline__ float frag_dot(const typename Mma<T>::Frag& a, const typename Mma<T>::Frag& b);
 template <> __device__ __forceinline__ float frag_dot<bf16_t>(const bf16x8& a, const bf16x8& b) {
   const u32x4 ua = __builtin_bit_cast(u32x4, a), ub = __builtin_bit_cast(u32x4, b);
@@ -259,7 +277,7 @@ struct AttnArgs {
   int B, N, H;
   float scale;
   const int* head_keep;
-  int v_dim;         // forward: 0 = [B, N, 3, H, 64]; 16 / 32 / 48 = compact rows [q H*64 | k H*64 | v H*v_dim], o [B, N, H*v_dim]
+  int v_dim;         // forward and uvc_attention_bwd_vdim: 0 = [B, N, 3, H, 64]; 16 / 32 / 48 = compact rows [q H*64 | k H*64 | v H*v_dim], o [B, N, H*v_dim]
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -448,40 +466,50 @@ __global__ __launch_bounds__(sizeof(T) == 2 ? 512 : 256, sizeof(T) == 2 ? 4 : 1)
 
 // ------------------------------------------------------------------------------------------------
 // backward, dQ (and delta = rowsum(dO * O)).  K, V in LDS.
-template <typename T, int NT16>
+// DV < 64 (uvc_attention_bwd_vdim): the compact layout of the forward -- qkv / dqkv rows [q H*64 | k H*64 | v H*DV], o / dout rows H*DV; delta and
+// dP = dO V^T contract over DV, the V image has DV columns at VGeom's stride.  q, k and dq keep 64 dims.
+template <typename T, int NT16, int DV = HD>
 __global__ __launch_bounds__(512) void k_attn_bwd_dq(AttnArgs a) {
   typedef Mma<T> MM;
   typedef Geom<T> G;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NP = NT16 * 16;
   char* sK = smem;
+  typedef VFrag<T, DV> VF;
   char* sV = smem + NP * G::ROWB;
   const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6, g = lane >> 4, li = lane & 15;
-  const size_t ldq = (size_t)3 * a.H * HD, ldo = (size_t)a.H * HD;
+  const size_t ldq = (size_t)a.H * (2 * HD + DV), ldo = (size_t)a.H * DV;
   const T* qb = reinterpret_cast<const T*>(a.qkv) + (size_t)b * a.N * ldq + h * HD;
   const T* kb = qb + a.H * HD;
-  const T* vb = qb + 2 * a.H * HD;
-  const T* ob = reinterpret_cast<const T*>(a.o) + (size_t)b * a.N * ldo + h * HD;
-  const T* dob = reinterpret_cast<const T*>(a.dout) + (size_t)b * a.N * ldo + h * HD;
+  const T* vb = qb + 2 * a.H * HD - h * (HD - DV);            // the v columns lie behind q and k of all heads, DV per head
+  const T* ob = reinterpret_cast<const T*>(a.o) + (size_t)b * a.N * ldo + h * DV;
+  const T* dob = reinterpret_cast<const T*>(a.dout) + (size_t)b * a.N * ldo + h * DV;
   T* dqb = reinterpret_cast<T*>(a.dqkv) + (size_t)b * a.N * ldq + h * HD;
-  if (a.head_keep && a.head_keep[h] == 0) {                 // pruned head (see uvc_attn_args.head_keep): dO is exactly zero, so is dq
+  if (DV == HD && a.head_keep && a.head_keep[h] == 0) {                 // pruned head (see uvc_attn_args.head_keep): dO is exactly zero, so is dq
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
     for (int i = threadIdx.x; i < a.N * 16; i += blockDim.x) Store4<T>::st(dqb + (size_t)(i >> 4) * ldq + (i & 15) * 4, z);
     return;
   }
-  stage_rows2<T>(sK, kb, ldq, sV, vb, ldq, a.N, NP);
+  if constexpr (DV == HD) {
+    stage_rows2<T>(sK, kb, ldq, sV, vb, ldq, a.N, NP);
+  } else {
+    stage_rows<T>(sK, kb, ldq, a.N, NP);
+    stage_rows<T, DV, VGeom<T, DV>::ROWB>(sV, vb, ldq, a.N, NP);
+  }
   __syncthreads();
   const int nqt = (a.N + 15) / 16;
   for (int qt = w; qt < nqt; qt += nw) {
     const int q = qt * 16 + li;
-    typename MM::Frag qf[G::KS], dof[G::KS];
+    typename MM::Frag qf[G::KS], dof[VF::KS];
     float dl = 0.f;
 #pragma unroll
     for (int ks = 0; ks < G::KS; ++ks) {
       qf[ks] = row_frag_global<T>(qb, ldq, q, a.N, ks * 4 + g);
-      dof[ks] = row_frag_global<T>(dob, ldo, q, a.N, ks * 4 + g);
-      dl += frag_dot<T>(dof[ks], row_frag_global<T>(ob, ldo, q, a.N, ks * 4 + g));
+      if (ks < VF::KS) {
+        dof[ks] = VF::global(dob, ldo, q, a.N, ks * 4 + g);
+        dl += frag_dot<T>(dof[ks], VF::global(ob, ldo, q, a.N, ks * 4 + g));
+      }
     }
     dl = sum_rows4(dl);
     const float c2 = a.scale * 1.44269504088896340736f;
@@ -500,7 +528,7 @@ __global__ __launch_bounds__(512) void k_attn_bwd_dq(AttnArgs a) {
 #pragma unroll
         for (int ks = 0; ks < G::KS; ++ks) {
           c = MM::mma(row_frag_lds<T>(sK, t * 16 + li, ks * 4 + g), qf[ks], c);
-          dp = MM::mma(row_frag_lds<T>(sV, t * 16 + li, ks * 4 + g), dof[ks], dp);
+          if (ks < VF::KS) dp = MM::mma(VF::lds(sV, t * 16 + li, ks * 4 + g), dof[ks], dp);
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -520,26 +548,29 @@ __global__ __launch_bounds__(512) void k_attn_bwd_dq(AttnArgs a) {
 
 // ------------------------------------------------------------------------------------------------
 // backward, dK and dV.  Q, dO (+ lse, delta) in LDS; each wave owns 16-key tiles.
-template <typename T, int NT16>
+// DV < 64: as k_attn_bwd_dq; the dO image has DV columns at VGeom's stride, dV has DV / 16 accumulator tiles.  k and dk keep 64 dims.
+template <typename T, int NT16, int DV = HD>
 __global__ __launch_bounds__(512) void k_attn_bwd_dkv(AttnArgs a) {
   typedef Mma<T> MM;
   typedef Geom<T> G;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NP = NT16 * 16;
   char* sQ = smem;
+  typedef VFrag<T, DV> VF;
+  constexpr int VROWB = VGeom<T, DV>::ROWB;
   char* sDO = smem + NP * G::ROWB;
-  float* sLse = reinterpret_cast<float*>(smem + 2 * NP * G::ROWB);
+  float* sLse = reinterpret_cast<float*>(smem + NP * (G::ROWB + VROWB));
   float* sDel = sLse + NP;
   const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6, g = lane >> 4, li = lane & 15;
-  const size_t ldq = (size_t)3 * a.H * HD, ldo = (size_t)a.H * HD;
+  const size_t ldq = (size_t)a.H * (2 * HD + DV), ldo = (size_t)a.H * DV;
   const T* qb = reinterpret_cast<const T*>(a.qkv) + (size_t)b * a.N * ldq + h * HD;
   const T* kb = qb + a.H * HD;
-  const T* vb = qb + 2 * a.H * HD;
-  const T* dob = reinterpret_cast<const T*>(a.dout) + (size_t)b * a.N * ldo + h * HD;
+  const T* vb = qb + 2 * a.H * HD - h * (HD - DV);            // the v columns lie behind q and k of all heads, DV per head
+  const T* dob = reinterpret_cast<const T*>(a.dout) + (size_t)b * a.N * ldo + h * DV;
   T* dkb = reinterpret_cast<T*>(a.dqkv) + (size_t)b * a.N * ldq + (a.H + h) * HD;
-  T* dvb = dkb + a.H * HD;
-  if (a.head_keep && a.head_keep[h] == 0) {                 // pruned head: dk = dv = 0 exactly
+  T* dvb = dkb + a.H * HD - h * (HD - DV);
+  if (DV == HD && a.head_keep && a.head_keep[h] == 0) {                 // pruned head: dk = dv = 0 exactly
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
     for (int i = threadIdx.x; i < a.N * 16; i += blockDim.x) {
       Store4<T>::st(dkb + (size_t)(i >> 4) * ldq + (i & 15) * 4, z);
@@ -547,7 +578,12 @@ __global__ __launch_bounds__(512) void k_attn_bwd_dkv(AttnArgs a) {
     }
     return;
   }
-  stage_rows2<T>(sQ, qb, ldq, sDO, dob, ldo, a.N, NP);
+  if constexpr (DV == HD) {
+    stage_rows2<T>(sQ, qb, ldq, sDO, dob, ldo, a.N, NP);
+  } else {
+    stage_rows<T>(sQ, qb, ldq, a.N, NP);
+    stage_rows<T, DV, VROWB>(sDO, dob, ldo, a.N, NP);
+  }
   for (int i = threadIdx.x; i < NP; i += blockDim.x) {      // lse pre-multiplied by log2(e); +inf on padded queries -> p = 0
     sLse[i] = i < a.N ? a.lse[((size_t)b * a.H + h) * a.N + i] * 1.44269504088896340736f : INFINITY;
     sDel[i] = i < a.N ? a.delta[((size_t)b * a.H + h) * a.N + i] : 0.f;
@@ -557,15 +593,18 @@ __global__ __launch_bounds__(512) void k_attn_bwd_dkv(AttnArgs a) {
   const int nkt = (a.N + 15) / 16;
   for (int kt = w; kt < nkt; kt += nw) {
     const int key = kt * 16 + li;
-    typename MM::Frag kf[G::KS], vf[G::KS];
+    typename MM::Frag kf[G::KS], vf[VF::KS];
 #pragma unroll
     for (int ks = 0; ks < G::KS; ++ks) {
       kf[ks] = row_frag_global<T>(kb, ldq, key, a.N, ks * 4 + g);
-      vf[ks] = row_frag_global<T>(vb, ldq, key, a.N, ks * 4 + g);
+      if (ks < VF::KS) vf[ks] = VF::global(vb, ldq, key, a.N, ks * 4 + g);
     }
-    f32x4 dk[4], dv[4];
+    f32x4 dk[4], dv[DV / 16];
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) { dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    for (int dt = 0; dt < 4; ++dt) {
+      dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (dt < DV / 16) dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 #pragma unroll 1
     for (int s = 0; s < NT16 / G::TPS; ++s) {
       f32x4 pp[G::TPS], ds[G::TPS];
@@ -576,7 +615,7 @@ __global__ __launch_bounds__(512) void k_attn_bwd_dkv(AttnArgs a) {
 #pragma unroll
         for (int ks = 0; ks < G::KS; ++ks) {
           c = MM::mma(row_frag_lds<T>(sQ, t * 16 + li, ks * 4 + g), kf[ks], c);
-          dp = MM::mma(row_frag_lds<T>(sDO, t * 16 + li, ks * 4 + g), vf[ks], dp);
+          if (ks < VF::KS) dp = MM::mma(VF::lds(sDO, t * 16 + li, ks * 4 + g), vf[ks], dp);
         }
         const f32x4 l4 = *reinterpret_cast<const f32x4*>(sLse + t * 16 + g * 4);
         const f32x4 d4 = *reinterpret_cast<const f32x4*>(sDel + t * 16 + g * 4);
@@ -591,13 +630,13 @@ __global__ __launch_bounds__(512) void k_attn_bwd_dkv(AttnArgs a) {
       const typename MM::Frag dsf = MM::pack(ds[0], ds[G::TPS - 1]);
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        dv[dt] = MM::mma(TrFrag<T>::ld(sDO, G::ROWB, s * MM::KSTEP, dt * 16, lane), pf, dv[dt]);
+        if (dt < DV / 16) dv[dt] = MM::mma(TrFrag<T>::ld(sDO, VROWB, s * MM::KSTEP, dt * 16, lane), pf, dv[dt]);
         dk[dt] = MM::mma(TrFrag<T>::ld(sQ, G::ROWB, s * MM::KSTEP, dt * 16, lane), dsf, dk[dt]);
       }
     }
     if (key < a.N) {
       store_tile16<T>(dkb + (size_t)key * ldq, g, dk, 1.0f);
-      store_tile16<T>(dvb + (size_t)key * ldq, g, dv, 1.0f);
+      store_out<T, DV>(dvb + (size_t)key * ldq, g, dv, 1.0f);
     }
   }
 }
@@ -1489,15 +1528,13 @@ template <typename T, int NT16, int DV = HD> int launch(const AttnArgs& a, int w
       UVC_MAX_LDS(sh, k_attn_fwd<T, NT16, 8, -1, DV>);
       k_attn_fwd<T, NT16, 8, -1, DV><<<fgrid, sizeof(T) == 2 ? 512 : 256, sh, st>>>(a);
     }
-  } else if constexpr (DV == HD) {
-    if (which == 1) {
-      UVC_MAX_LDS(sh, k_attn_bwd_dq<T, NT16>);
-      k_attn_bwd_dq<T, NT16><<<grid, threads, sh, st>>>(a);
-    } else {
-      sh += (size_t)2 * NP * sizeof(float);
-      UVC_MAX_LDS(sh, k_attn_bwd_dkv<T, NT16>);
-      k_attn_bwd_dkv<T, NT16><<<grid, threads, sh, st>>>(a);
-    }
+  } else if (which == 1) {                                 // (DV < 64: from uvc_attention_bwd_vdim alone)
+    UVC_MAX_LDS(sh, k_attn_bwd_dq<T, NT16, DV>);
+    k_attn_bwd_dq<T, NT16, DV><<<grid, threads, sh, st>>>(a);
+  } else {
+    sh += (size_t)2 * NP * sizeof(float);
+    UVC_MAX_LDS(sh, k_attn_bwd_dkv<T, NT16, DV>);
+    k_attn_bwd_dkv<T, NT16, DV><<<grid, threads, sh, st>>>(a);
   }
   UVC_CHECK_LAUNCH();
   return UVC_OK;
@@ -1510,6 +1547,7 @@ template <typename T, int DV = HD> int dispatch(const AttnArgs& a, int which, hi
   if (nt <= 8) return launch<T, 8, DV>(a, which, st);
   if (nt <= 14) return launch<T, 14, DV>(a, which, st);
   if (nt <= 16) return launch<T, 16, DV>(a, which, st);
+  if (DV != HD && which != 0) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "attention backward at a value width: N <= 256 (the streaming pair has no v_dim form)");
   if (a.N <= LONG_MAX_N) return launch_long<T, DV>(a, which, st);
   return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "attention: sequence length > 1026 not supported");
 }
@@ -1628,4 +1666,26 @@ extern "C" int uvc_attention_bwd(const uvc_attn_args* p, void* stream) {
 #endif
   if (int e = dispatch<bf16_t>(a, 1, st)) return e;
   return dispatch<bf16_t>(a, 2, st);
+}
+
+template <typename T> int dispatch_bwd_vdim(const AttnArgs& a, hipStream_t st) {
+  switch (a.v_dim) {
+    case 16: if (int e = dispatch<T, 16>(a, 1, st)) return e; return dispatch<T, 16>(a, 2, st);
+    case 32: if (int e = dispatch<T, 32>(a, 1, st)) return e; return dispatch<T, 32>(a, 2, st);
+    case 48: if (int e = dispatch<T, 48>(a, 1, st)) return e; return dispatch<T, 48>(a, 2, st);
+    default: if (int e = dispatch<T>(a, 1, st)) return e; return dispatch<T>(a, 2, st);     // 64: the kernels of uvc_attention_bwd(variant = 1)
+  }
+}
+
+extern "C" int uvc_attention_bwd_vdim(const uvc_attn_args* p, void* stream) {
+  if (!p || !p->qkv || !p->o || !p->lse || !p->dout || !p->dqkv || !p->delta) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_attention_bwd_vdim: null pointer");
+  if (p->head_dim != HD) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_attention_bwd_vdim: head_dim must be 64");
+  if (p->B <= 0 || p->N <= 0 || p->H <= 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_attention_bwd_vdim: empty problem");
+  if (p->dtype != UVC_F32 && p->dtype != UVC_BF16) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_attention_bwd_vdim: bad dtype");
+  if (p->v_dim != 16 && p->v_dim != 32 && p->v_dim != 48 && p->v_dim != 64) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_attention_bwd_vdim: v_dim must be 16, 32, 48 or 64");
+  if (p->head_keep) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_attention_bwd_vdim: takes no head_keep (a compact model has no pruned heads left)");
+  if (p->N > 256) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_attention_bwd_vdim: N <= 256 (the streaming backward pair has no v_dim form)");
+  if ((int64_t)p->B * p->H > 0x7fffffff) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_attention_bwd_vdim: too many workgroups");
+  const AttnArgs a = conv(p);
+  return p->dtype == UVC_F32 ? dispatch_bwd_vdim<float>(a, (hipStream_t)stream) : dispatch_bwd_vdim<bf16_t>(a, (hipStream_t)stream);
 }

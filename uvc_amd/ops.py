@@ -113,6 +113,14 @@ def attention_bwd(qkv, o, lse, dout, dqkv, delta, B, N, H, dtype, head_keep=None
     L.check(L.lib().uvc_attention_bwd(C.byref(a), L.cur_stream()), "uvc_attention_bwd")
 
 
+def attention_bwd_vdim(qkv, o, lse, dout, dqkv, delta, B, N, H, v_dim, dtype):
+    """The attention backward at a compact model's value width (include/uvc_kernels.h: uvc_attention_bwd_vdim): qkv / dqkv rows
+    [q H*64 | k H*64 | v H*v_dim], o / dout [B, N, H*v_dim].  v_dim 16, 32, 48 or 64, N <= 256."""
+    a = _attn_args(qkv, o, lse, B, N, H, dtype, dout, dqkv, delta)
+    a.v_dim = int(v_dim)
+    L.check(L.lib().uvc_attention_bwd_vdim(C.byref(a), L.cur_stream()), "uvc_attention_bwd_vdim")
+
+
 def qkv_attention_supported(B, N, H, D, dtype):
     return bool(L.lib().uvc_qkv_attention_supported(B, N, H, D, dtype))
 

@@ -50,7 +50,11 @@ def _clip_state(model):
 
 
 def _small_tensors(model):
-    """(name, parameter, offset) of the conditionally-active tensors."""
+    """(name, parameter, offset) of the conditionally-active tensors (a model without gate logits or a patch scorer -- a compact
+    model, compact_train.py -- states its own list)."""
+    own = getattr(model, "_optim_small_tensors", None)
+    if own is not None:
+        return own()
     o = model._off
     out = [("gate", model.block_skip_gating, o.gate)]
     if getattr(model, "gumbel", None) is not None:
@@ -80,7 +84,7 @@ class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, max_grad_norm=None,
                  filter_bias_and_bn=False):
         if not hasattr(model, "_flat"):
-            raise L.UvcHipError("FusedAdamW needs a uvc_amd DistilledVisionTransformer (flat parameter buffer)")
+            raise L.UvcHipError("FusedAdamW needs a uvc_amd model over a flat parameter buffer (DistilledVisionTransformer, CompactTrainableViT)")
         model._check_flat()
         super().__init__(list(model.parameters()), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.model = model

@@ -244,36 +244,43 @@ def eval_model(args, device, checkpoint=None, model_path=None):
     return model
 
 
-def main(argv=None):
-    """Stage-2 run: loads a Stage-1 checkpoint and fine-tunes it on synthetic batches (``--synthetic 1``, the default) or on
-    ``--dataset`` under ``--data_dir`` (``--synthetic 0``: uvc_amd/data.py, with the reference's Mixup / CutMix, post_train.py:614-621)."""
-    p = argparse.ArgumentParser(description="UVC Stage-2 masked fine-tune on MI355X")
+def add_stage2_flags(p, skip=()):
+    """Stage 2's command-line flags on the parser ``p`` (``default_args`` as ``--name`` flags, then the run, data, Mixup and teacher
+    flags); ``skip``: names a caller defines itself."""
+    add = lambda *names, **kw: None if names[0].lstrip("-") in skip else p.add_argument(*names, **kw)
     d = default_args()
     for k, v in vars(d).items():
         if v is None or isinstance(v, (list, tuple)):
-            p.add_argument("--" + k, default=v)
+            add("--" + k, default=v)
         else:
-            p.add_argument("--" + k, type=type(v), default=v)
-    p.add_argument("--checkpoint_dir", type=str, default=None, help="Stage-1 checkpoint (bare state_dict)")
-    p.add_argument("--steps", type=int, default=20, help="steps per synthetic epoch")
-    p.add_argument("--model_cfg", type=str, default=None, help="JSON dims for a --model_type outside models/configs.py (tests)")
-    p.add_argument("--eval_steps", type=int, default=2, help="synthetic validation batches per epoch (valid(), post_train.py:188-234)")
-    p.add_argument("--eval_batch_size", type=int, default=64)
-    p.add_argument("--synthetic", type=int, default=1, help="synthetic batches; 0 = read --dataset under --data_dir")
-    p.add_argument("--dataset", choices=["cifar10", "cifar100", "imagenet"], default="imagenet")         # post_train.py:411-414
-    p.add_argument("--data_dir", default="/ssd1/xinyu/dataset/imagenet2012")
-    p.add_argument("--num_workers", type=int, default=8, help="decode threads (at most 16)")                   # post_train.py:417
+            add("--" + k, type=type(v), default=v)
+    add("--checkpoint_dir", type=str, default=None, help="Stage-1 checkpoint (bare state_dict)")
+    add("--steps", type=int, default=20, help="steps per synthetic epoch")
+    add("--model_cfg", type=str, default=None, help="JSON dims for a --model_type outside models/configs.py (tests)")
+    add("--eval_steps", type=int, default=2, help="synthetic validation batches per epoch (valid(), post_train.py:188-234)")
+    add("--eval_batch_size", type=int, default=64)
+    add("--synthetic", type=int, default=1, help="synthetic batches; 0 = read --dataset under --data_dir")
+    add("--dataset", choices=["cifar10", "cifar100", "imagenet"], default="imagenet")         # post_train.py:411-414
+    add("--data_dir", default="/ssd1/xinyu/dataset/imagenet2012")
+    add("--num_workers", type=int, default=8, help="decode threads (at most 16)")                   # post_train.py:417
     # Stage-2 Mixup / CutMix and smoothing (post_train.py:502,539-550): applied on the real-data path only
-    p.add_argument("--smoothing", type=float, default=0.1)
-    p.add_argument("--mixup", type=float, default=0.8); p.add_argument("--cutmix", type=float, default=1.0)
-    p.add_argument("--cutmix-minmax", type=float, nargs="+", default=None); p.add_argument("--mixup-prob", type=float, default=0.8)
-    p.add_argument("--mixup-switch-prob", type=float, default=0.5); p.add_argument("--mixup-mode", type=str, default="batch")
+    add("--smoothing", type=float, default=0.1)
+    add("--mixup", type=float, default=0.8); add("--cutmix", type=float, default=1.0)
+    add("--cutmix-minmax", type=float, nargs="+", default=None); add("--mixup-prob", type=float, default=0.8)
+    add("--mixup-switch-prob", type=float, default=0.5); add("--mixup-mode", type=str, default="batch")
     # pretrained weights (post_train.py:422,554-556,635-640); the reference's --model_path default is a URL, and nothing is downloaded here
-    p.add_argument("--model_path", type=str, default=None, help="pretrained checkpoint: the teacher's default source, and the model of --eval_only without --checkpoint_dir")
-    p.add_argument("--teacher-model", type=str, default="", help="teacher architecture (default: --model_type)")
-    p.add_argument("--teacher-path", type=str, default="", help="teacher checkpoint (default: --model_path)")
-    p.add_argument("--teacher_cfg", type=str, default=None, help="with --teacher-model custom / custom_t2t: the teacher's JSON dims")
-    p.add_argument("--eval_only", type=int, default=0, help="1: evaluate the model once (valid()) and print the JSON line, no training")
+    add("--model_path", type=str, default=None, help="pretrained checkpoint: the teacher's default source, and the model of --eval_only without --checkpoint_dir")
+    add("--teacher-model", type=str, default="", help="teacher architecture (default: --model_type)")
+    add("--teacher-path", type=str, default="", help="teacher checkpoint (default: --model_path)")
+    add("--teacher_cfg", type=str, default=None, help="with --teacher-model custom / custom_t2t: the teacher's JSON dims")
+    add("--eval_only", type=int, default=0, help="1: evaluate the model once (valid()) and print the JSON line, no training")
+    return p
+
+
+def main(argv=None):
+    """Stage-2 run: loads a Stage-1 checkpoint and fine-tunes it on synthetic batches (``--synthetic 1``, the default) or on
+    ``--dataset`` under ``--data_dir`` (``--synthetic 0``: uvc_amd/data.py, with the reference's Mixup / CutMix, post_train.py:614-621)."""
+    p = add_stage2_flags(argparse.ArgumentParser(description="UVC Stage-2 masked fine-tune on MI355X"))
     args = p.parse_args(argv)
     if args.model_cfg:
         args.model_cfg = json.loads(args.model_cfg)
