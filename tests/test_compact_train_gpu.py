@@ -433,6 +433,23 @@ def test_compact_trainer_resumes_bit_for_bit_and_evaluates_like_the_inference_mo
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_training_and_eval_forward_return_the_same_bits(precision):
+    """One forward body serves both modes: the training forward (a buffer set per block, GELU' kept beside fc1's output) and the eval
+    forward (one shared buffer set) launch the same kernels on the same operands, so the two heads' logits are equal bit for bit."""
+    r, cfg, ex, teacher = fixture_export("stage2_micro_deit")
+    S = ex["cfg"]["img_size"]
+    x = torch.randn(4, 3, S, S, device="cuda", generator=torch.Generator(device="cuda").manual_seed(11))
+    m = CT.CompactTrainableViT(ex, precision=precision)
+    (o, od), _ = m(x)                                   # uvc_vit_compact_train_forward
+    with torch.no_grad():
+        (eo, eod), _ = m(x)                             # training mode without autograd: uvc_vit_compact_forward, heads kept apart
+        m.eval()
+        avg, _ = m(x)
+    assert o.requires_grad and not eo.requires_grad
+    assert torch.equal(o, eo) and torch.equal(od, eod) and torch.equal((o + od) / 2, avg)
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
 def test_twenty_steps_on_one_batch_lower_the_loss(precision):
     r, cfg, ex, teacher = fixture_export("stage2_micro_none")
     args = trainer_args(r, ex, precision, train_batch_size=16, learning_rate=1e-3 * 512 / 16, distillation_type="none", warmup_epochs=0)

@@ -308,109 +308,122 @@ def apply_synthetic_masks(model, masks):
 
 
 # ---- the MI355X module ----------------------------------------------------------------------------------------------------------
-_BOUND = False
+_SLOTS = ["norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias", "norm2.weight",
+          "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias"]      # uvc_vit_offsets.blk[k][0..11]
 
 
 def _bind():
-    global _BOUND
+    """The library with the argument types of the ten compact entry points (include/uvc_vit.h, uvc_vit_compact_*) set."""
     from . import _lib as L
     from .model_distilled import uvc_vit_cfg, uvc_vit_io, uvc_vit_offsets, uvc_vit_shadow_offsets
     lib = L.lib()
-    if not _BOUND:
-        B = C.POINTER(L.uvc_compact_block)
-        lib.uvc_vit_compact_layout.argtypes = [C.POINTER(uvc_vit_cfg), B, C.c_int32, C.POINTER(uvc_vit_offsets), C.POINTER(uvc_vit_shadow_offsets)]
-        lib.uvc_vit_compact_workspace_bytes.argtypes = [C.POINTER(uvc_vit_cfg), B, C.c_int32, C.c_int32]
-        lib.uvc_vit_compact_workspace_bytes.restype = C.c_int64
-        lib.uvc_vit_compact_update_shadows.argtypes = [C.POINTER(uvc_vit_cfg), B, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.uvc_vit_compact_forward.argtypes = [C.POINTER(uvc_vit_cfg), B, C.c_int32, C.POINTER(uvc_vit_io), C.c_void_p]
-        for n in ("uvc_vit_compact_layout", "uvc_vit_compact_update_shadows", "uvc_vit_compact_forward"):
-            getattr(lib, n).restype = C.c_int
-        _BOUND = True
+    if not getattr(lib, "_compact_bound", False):
+        head = [C.POINTER(uvc_vit_cfg), C.POINTER(L.uvc_compact_block), C.c_int32]
+        run = [C.POINTER(uvc_vit_io), C.c_void_p]
+        tails = {"layout": [C.POINTER(uvc_vit_offsets), C.POINTER(uvc_vit_shadow_offsets)], "workspace_bytes": [C.c_int32],
+                 "update_shadows": [C.c_void_p, C.c_void_p, C.c_void_p], "forward": run, "train_forward": run, "backward": run,
+                 "frozen_ranges": [C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]}
+        for n in ("layout", "workspace_bytes", "update_shadows"):
+            tails["train_" + n] = tails[n]
+        for n, tail in tails.items():
+            f = getattr(lib, "uvc_vit_compact_" + n)
+            f.argtypes, f.restype = head + tail, C.c_int64 if n.endswith("workspace_bytes") else C.c_int
+        lib._compact_bound = True
     return lib
 
 
-class CompactVisionTransformer(nn.Module):
-    """Inference-only compact DeiT over ONE flat float32 parameter buffer (uvc_vit_compact_layout).  ``forward(x)`` returns the eval
-    logits (``(x + x_dist) / 2`` with the distillation token) and the compact model's MACs, as the dense model's eval forward does."""
+class _CompactModule(nn.Module):
+    """What the inference module and the trainable one share: the refusals, the C descriptors (``_cfg``, ``_blocks``), ONE flat
+    float32 parameter buffer in the layout ``layout`` names (uvc_vit_compact_layout, or the training layout, which appends to it),
+    the per-batch workspaces and the eval forward through ``uvc_vit_compact_forward``.  A subclass allocates ``_shadow``."""
 
-    def __init__(self, export: dict, precision: str = "bf16", device=None):
+    def __init__(self, export: dict, precision: str, device, layout: str, max_tokens=None):
         super().__init__()
         from . import _lib as L
         from . import ops
         from .model_distilled import uvc_vit_cfg, uvc_vit_offsets, uvc_vit_shadow_offsets
         check_export(export)
         if precision == "bf16_f32resid":
-            raise NotImplementedError("compact models run in 'bf16' or 'fp32'")
+            raise NotImplementedError("compact models run in 'bf16' or 'fp32' (the float32 residual rows of 'bf16_f32resid' are a dense-model mode)")
         if precision not in ("bf16", "fp32"):
             raise ValueError("precision must be 'bf16' or 'fp32'")
         dev = torch.device(device if device is not None else "cuda")
         if dev.type != "cuda":
             raise L.UvcHipError("uvc_amd models run on MI355X only (no CPU fallback)")
-        self.export, self.precision = export, precision
         c = export["cfg"]
+        if max_tokens is not None and _seq(c) > max_tokens:
+            raise NotImplementedError(f"fine-tuning a compact model with {_seq(c)} tokens: the attention backward at a value width takes at most "
+                                      f"{max_tokens} (384-px and patch-8 files can be evaluated, not trained)")
+        self._export, self.precision = export, precision
         self.num_tokens = 2 if c["enable_dist"] else 1
         self._cfg = uvc_vit_cfg(c["img_size"], c["patch_size"], c["in_chans"], c["num_classes"], c["embed_dim"], c["depth"], c["num_heads"],
                                 c["hidden"], self.num_tokens, ops.UVC_F32 if precision == "fp32" else ops.UVC_BF16)
         self._cfg.ln_eps = float(c["ln_eps"])
-        nb = len(export["blocks"])
-        self._blocks = (L.uvc_compact_block * max(1, nb))()
+        self._nb = len(export["blocks"])
+        self._blocks = (L.uvc_compact_block * max(1, self._nb))()
         for k, b in enumerate(export["blocks"]):
             self._blocks[k].heads, self._blocks[k].v_dim, self._blocks[k].hidden = len(b["heads"]), b["v_dim"], b["hidden"]
-        self._nb = nb
         self._off, self._soff = uvc_vit_offsets(), uvc_vit_shadow_offsets()
-        lib = _bind()
-        L.check(lib.uvc_vit_compact_layout(C.byref(self._cfg), self._blocks, nb, C.byref(self._off), C.byref(self._soff)), "uvc_vit_compact_layout")
+        L.check(self._lib_call(layout, C.byref(self._off), C.byref(self._soff)), layout)
         flat = torch.zeros(self._off.n_total, dtype=torch.float32)
         for name, t in export["state_dict"].items():
             o = self._offset(name)
             flat[o:o + t.numel()] = t.reshape(-1).float()
         self._flat = flat.to(dev)
-        self._shadow = torch.empty(max(1, self._soff.n_total) if precision == "bf16" else 1, dtype=torch.bfloat16, device=dev)
-        with torch.cuda.device(dev):
-            L.check(lib.uvc_vit_compact_update_shadows(C.byref(self._cfg), self._blocks, nb, L.ptr(self._flat), L.ptr(self._shadow), L.cur_stream()),
-                    "uvc_vit_compact_update_shadows")
         self._ws = {}
-        self.eval()
+
+    def _lib_call(self, entry, *args):
+        """``entry(cfg, blocks, nblocks, *args)`` of the library."""
+        return getattr(_bind(), entry)(C.byref(self._cfg), self._blocks, self._nb, *args)
 
     def _offset(self, name):
         o = self._off
         if name.startswith("blocks."):
             _, k, rest = name.split(".", 2)
-            slots = ["norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias", "norm2.weight",
-                     "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias"]
-            return o.blk[int(k)][slots.index(rest)]
+            return o.blk[int(k)][_SLOTS.index(rest)]
         return dict(cls_token=o.cls_token, dist_token=o.dist_token, pos_embed=o.pos_embed, patch_gating=o.patch_gating,
                     **{"patch_embed.proj.weight": o.patch_w, "patch_embed.proj.bias": o.patch_b, "norm.weight": o.norm_w, "norm.bias": o.norm_b,
                        "head.weight": o.head_w, "head.bias": o.head_b, "head_dist.weight": o.headd_w, "head_dist.bias": o.headd_b})[name]
 
     def num_params(self) -> int:
-        return sum(int(t.numel()) for k, t in self.export["state_dict"].items() if k != "patch_gating")
+        return sum(int(t.numel()) for k, t in self._export["state_dict"].items() if k != "patch_gating")
 
     def macs(self, B=1) -> int:
-        return compact_macs(self.export, B, padded=True)
+        return compact_macs(self._export, B, padded=True)
 
-    @torch.no_grad()
-    def forward(self, x):
+    def _refresh_shadows(self):
+        """Bring ``_shadow`` up to date with ``_flat`` before a run (the inference module's weights never change)."""
+
+    def _prep(self, x):
         from . import _lib as L
-        from . import ops
-        from .model_distilled import uvc_vit_io
         L.require_cuda(x)
         if x.dtype != torch.float32 or not x.is_contiguous():
             x = x.contiguous().float()
-        c, B = self.export["cfg"], x.shape[0]
+        c = self._export["cfg"]
         if tuple(x.shape[1:]) != (c["in_chans"], c["img_size"], c["img_size"]):
             raise AssertionError(f"Input image size ({x.shape[2]}*{x.shape[3]}) doesn't match model ({c['img_size']}*{c['img_size']}).")
-        lib = _bind()
-        dev = self._flat.device
-        stream = L.cur_stream()
-        if B not in self._ws:
-            n = lib.uvc_vit_compact_workspace_bytes(C.byref(self._cfg), self._blocks, self._nb, B)
+        return x
+
+    def _workspace(self, B, training):
+        """One workspace per mode, for the last batch size seen."""
+        key = (B, bool(training))
+        if key not in self._ws:
+            from . import _lib as L
+            entry = "uvc_vit_compact_train_workspace_bytes" if training else "uvc_vit_compact_workspace_bytes"
+            n = self._lib_call(entry, B)
             if n < 0:
-                L.check(-1, "uvc_vit_compact_workspace_bytes")
-            self._ws = {B: torch.empty(n, dtype=torch.uint8, device=dev)}
-        ws = self._ws[B]
-        logits = torch.empty(B, c["num_classes"], device=dev)
-        logits_dist = torch.empty(B, c["num_classes"], device=dev) if self.num_tokens == 2 else None
+                L.check(-1, entry)
+            self._ws = {k: v for k, v in self._ws.items() if k[1] != bool(training)}
+            self._ws[key] = torch.empty(n, dtype=torch.uint8, device=self._flat.device)
+        return self._ws[key]
+
+    def _io(self, x, B, training):
+        """(uvc_vit_io of a pass over the prepared batch ``x``, its patch mask or None)."""
+        from . import _lib as L
+        from . import ops
+        from .model_distilled import uvc_vit_io
+        c, dev = self._export["cfg"], self._flat.device
+        ws = self._workspace(B, training)
         mask = None
         if c["patch_gating"]:
             P = (c["img_size"] // c["patch_size"]) ** 2
@@ -419,10 +432,47 @@ class CompactVisionTransformer(nn.Module):
             ops.patch_gate_sigmoid(self._flat[o:o + P], mask, B, P, bool(c["patch_hard"]))
         io = uvc_vit_io()
         io.params, io.shadow, io.workspace, io.workspace_bytes = L.ptr(self._flat), L.ptr(self._shadow), L.ptr(ws), ws.numel()
-        io.x, io.logits, io.logits_dist, io.patch_mask, io.batch = L.ptr(x), L.ptr(logits), L.ptr(logits_dist), L.ptr(mask), B
-        L.check(lib.uvc_vit_compact_forward(C.byref(self._cfg), self._blocks, self._nb, C.byref(io), stream), "uvc_vit_compact_forward")
-        out = logits if logits_dist is None else (logits + logits_dist) / 2
-        return out, self.macs(B)
+        io.x, io.patch_mask, io.batch, io.training = L.ptr(x), L.ptr(mask), B, int(training)
+        return io, mask
+
+    def _forward(self, x, training=False):
+        """``(logits, logits_dist or None, what a backward needs of the pass)`` through the eval or the training forward."""
+        from . import _lib as L
+        x = self._prep(x)
+        B, dev = x.shape[0], self._flat.device
+        self._refresh_shadows()
+        io, mask = self._io(x, B, training)
+        nc = self._export["cfg"]["num_classes"]
+        logits = torch.empty(B, nc, device=dev)
+        logits_dist = torch.empty(B, nc, device=dev) if self.num_tokens == 2 else None
+        io.logits, io.logits_dist = L.ptr(logits), L.ptr(logits_dist)
+        entry = "uvc_vit_compact_train_forward" if training else "uvc_vit_compact_forward"
+        L.check(self._lib_call(entry, C.byref(io), L.cur_stream()), entry)
+        return logits, logits_dist, dict(x=x, B=B, mask=mask)
+
+    @torch.no_grad()
+    def _eval_logits(self, x):
+        """The eval logits: ``(x + x_dist) / 2`` with the distillation token."""
+        o, od, _ = self._forward(x)
+        return o if od is None else (o + od) / 2
+
+
+class CompactVisionTransformer(_CompactModule):
+    """Inference-only compact DeiT over ONE flat float32 parameter buffer (uvc_vit_compact_layout).  ``forward(x)`` returns the eval
+    logits (``(x + x_dist) / 2`` with the distillation token) and the compact model's MACs, as the dense model's eval forward does."""
+
+    def __init__(self, export: dict, precision: str = "bf16", device=None):
+        from . import _lib as L
+        super().__init__(export, precision, device, "uvc_vit_compact_layout")
+        self.export = export
+        dev = self._flat.device
+        self._shadow = torch.empty(max(1, self._soff.n_total) if precision == "bf16" else 1, dtype=torch.bfloat16, device=dev)
+        with torch.cuda.device(dev):
+            L.check(self._lib_call("uvc_vit_compact_update_shadows", L.ptr(self._flat), L.ptr(self._shadow), L.cur_stream()), "uvc_vit_compact_update_shadows")
+        self.eval()
+
+    def forward(self, x):
+        return self._eval_logits(x), self.macs(x.shape[0])
 
 
 # ---- command line -------------------------------------------------------------------------------------------------------------

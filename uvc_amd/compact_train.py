@@ -26,32 +26,7 @@ from . import _lib as L
 from . import compact as CP
 
 MAX_TOKENS = 256
-_SLOTS = ["norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias", "norm2.weight",
-          "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias"]
-
-
-def _bind():
-    from .model_distilled import uvc_vit_cfg, uvc_vit_io, uvc_vit_offsets, uvc_vit_shadow_offsets
-    lib = CP._bind()
-    if not getattr(lib, "_compact_train_bound", False):
-        B = C.POINTER(L.uvc_compact_block)
-        cfgp = C.POINTER(uvc_vit_cfg)
-        lib.uvc_vit_compact_train_layout.argtypes = [cfgp, B, C.c_int32, C.POINTER(uvc_vit_offsets), C.POINTER(uvc_vit_shadow_offsets)]
-        lib.uvc_vit_compact_train_workspace_bytes.argtypes = [cfgp, B, C.c_int32, C.c_int32]
-        lib.uvc_vit_compact_train_workspace_bytes.restype = C.c_int64
-        lib.uvc_vit_compact_train_update_shadows.argtypes = [cfgp, B, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.uvc_vit_compact_frozen_ranges.argtypes = [cfgp, B, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]
-        for n in ("uvc_vit_compact_train_forward", "uvc_vit_compact_backward"):
-            getattr(lib, n).argtypes = [cfgp, B, C.c_int32, C.POINTER(uvc_vit_io), C.c_void_p]
-        for n in ("uvc_vit_compact_train_layout", "uvc_vit_compact_train_update_shadows", "uvc_vit_compact_frozen_ranges",
-                  "uvc_vit_compact_train_forward", "uvc_vit_compact_backward"):
-            getattr(lib, n).restype = C.c_int
-        lib._compact_train_bound = True
-    return lib
-
-
-def seq_len(cfg) -> int:
-    return (cfg["img_size"] // cfg["patch_size"]) ** 2 + (2 if cfg["enable_dist"] else 1)
+_bind = CP._bind
 
 
 def unread_parameters(export: dict):
@@ -114,47 +89,14 @@ class _CompactFunction(torch.autograd.Function):
         return None, None, None
 
 
-class CompactTrainableViT(nn.Module):
+class CompactTrainableViT(CP._CompactModule):
     """``model(x)`` in train mode returns ``((logits, logits_dist), macs)`` (``logits_dist is logits`` without the distillation
     token), in eval mode what ``CompactVisionTransformer`` returns -- same kernels, same bits."""
 
     def __init__(self, export: dict, precision: str = "bf16", device=None):
-        super().__init__()
-        from . import ops
-        from .model_distilled import uvc_vit_cfg, uvc_vit_offsets, uvc_vit_shadow_offsets
-        CP.check_export(export)
-        if precision == "bf16_f32resid":
-            raise NotImplementedError("compact models train in 'bf16' or 'fp32' (the float32 residual rows of 'bf16_f32resid' are a dense-model mode)")
-        if precision not in ("bf16", "fp32"):
-            raise ValueError("precision must be 'bf16' or 'fp32'")
-        dev = torch.device(device if device is not None else "cuda")
-        if dev.type != "cuda":
-            raise L.UvcHipError("uvc_amd models run on MI355X only (no CPU fallback)")
-        c = export["cfg"]
-        if seq_len(c) > MAX_TOKENS:
-            raise NotImplementedError(f"fine-tuning a compact model with {seq_len(c)} tokens: the attention backward at a value width takes at most "
-                                      f"{MAX_TOKENS} (384-px and patch-8 files can be evaluated, not trained)")
-        self._export, self.precision = export, precision
-        self.num_tokens = 2 if c["enable_dist"] else 1
-        self._cfg = uvc_vit_cfg(c["img_size"], c["patch_size"], c["in_chans"], c["num_classes"], c["embed_dim"], c["depth"], c["num_heads"],
-                                c["hidden"], self.num_tokens, ops.UVC_F32 if precision == "fp32" else ops.UVC_BF16)
-        self._cfg.ln_eps = float(c["ln_eps"])
-        nb = len(export["blocks"])
-        self._blocks = (L.uvc_compact_block * max(1, nb))()
-        for k, b in enumerate(export["blocks"]):
-            self._blocks[k].heads, self._blocks[k].v_dim, self._blocks[k].hidden = len(b["heads"]), b["v_dim"], b["hidden"]
-        self._nb = nb
-        self._off, self._soff = uvc_vit_offsets(), uvc_vit_shadow_offsets()
-        lib = _bind()
-        L.check(lib.uvc_vit_compact_train_layout(C.byref(self._cfg), self._blocks, nb, C.byref(self._off), C.byref(self._soff)),
-                "uvc_vit_compact_train_layout")
-        n = self._off.n_total
-        flat = torch.zeros(n, dtype=torch.float32)
-        for name, t in export["state_dict"].items():
-            o = self._offset(name)
-            flat[o:o + t.numel()] = t.reshape(-1).float()
-        self._flat = flat.to(dev)
-        self._flat_grad = torch.zeros(n, dtype=torch.float32, device=dev)
+        super().__init__(export, precision, device, "uvc_vit_compact_train_layout", max_tokens=MAX_TOKENS)
+        dev, nb = self._flat.device, self._nb
+        self._flat_grad = torch.zeros(self._off.n_total, dtype=torch.float32, device=dev)
         tsz = 4 if precision == "fp32" else 2
         self._shadow = torch.zeros(max(1, self._soff.n_total) * tsz, dtype=torch.uint8, device=dev)
         self._shadow_fresh = False
@@ -168,11 +110,9 @@ class CompactTrainableViT(nn.Module):
             self.register_parameter(name.replace(".", "__"), p)
         cnt = C.c_int32()
         ranges = (C.c_int64 * (4 * max(1, nb)))()
-        L.check(lib.uvc_vit_compact_frozen_ranges(C.byref(self._cfg), self._blocks, nb, ranges, 2 * max(1, nb), C.byref(cnt)),
-                "uvc_vit_compact_frozen_ranges")
+        L.check(self._lib_call("uvc_vit_compact_frozen_ranges", ranges, 2 * max(1, nb), C.byref(cnt)), "uvc_vit_compact_frozen_ranges")
         self._frozen = [(int(ranges[2 * i]), int(ranges[2 * i + 1])) for i in range(cnt.value)]
         self._unread = set(unread_parameters(export))
-        self._ws = {}
         self._last = None
         self.grad_accumulate = False
         self.train()
@@ -229,15 +169,6 @@ class CompactTrainableViT(nn.Module):
                     self._by_name[n].copy_(sd[n].to(self._flat.device).reshape(self._by_name[n].shape))
         self.mark_weights_changed()
 
-    def _offset(self, name):
-        o = self._off
-        if name.startswith("blocks."):
-            _, k, rest = name.split(".", 2)
-            return o.blk[int(k)][_SLOTS.index(rest)]
-        return dict(cls_token=o.cls_token, dist_token=o.dist_token, pos_embed=o.pos_embed, patch_gating=o.patch_gating,
-                    **{"patch_embed.proj.weight": o.patch_w, "patch_embed.proj.bias": o.patch_b, "norm.weight": o.norm_w, "norm.bias": o.norm_b,
-                       "head.weight": o.head_w, "head.bias": o.head_b, "head_dist.weight": o.headd_w, "head_dist.bias": o.headd_b})[name]
-
     def grad_views(self):
         """Point ``.grad`` of every parameter a forward reads at its slice of the flat gradient buffer; the others keep None."""
         base = self._flat_grad.data_ptr()
@@ -251,78 +182,24 @@ class CompactTrainableViT(nn.Module):
                 p.grad = self._flat_grad[off:off + p.numel()].view(p.shape)
 
     # -- reference-style API ---------------------------------------------------------------------------------------------------------
-    def num_params(self) -> int:
-        return sum(int(self._by_name[n].numel()) for n in self._names if n != "patch_gating")
-
-    def macs(self, B=1) -> int:
-        return CP.compact_macs(self._export, B, padded=True)
-
     def export(self) -> dict:
         """A version-1 compact dict with the current weights and the source file's ``cfg`` / ``blocks``."""
         return with_state(self._export, self.state_dict())
 
     def _refresh_shadows(self):
         if not self._shadow_fresh:
-            L.check(_bind().uvc_vit_compact_train_update_shadows(C.byref(self._cfg), self._blocks, self._nb, L.ptr(self._flat), L.ptr(self._shadow),
-                                                                 L.cur_stream()), "uvc_vit_compact_train_update_shadows")
+            L.check(self._lib_call("uvc_vit_compact_train_update_shadows", L.ptr(self._flat), L.ptr(self._shadow), L.cur_stream()),
+                    "uvc_vit_compact_train_update_shadows")
             self._shadow_fresh = True
 
-    def _prep(self, x):
-        L.require_cuda(x)
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            x = x.contiguous().float()
-        c = self._export["cfg"]
-        if tuple(x.shape[1:]) != (c["in_chans"], c["img_size"], c["img_size"]):
-            raise AssertionError(f"Input image size ({x.shape[2]}*{x.shape[3]}) doesn't match model ({c['img_size']}*{c['img_size']}).")
-        return x
-
-    def _workspace(self, B, training):
-        key = (B, bool(training))
-        if key not in self._ws:
-            lib = _bind()
-            fn = lib.uvc_vit_compact_train_workspace_bytes if training else lib.uvc_vit_compact_workspace_bytes
-            n = fn(C.byref(self._cfg), self._blocks, self._nb, B)
-            if n < 0:
-                raise L.UvcHipError(f"compact workspace query failed: {L.lib().uvc_last_error().decode()}")
-            self._ws = {k: v for k, v in self._ws.items() if k[1] != bool(training)}
-            self._ws[key] = torch.empty(n, dtype=torch.uint8, device=self._flat.device)
-        return self._ws[key]
-
     def _io(self, x, B, training):
-        from . import ops
-        from .model_distilled import uvc_vit_io
-        c, dev = self._export["cfg"], self._flat.device
-        ws = self._workspace(B, training)
-        mask = None
-        if c["patch_gating"]:
-            P = (c["img_size"] // c["patch_size"]) ** 2
-            mask = torch.empty(B, P, device=dev)
-            o = self._off.patch_gating
-            ops.patch_gate_sigmoid(self._flat[o:o + P], mask, B, P, bool(c["patch_hard"]))
-        io = uvc_vit_io()
-        io.params, io.shadow, io.grads = L.ptr(self._flat), L.ptr(self._shadow), L.ptr(self._flat_grad)
-        io.workspace, io.workspace_bytes = L.ptr(ws), ws.numel()
-        io.x, io.patch_mask, io.batch, io.training = L.ptr(x), L.ptr(mask), B, int(training)
+        io, mask = super()._io(x, B, training)
+        io.grads = L.ptr(self._flat_grad)
         return io, mask
 
-    def _run(self, x, training):
-        x = self._prep(x)
-        B = x.shape[0]
-        self._refresh_shadows()
-        dev = self._flat.device
-        io, mask = self._io(x, B, training)
-        nc = self._export["cfg"]["num_classes"]
-        logits = torch.empty(B, nc, device=dev)
-        logits_dist = torch.empty(B, nc, device=dev) if self.num_tokens == 2 else None
-        io.logits, io.logits_dist = L.ptr(logits), L.ptr(logits_dist)
-        lib = _bind()
-        fn, what = (lib.uvc_vit_compact_train_forward, "uvc_vit_compact_train_forward") if training else (lib.uvc_vit_compact_forward, "uvc_vit_compact_forward")
-        L.check(fn(C.byref(self._cfg), self._blocks, self._nb, C.byref(io), L.cur_stream()), what)
-        self._last = dict(x=x, B=B, mask=mask) if training else self._last
-        return logits, logits_dist
-
     def _train_forward(self, x):
-        return self._run(x, True)
+        logits, logits_dist, self._last = self._forward(x, True)
+        return logits, logits_dist
 
     def _train_backward(self, d_logits, d_logits_dist):
         st = self._last
@@ -336,18 +213,18 @@ class CompactTrainableViT(nn.Module):
         if self.num_tokens == 2:
             d_logits_dist = d_logits_dist.contiguous()
             io.d_logits_dist = L.ptr(d_logits_dist)
-        L.check(_bind().uvc_vit_compact_backward(C.byref(self._cfg), self._blocks, self._nb, C.byref(io), L.cur_stream()), "uvc_vit_compact_backward")
+        L.check(self._lib_call("uvc_vit_compact_backward", C.byref(io), L.cur_stream()), "uvc_vit_compact_backward")
 
     def forward(self, x):
         macs = self.macs(x.shape[0])
         if self.training and torch.is_grad_enabled():
             out = _CompactFunction.apply(self, x, self._by_name["cls_token"])
             return (out if self.num_tokens == 2 else (out, out)), macs
+        if not self.training:
+            return self._eval_logits(x), macs
         with torch.no_grad():
-            o, od = self._run(x, False)
-        if self.training:
-            return (o, o if od is None else od), macs
-        return (o if od is None else (o + od) / 2), macs
+            o, od, _ = self._forward(x)
+        return (o, o if od is None else od), macs
 
 
 def _refuse(args, precision):
@@ -372,9 +249,6 @@ class CompactTrainer:
         _refuse(args, args.precision)
         self.args = args
         c = export["cfg"]
-        if seq_len(c) > MAX_TOKENS:
-            raise NotImplementedError(f"fine-tuning a compact model with {seq_len(c)} tokens: the attention backward at a value width takes at most "
-                                      f"{MAX_TOKENS} (384-px and patch-8 files can be evaluated, not trained)")
         self.model = CompactTrainableViT(export, precision=args.precision, device=device)
         teacher, self.teacher_source = None, None
         if args.distillation_type != "none":

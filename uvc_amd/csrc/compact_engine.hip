@@ -1,24 +1,26 @@
-// Compact-model sequencers (include/uvc_vit.h, uvc_vit_compact_*): the eval forward of a pruned DeiT exported at its kept widths
-// (uvc_amd/compact.py) -- per block LayerNorm1, qkv GEMM, attention with a value head dim of its own (uvc_attn_args.v_dim), proj GEMM
-// (+ bias + residual), LayerNorm2, fc1 (+ bias, GELU), fc2 (+ bias + residual).  Host code only; every arithmetic step is one of the
-// kernels behind uvc_kernels.h, the embedding, token assembly, final norm and heads as uvc_vit_forward runs them.
-// Second half of the file: the training forward and the backward of the same network (uvc_vit_compact_train_*, uvc_vit_compact_backward),
-// fine-tuning a compact model at its kept widths -- plain GEMMs, the attention backward at a value width, one stream.
-#include "common.h"
-#include "../../include/uvc_kernels.h"
-#include "../../include/uvc_vit.h"
-#include <string.h>
+// Compact-model sequencers (include/uvc_vit.h, uvc_vit_compact_*): a pruned DeiT exported at its kept widths (uvc_amd/compact.py) --
+// per block LayerNorm1, qkv GEMM, attention with a value head dim of its own (uvc_attn_args.v_dim), proj GEMM (+ bias + residual),
+// LayerNorm2, fc1 (+ bias, GELU), fc2 (+ bias + residual).  Host code only; every arithmetic step is one of the kernels behind
+// uvc_kernels.h, the embedding, token assembly, final norm and heads as uvc_vit_forward runs them.
+// ONE forward body serves evaluation (uvc_vit_compact_forward) and fine-tuning (uvc_vit_compact_train_forward): the same kernels in the
+// same order on one stream.  The modes differ in where a block's buffers live (carve: one shared set in eval, a set per block that
+// the backward reads in training) and in the fc1 epilogue (training also keeps GELU').  uvc_vit_compact_backward walks the blocks in
+// reverse: plain GEMMs and the attention backward at a value width.
+#include "engine_host.h"
 
 namespace {
 
-#define TRY(x) do { if (int e_ = (x)) return e_; } while (0)
-
-struct CDims {
-  int B, S, P, C, D, NC, ntok, np, N, M, K0, dtype, rlow;
+struct CDims : Dims {
   int maxQ, maxO, maxH, maxF;    // widest qkv row, attention output row, head count and hidden width over the blocks
-  float eps;
-  size_t tsz, rsz;
 };
+
+// rows of a block's qkv matrix (64 q and 64 k dims per kept head, v_dim value dims) and columns of its attention output
+int qkv_rows(const uvc_compact_block& b) { return b.heads * (128 + b.v_dim); }
+int attn_cols(const uvc_compact_block& b) { return b.heads * b.v_dim; }
+// the four matrices of a block as [out, in] -- qkv, proj, fc1, fc2: parameter slots 2, 4, 8, 10, shadow slots 0..3
+struct Mats { int64_t R[4], C[4]; };
+Mats mats_of(const uvc_compact_block& b, int D) { return {{qkv_rows(b), D, b.hidden, D}, {D, attn_cols(b), D, b.hidden}}; }
+constexpr int MAT_SLOT[4] = {2, 4, 8, 10};
 
 int check_blocks(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nblocks) {
   TRY(uvc_vit_layout(cfg, nullptr, nullptr));              // the dense model's checks (dims, dtype, ntok, classes, patches)
@@ -36,234 +38,17 @@ int check_blocks(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nb
 
 CDims cdims_of(const uvc_vit_cfg& c, const uvc_compact_block* blocks, int nblocks, int B) {
   CDims d;
-  d.B = B; d.S = c.img_size; d.P = c.patch_size; d.C = c.in_chans; d.D = c.embed_dim; d.NC = c.num_classes; d.ntok = c.ntok;
-  d.np = (c.img_size / c.patch_size) * (c.img_size / c.patch_size);
-  d.N = d.np + d.ntok; d.M = B * d.N; d.K0 = c.in_chans * c.patch_size * c.patch_size; d.dtype = c.dtype;
-  d.tsz = c.dtype == UVC_F32 ? 4 : 2;
-  d.rlow = (c.dtype == UVC_BF16 && !c.resid_f32) ? 1 : 0;
-  d.rsz = d.rlow ? 2 : 4;
-  d.eps = c.ln_eps > 0.f ? c.ln_eps : 1e-6f;
+  static_cast<Dims&>(d) = dims_of(c, B);
   d.maxQ = d.maxO = d.maxH = d.maxF = 0;
   for (int k = 0; k < nblocks; ++k) {
     const uvc_compact_block& b = blocks[k];
-    if (b.heads * (128 + b.v_dim) > d.maxQ) d.maxQ = b.heads * (128 + b.v_dim);
-    if (b.heads * b.v_dim > d.maxO) d.maxO = b.heads * b.v_dim;
+    if (qkv_rows(b) > d.maxQ) d.maxQ = qkv_rows(b);
+    if (attn_cols(b) > d.maxO) d.maxO = attn_cols(b);
     if (b.heads > d.maxH) d.maxH = b.heads;
     if (b.hidden > d.maxF) d.maxF = b.hidden;
   }
   return d;
 }
-
-struct Carver {
-  char* base; int64_t off;
-  void* take(int64_t bytes) { void* p = base ? base + off : nullptr; off += (bytes + 255) & ~(int64_t)255; return p; }
-};
-
-struct CWork {
-  void* patches; float* pe; void* r[3];      // r: residual-stream rows [M, D]; a block's input, x1 and output take whichever are free
-  void* h; void* qkv; void* o; float* lse; void* u; float* mean; float* rstd; float* ones;
-  void* hc; float* meanf; float* rstdf;
-};
-
-int64_t carve(const CDims& d, char* base, CWork& w) {
-  Carver c{base, 0};
-  const int64_t M = d.M;
-  w.patches = c.take((int64_t)d.B * d.np * d.K0 * d.tsz);
-  w.pe = (float*)c.take((int64_t)d.B * d.np * d.D * 4);
-  for (int i = 0; i < 3; ++i) w.r[i] = c.take(M * d.D * d.rsz);
-  w.h = c.take(M * d.D * d.tsz);
-  w.qkv = c.take(M * d.maxQ * d.tsz);
-  w.o = c.take(M * d.maxO * d.tsz);
-  w.lse = (float*)c.take((int64_t)d.B * d.maxH * d.N * 4);
-  w.u = c.take(M * d.maxF * d.tsz);
-  w.mean = (float*)c.take(M * 4); w.rstd = (float*)c.take(M * 4);
-  w.ones = (float*)c.take(M * 4);
-  w.hc = c.take((int64_t)d.B * d.ntok * d.D * d.tsz);
-  w.meanf = (float*)c.take((int64_t)d.B * d.ntok * 4); w.rstdf = (float*)c.take((int64_t)d.B * d.ntok * 4);
-  return c.off;
-}
-
-struct CCtx { CDims d; const uvc_vit_io* io; void* st; };
-
-// C[M,N] = epi(A[M,K] . B[N,K]^T); bf16 mode reads the shadow's [out, in] copy, float32 mode the master weights
-int nt(const CCtx& c, const void* A, const void* B, void* C, int c_f32, int M, int N, int K, int epi, const float* bias, const void* R = nullptr,
-       int lda = 0) {
-  uvc_gemm_nt_args a;
-  memset(&a, 0, sizeof(a));
-  a.A = A; a.B = B; a.C = C; a.bias = bias; a.R = R;
-  a.alpha = 1.0f; a.M = M; a.N = N; a.K = K; a.lda = lda ? lda : K; a.ldb = K; a.ldc = N; a.ldr = N; a.ldaux = N;
-  a.dtype = c.d.dtype; a.a_is_f32 = c.d.dtype == UVC_F32; a.c_is_f32 = c_f32 || c.d.dtype == UVC_F32; a.epilogue = epi;
-  a.r_is_f32 = a.c_is_f32;
-  return uvc_gemm_nt(&a, c.st);
-}
-int ln_fwd(const CCtx& c, const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int rows, int rpg, int64_t gs) {
-  uvc_ln_args a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.x_lowp = c.d.rlow; a.gamma = gamma; a.beta = beta; a.y = y; a.mean = mean; a.rstd = rstd; a.eps = c.d.eps;
-  a.rows = rows; a.D = c.d.D; a.rows_per_group = rpg; a.group_stride = gs; a.dtype = c.d.dtype;
-  return uvc_layernorm_fwd(&a, c.st);
-}
-
-}  // namespace
-
-extern "C" int uvc_vit_compact_layout(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, uvc_vit_offsets* off,
-                                      uvc_vit_shadow_offsets* soff) {
-  TRY(check_blocks(cfg, blocks, nblocks));
-  const CDims d = cdims_of(*cfg, blocks, nblocks, 1);
-  if (off) {
-    memset(off, 0xff, sizeof(*off));
-    int64_t o = 0;
-    auto put = [&](int64_t& slot, int64_t n) { slot = o; o += (n + 3) & ~(int64_t)3; };
-    put(off->cls_token, d.D);
-    if (d.ntok == 2) put(off->dist_token, d.D);
-    put(off->pos_embed, (int64_t)d.N * d.D);
-    put(off->patch_w, (int64_t)d.D * d.K0); put(off->patch_b, d.D);
-    for (int k = 0; k < nblocks; ++k) {
-      int64_t* b = off->blk[k];
-      const int64_t nq = (int64_t)blocks[k].heads * (128 + blocks[k].v_dim), no = (int64_t)blocks[k].heads * blocks[k].v_dim, F = blocks[k].hidden;
-      put(b[0], d.D); put(b[1], d.D); put(b[2], nq * d.D); put(b[3], nq); put(b[4], d.D * no); put(b[5], d.D);
-      put(b[6], d.D); put(b[7], d.D); put(b[8], F * d.D); put(b[9], F); put(b[10], d.D * F); put(b[11], d.D);
-    }
-    put(off->norm_w, d.D); put(off->norm_b, d.D);
-    put(off->head_w, (int64_t)d.NC * d.D); put(off->head_b, d.NC);
-    if (d.ntok == 2) { put(off->headd_w, (int64_t)d.NC * d.D); put(off->headd_b, d.NC); }
-    off->n_main = o;
-    put(off->patch_gating, d.np);
-    off->n_total = o;
-  }
-  if (soff) {
-    memset(soff, 0xff, sizeof(*soff));
-    int64_t o = 0;
-    auto put = [&](int64_t& slot, int64_t n) { slot = o; o += (n + 7) & ~(int64_t)7; };
-    put(soff->patch_w, (int64_t)d.D * d.K0);
-    for (int k = 0; k < nblocks; ++k) {
-      const int64_t nq = (int64_t)blocks[k].heads * (128 + blocks[k].v_dim), no = (int64_t)blocks[k].heads * blocks[k].v_dim, F = blocks[k].hidden;
-      put(soff->blk_w[k][0], nq * d.D); put(soff->blk_w[k][1], d.D * no); put(soff->blk_w[k][2], F * d.D); put(soff->blk_w[k][3], d.D * F);
-    }
-    put(soff->head_w, (int64_t)d.NC * d.D);
-    if (d.ntok == 2) put(soff->headd_w, (int64_t)d.NC * d.D);
-    soff->n_total = o;
-  }
-  return UVC_OK;
-}
-
-extern "C" int64_t uvc_vit_compact_workspace_bytes(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int32_t batch) {
-  if (check_blocks(cfg, blocks, nblocks) || batch <= 0) return -1;
-  CWork w;
-  return carve(cdims_of(*cfg, blocks, nblocks, batch), nullptr, w);
-}
-
-extern "C" int uvc_vit_compact_update_shadows(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const float* params, void* shadow,
-                                              void* stream) {
-  TRY(check_blocks(cfg, blocks, nblocks));
-  if (cfg->dtype == UVC_F32) return UVC_OK;                 // the GEMMs read the float32 master weights
-  if (!params || !shadow) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_update_shadows: null pointer");
-  const CDims d = cdims_of(*cfg, blocks, nblocks, 1);
-  uvc_vit_offsets off; uvc_vit_shadow_offsets so;
-  TRY(uvc_vit_compact_layout(cfg, blocks, nblocks, &off, &so));
-  int64_t srcs[64], ws[64], wts[64];
-  int32_t Rs[64], Cs[64];
-  int n = 0;
-  auto flush = [&]() -> int {
-    if (n == 0) return UVC_OK;
-    const int e = uvc_cast_transpose_multi(params, shadow, n, srcs, Rs, Cs, ws, wts, d.dtype, stream);
-    n = 0;
-    return e;
-  };
-  auto one = [&](int64_t p, int R, int C, int64_t sw) -> int {
-    if (R == 0 || C == 0) return UVC_OK;                   // (a block without heads / units has no such matrix)
-    srcs[n] = p; Rs[n] = R; Cs[n] = C; ws[n] = sw; wts[n] = -1; ++n;
-    return n == 64 ? flush() : UVC_OK;
-  };
-  TRY(one(off.patch_w, d.D, d.K0, so.patch_w));
-  for (int k = 0; k < nblocks; ++k) {
-    const int nq = blocks[k].heads * (128 + blocks[k].v_dim), no = blocks[k].heads * blocks[k].v_dim, F = blocks[k].hidden;
-    TRY(one(off.blk[k][2], nq, d.D, so.blk_w[k][0])); TRY(one(off.blk[k][4], d.D, no, so.blk_w[k][1]));
-    TRY(one(off.blk[k][8], F, d.D, so.blk_w[k][2])); TRY(one(off.blk[k][10], d.D, F, so.blk_w[k][3]));
-  }
-  TRY(one(off.head_w, d.NC, d.D, so.head_w));
-  if (d.ntok == 2) TRY(one(off.headd_w, d.NC, d.D, so.headd_w));
-  return flush();
-}
-
-extern "C" int uvc_vit_compact_forward(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* stream) {
-  TRY(check_blocks(cfg, blocks, nblocks));
-  if (!io || !io->params || !io->workspace || io->batch <= 0 || !io->x || !io->logits || (cfg->ntok == 2 && !io->logits_dist))
-    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_forward: null io member");
-  if (cfg->dtype == UVC_BF16 && !io->shadow) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_forward: bf16 mode needs the shadow buffer");
-  CCtx c;
-  c.d = cdims_of(*cfg, blocks, nblocks, io->batch); c.io = io; c.st = stream;
-  const CDims& d = c.d;
-  CWork w;
-  if (io->workspace_bytes < carve(d, nullptr, w)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_forward: workspace too small");
-  carve(d, (char*)io->workspace, w);
-  if (io->patches_in) w.patches = const_cast<void*>(io->patches_in);
-  uvc_vit_offsets o; uvc_vit_shadow_offsets so;
-  TRY(uvc_vit_compact_layout(cfg, blocks, nblocks, &o, &so));
-  const float* P = io->params;
-  auto wm = [&](int64_t poff, int64_t soff) -> const void* { return d.dtype == UVC_F32 ? (const void*)(P + poff) : (const void*)((const char*)io->shadow + soff * d.tsz); };
-  const int rf = d.rlow ? 0 : 1;                           // "C is float32" of the GEMMs that write residual-stream rows
-  // patch embedding (PatchEmbed.forward :145-153) and token assembly with the mode-1 token mask (:434-471)
-  if (!io->patches_in) TRY(uvc_patchify(io->x, w.patches, d.B, d.C, d.S, d.P, d.dtype, stream));
-  TRY(nt(c, w.patches, wm(o.patch_w, so.patch_w), w.pe, 1, d.B * d.np, d.D, d.K0, UVC_EPI_BIAS, P + o.patch_b));
-  void* xin = w.r[0];
-  TRY(uvc_assemble_tokens(w.pe, P + o.cls_token, d.ntok == 2 ? P + o.dist_token : nullptr, P + o.pos_embed, io->patch_mask, xin, d.B, d.np,
-                          d.D, d.ntok, d.rlow, stream));
-  bool ones_ready = false;
-  // a bias-only branch (no kept head / unit): rows += 1 * bias, in place -- the GEMM epilogue's acc + bias + R with acc = 0
-  auto add_bias = [&](void* x, const float* bias) -> int {
-    if (!ones_ready) {
-      const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)w.ones, 0x3f800000, (size_t)d.M, (hipStream_t)stream);
-      if (e != hipSuccess) return uvc_set_error(e, __FILE__, __LINE__);
-      ones_ready = true;
-    }
-    return uvc_add_outer(x, w.ones, bias, d.M, d.D, d.dtype, rf, stream);
-  };
-  auto free_buf = [&](const void* a, const void* b) -> void* {
-    for (int i = 0; i < 3; ++i) if (w.r[i] != a && w.r[i] != b) return w.r[i];
-    return nullptr;
-  };
-  for (int k = 0; k < nblocks; ++k) {
-    const uvc_compact_block& bk = blocks[k];
-    const int64_t* q = o.blk[k];
-    const int nq = bk.heads * (128 + bk.v_dim), no = bk.heads * bk.v_dim;
-    void* x1 = xin;
-    if (bk.heads > 0) {
-      TRY(ln_fwd(c, xin, P + q[0], P + q[1], w.h, w.mean, w.rstd, d.M, 1, d.D));
-      TRY(nt(c, w.h, wm(q[2], so.blk_w[k][0]), w.qkv, 0, d.M, nq, d.D, UVC_EPI_BIAS, P + q[3]));
-      uvc_attn_args a;
-      memset(&a, 0, sizeof(a));
-      a.qkv = w.qkv; a.o = w.o; a.lse = w.lse; a.B = d.B; a.N = d.N; a.H = bk.heads; a.head_dim = 64; a.dtype = d.dtype; a.scale = 0.125f;
-      a.v_dim = bk.v_dim;
-      TRY(uvc_attention_fwd(&a, stream));
-      x1 = free_buf(xin, nullptr);
-      TRY(nt(c, w.o, wm(q[4], so.blk_w[k][1]), x1, rf, d.M, d.D, no, UVC_EPI_BIAS_RESID, P + q[5], xin));
-    } else {
-      TRY(add_bias(x1, P + q[5]));
-    }
-    void* xout = x1;
-    if (bk.hidden > 0) {
-      TRY(ln_fwd(c, x1, P + q[6], P + q[7], w.h, w.mean, w.rstd, d.M, 1, d.D));
-      TRY(nt(c, w.h, wm(q[8], so.blk_w[k][2]), w.u, 0, d.M, bk.hidden, d.D, UVC_EPI_BIAS_GELU_OUT, P + q[9]));
-      xout = free_buf(x1, nullptr);
-      TRY(nt(c, w.u, wm(q[10], so.blk_w[k][3]), xout, rf, d.M, d.D, bk.hidden, UVC_EPI_BIAS_RESID, P + q[11], x1));
-    } else {
-      TRY(add_bias(xout, P + q[11]));
-    }
-    xin = xout;
-  }
-  // final norm on the class (/ distillation) token rows (:507-508), then the head(s) (:522-526)
-  TRY(ln_fwd(c, xin, P + o.norm_w, P + o.norm_b, w.hc, w.meanf, w.rstdf, d.B * d.ntok, d.ntok, (int64_t)d.N * d.D));
-  TRY(nt(c, w.hc, wm(o.head_w, so.head_w), io->logits, 1, d.B, d.NC, d.D, UVC_EPI_BIAS, P + o.head_b, nullptr, d.ntok * d.D));
-  if (d.ntok == 2)
-    TRY(nt(c, (const char*)w.hc + (size_t)d.D * d.tsz, wm(o.headd_w, so.headd_w), io->logits_dist, 1, d.B, d.NC, d.D, UVC_EPI_BIAS, P + o.headd_b,
-           nullptr, d.ntok * d.D));
-  return UVC_OK;
-}
-
-// =================================================================================================================================
-// Training: forward that keeps what the backward reads, and the backward, in reverse order of the forward above.
-namespace {
 
 constexpr int TRAIN_MAX_N = 256;     // the attention backward at a value width (uvc_attention_bwd_vdim) takes N <= 256
 
@@ -275,12 +60,16 @@ int check_train(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nbl
   return UVC_OK;
 }
 
-struct TBlock {      // what block k leaves for its backward; x1 / xo only where the branch has a GEMM (a bias-only branch adds in place)
+// ---- workspace -------------------------------------------------------------------------------------------------------------------
+// Block k's buffers.  Training: its own, kept for the backward; x1 / xo (residual-stream rows [M, D]) only where the branch has a GEMM
+// (a bias-only branch adds in place).  Eval: every block points at one shared set sized by the widest block (h1 = h2, one mean / rstd
+// pair, no gp), and x1 / xo alternate between two residual-row buffers.
+struct BlockBufs {
   void* h1; void* qkv; void* o; float* lse; float* mean1; float* rstd1; void* x1;
   void* h2; float* mean2; float* rstd2; void* gp; void* u; void* xo;
 };
-struct TWork {
-  void* patches; float* pe; void* x0; TBlock blk[UVC_VIT_MAX_DEPTH];
+struct Work {
+  void* patches; float* pe; void* x0; BlockBufs blk[UVC_VIT_MAX_DEPTH];
   void* hc; float* meanf; float* rstdf; float* ones;
   // backward: the dL/dx stream ping-pongs between g[0] and g[1] (T: bf16, or float32 in the exact mode)
   void* g[2]; void* dA; void* dH; void* dO; void* dqkv; float* delta; float* ln_partial; int64_t ln_region; float* cs_partial;
@@ -292,22 +81,39 @@ int64_t train_tn_ws(const CDims& d, const uvc_compact_block* blocks, int nblocks
   auto one = [&](int M, int N1, int N2) { if (N1 > 0 && N2 > 0) { uvc_gemm_tn_workspace_bytes(M, N1, N2, &b, &s); if (b > best) best = b; } };
   one(d.B, d.NC, d.D); one(d.B * d.np, d.D, d.K0);
   for (int k = 0; k < nblocks; ++k) {
-    const int nq = blocks[k].heads * (128 + blocks[k].v_dim), no = blocks[k].heads * blocks[k].v_dim, F = blocks[k].hidden;
+    const int nq = qkv_rows(blocks[k]), no = attn_cols(blocks[k]), F = blocks[k].hidden;
     one(d.M, d.D, F); one(d.M, F, d.D); one(d.M, d.D, no); one(d.M, nq, d.D);
   }
   return best;
 }
 
-int64_t carve_train(const CDims& d, const uvc_compact_block* blocks, int nblocks, char* base, TWork& w) {
+int64_t carve(const CDims& d, const uvc_compact_block* blocks, int nblocks, int training, char* base, Work& w) {
   Carver c{base, 0};
   const int64_t M = d.M, MD = M * d.D;
+  memset(&w, 0, sizeof(w));
   w.patches = c.take((int64_t)d.B * d.np * d.K0 * d.tsz);
   w.pe = (float*)c.take((int64_t)d.B * d.np * d.D * 4);
   w.x0 = c.take(MD * d.rsz);
+  BlockBufs shared = {};
+  void* r[2] = {w.x0, nullptr};
+  int cur = 0;
+  if (!training) {
+    r[1] = c.take(MD * d.rsz);
+    shared.h1 = shared.h2 = c.take(MD * d.tsz);
+    shared.qkv = c.take(M * d.maxQ * d.tsz); shared.o = c.take(M * d.maxO * d.tsz);
+    shared.lse = (float*)c.take((int64_t)d.B * d.maxH * d.N * 4);
+    shared.u = c.take(M * d.maxF * d.tsz);
+    shared.mean1 = shared.mean2 = (float*)c.take(M * 4); shared.rstd1 = shared.rstd2 = (float*)c.take(M * 4);
+  }
   for (int k = 0; k < nblocks; ++k) {
-    TBlock& b = w.blk[k];
-    memset(&b, 0, sizeof(b));
-    const int64_t nq = blocks[k].heads * (128 + blocks[k].v_dim), no = blocks[k].heads * blocks[k].v_dim, F = blocks[k].hidden;
+    BlockBufs& b = w.blk[k];
+    const int64_t nq = qkv_rows(blocks[k]), no = attn_cols(blocks[k]), F = blocks[k].hidden;
+    if (!training) {      // the rows a GEMM writes go to the buffer its residual operand is not in
+      b = shared;
+      if (blocks[k].heads > 0) b.x1 = r[cur ^= 1];
+      if (F > 0) b.xo = r[cur ^= 1];
+      continue;
+    }
     if (blocks[k].heads > 0) {
       b.h1 = c.take(MD * d.tsz); b.qkv = c.take(M * nq * d.tsz); b.o = c.take(M * no * d.tsz);
       b.lse = (float*)c.take((int64_t)d.B * blocks[k].heads * d.N * 4);
@@ -323,6 +129,7 @@ int64_t carve_train(const CDims& d, const uvc_compact_block* blocks, int nblocks
   w.hc = c.take((int64_t)d.B * d.ntok * d.D * d.tsz);
   w.meanf = (float*)c.take((int64_t)d.B * d.ntok * 4); w.rstdf = (float*)c.take((int64_t)d.B * d.ntok * 4);
   w.ones = (float*)c.take(M * 4);
+  if (!training) return c.off;
   w.g[0] = c.take(MD * d.tsz); w.g[1] = c.take(MD * d.tsz);
   w.dA = c.take(M * (d.maxF > 0 ? d.maxF : 1) * d.tsz);
   w.dH = c.take(MD * d.tsz);
@@ -341,7 +148,7 @@ int64_t carve_train(const CDims& d, const uvc_compact_block* blocks, int nblocks
 
 // the residual-stream rows of block k: its input, the rows behind the attention branch, its output (aliases where a branch is a bias)
 struct Chain { void* xin[UVC_VIT_MAX_DEPTH + 1]; void* x1[UVC_VIT_MAX_DEPTH]; };
-Chain chain_of(const TWork& w, const uvc_compact_block* blocks, int nblocks) {
+Chain chain_of(const Work& w, const uvc_compact_block* blocks, int nblocks) {
   Chain ch;
   ch.xin[0] = w.x0;
   for (int k = 0; k < nblocks; ++k) {
@@ -351,10 +158,20 @@ Chain chain_of(const TWork& w, const uvc_compact_block* blocks, int nblocks) {
   return ch;
 }
 
-struct TCtx { CDims d; const uvc_vit_io* io; void* st; TWork w; uvc_ln_reduce_item ln_items[64]; int n_ln; };
+// ---- small helpers around the kernel entry points ----------------------------------------------------------------------------------
+struct Ctx { CDims d; const uvc_vit_io* io; void* st; Work w; uvc_ln_reduce_item ln_items[64]; int n_ln; };
 
-int ntx(const TCtx& c, const void* A, int a_f32, const void* B, void* C, int c_f32, int M, int N, int K, int epi, const float* bias = nullptr,
-        const void* R = nullptr, const void* aux = nullptr, void* C2 = nullptr, int lda = 0, int ldc = 0) {
+// fills the context and carves io->workspace; false when the workspace is too small for the mode
+bool bind(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nblocks, const uvc_vit_io* io, void* stream, int training) {
+  c.d = cdims_of(*cfg, blocks, nblocks, io->batch); c.io = io; c.st = stream; c.n_ln = 0;
+  const int64_t need = carve(c.d, blocks, nblocks, training, (char*)io->workspace, c.w);
+  if (io->patches_in) c.w.patches = const_cast<void*>(io->patches_in);
+  return io->workspace_bytes >= need;
+}
+
+// C[M,N] = epi(A[M,K] . B[N,K]^T); B: a shadow copy (bf16 mode) or the float32 master weights
+int nt(const Ctx& c, const void* A, int a_f32, const void* B, void* C, int c_f32, int M, int N, int K, int epi, const float* bias = nullptr,
+       const void* R = nullptr, const void* aux = nullptr, void* C2 = nullptr, int lda = 0, int ldc = 0) {
   uvc_gemm_nt_args a;
   memset(&a, 0, sizeof(a));
   a.A = A; a.B = B; a.C = C; a.C2 = C2; a.bias = bias; a.R = R; a.aux = aux;
@@ -364,7 +181,7 @@ int ntx(const TCtx& c, const void* A, int a_f32, const void* B, void* C, int c_f
   return uvc_gemm_nt(&a, c.st);
 }
 // C[N1,N2] = A[M,N1]^T . B[M,N2] and bias_grad[N1] = column sums of A (the weight and bias gradient of a Linear, one pass)
-int tnx(const TCtx& c, const void* A, int a_f32, const void* B, float* C, float* bias_grad, int M, int N1, int N2, int lda = 0, int ldb = 0) {
+int tn(const Ctx& c, const void* A, int a_f32, const void* B, float* C, float* bias_grad, int M, int N1, int N2, int lda = 0, int ldb = 0) {
   uvc_gemm_tn_args a;
   memset(&a, 0, sizeof(a));
   a.A = A; a.B = B; a.C = C; a.colsum_out = bias_grad; a.workspace = c.w.tn_ws; a.workspace_bytes = c.w.tn_ws_bytes;
@@ -372,23 +189,23 @@ int tnx(const TCtx& c, const void* A, int a_f32, const void* B, float* C, float*
   a.dtype = c.d.dtype; a.a_is_f32 = a_f32 || c.d.dtype == UVC_F32;
   return uvc_gemm_tn(&a, c.st);
 }
-int ln_fwd_t(const TCtx& c, const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int rows, int rpg, int64_t gs) {
+int ln_fwd(const Ctx& c, const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int rows, int rpg, int64_t gs) {
   uvc_ln_args a;
   memset(&a, 0, sizeof(a));
   a.x = x; a.x_lowp = c.d.rlow; a.gamma = gamma; a.beta = beta; a.y = y; a.mean = mean; a.rstd = rstd; a.eps = c.d.eps;
   a.rows = rows; a.D = c.d.D; a.rows_per_group = rpg; a.group_stride = gs; a.dtype = c.d.dtype;
   return uvc_layernorm_fwd(&a, c.st);
 }
-int flush_ln_t(TCtx& c) {
+int flush_ln(Ctx& c) {
   if (c.n_ln == 0) return UVC_OK;
   const int e = uvc_layernorm_bwd_reduce_batch(c.ln_items, c.n_ln, c.d.D, 0.f, c.st);
   c.n_ln = 0;
   return e;
 }
 // dx = LN'(dy; x) + add1; dgamma / dbeta through the batched reduction at the end of the pass
-int ln_bwd_t(TCtx& c, int slot, const void* dy, const void* x, const float* gamma, float* dgamma, float* dbeta, const float* mean, const float* rstd,
-             void* dx, const void* add1, int rows, int rpg, int64_t gs) {
-  if (c.n_ln == 64) TRY(flush_ln_t(c));
+int ln_bwd(Ctx& c, int slot, const void* dy, const void* x, const float* gamma, float* dgamma, float* dbeta, const float* mean, const float* rstd,
+           void* dx, const void* add1, int rows, int rpg, int64_t gs) {
+  if (c.n_ln == 64) TRY(flush_ln(c));
   uvc_ln_args a;
   memset(&a, 0, sizeof(a));
   a.x = x; a.x_lowp = c.d.rlow; a.gamma = gamma; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd); a.dy = dy; a.dx = dx; a.add1 = add1;
@@ -399,25 +216,139 @@ int ln_bwd_t(TCtx& c, int slot, const void* dy, const void* x, const float* gamm
   a.g_lowp = c.d.dtype == UVC_BF16;
   return uvc_layernorm_bwd(&a, c.st);
 }
-int zero_f32(const TCtx& c, float* p, int64_t n) {
+int zero_f32(const Ctx& c, float* p, int64_t n) {
   if (n <= 0) return UVC_OK;
   const hipError_t e = hipMemsetAsync(p, 0, (size_t)n * 4, (hipStream_t)c.st);
   return e == hipSuccess ? UVC_OK : uvc_set_error(e, __FILE__, __LINE__);
 }
 
-int setup_train(TCtx& c, const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nblocks, const uvc_vit_io* io, void* stream) {
+int setup_train(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nblocks, const uvc_vit_io* io, void* stream) {
   TRY(check_train(cfg, blocks, nblocks));
   if (!io || !io->params || !io->shadow || !io->workspace || io->batch <= 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact training: null io member (params, shadow, workspace) or batch <= 0");
   if (io->accumulate != 0.f) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_vit_compact training: gradient accumulation (io.accumulate must be 0)");
-  c.d = cdims_of(*cfg, blocks, nblocks, io->batch); c.io = io; c.st = stream; c.n_ln = 0;
-  memset(&c.w, 0, sizeof(c.w));
-  if (io->workspace_bytes < carve_train(c.d, blocks, nblocks, nullptr, c.w)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact training: workspace too small (uvc_vit_compact_train_workspace_bytes)");
-  carve_train(c.d, blocks, nblocks, (char*)io->workspace, c.w);
-  if (io->patches_in) c.w.patches = const_cast<void*>(io->patches_in);
+  if (!bind(c, cfg, blocks, nblocks, io, stream, 1)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact training: workspace too small (uvc_vit_compact_train_workspace_bytes)");
+  return UVC_OK;
+}
+
+// the [out, in] shadow copies of every GEMM weight and, with `transposed` (training), the [in, out] copies behind them.  float32 mode: the
+// GEMMs read the master weights, so only the transposed copies are written
+int update_shadows(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nblocks, const float* params, void* shadow, void* stream, bool transposed) {
+  const CDims d = cdims_of(*cfg, blocks, nblocks, 1);
+  uvc_vit_offsets off; uvc_vit_shadow_offsets so;      // (the eval layout leaves every transposed slot at -1)
+  TRY((transposed ? uvc_vit_compact_train_layout : uvc_vit_compact_layout)(cfg, blocks, nblocks, &off, &so));
+  const bool f32 = d.dtype == UVC_F32;
+  ShadowBatch sb{params, shadow, d.dtype, stream};
+  auto one = [&](int64_t p, int64_t R, int64_t C, int64_t sw, int64_t swt) { return sb.add(p, R, C, f32 ? -1 : sw, swt); };
+  TRY(one(off.patch_w, d.D, d.K0, so.patch_w, -1));
+  for (int k = 0; k < nblocks; ++k) {
+    const Mats m = mats_of(blocks[k], d.D);
+    for (int j = 0; j < 4; ++j) TRY(one(off.blk[k][MAT_SLOT[j]], m.R[j], m.C[j], so.blk_w[k][j], so.blk_wt[k][j]));
+  }
+  TRY(one(off.head_w, d.NC, d.D, so.head_w, so.head_wt));
+  if (d.ntok == 2) TRY(one(off.headd_w, d.NC, d.D, so.headd_w, so.headd_wt));
+  return sb.flush();
+}
+
+// the forward of both modes; `training` keeps GELU' of fc1 beside its output (and c.w holds a buffer set per block)
+int forward(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nblocks, int training) {
+  const CDims& d = c.d;
+  const Work& w = c.w;
+  const uvc_vit_io* io = c.io;
+  void* stream = c.st;
+  uvc_vit_offsets o; uvc_vit_shadow_offsets so;
+  TRY(uvc_vit_compact_layout(cfg, blocks, nblocks, &o, &so));      // (the training layout appends to it: same [out, in] offsets)
+  const float* P = io->params;
+  auto wm = [&](int64_t poff, int64_t soff) -> const void* { return d.dtype == UVC_F32 ? (const void*)(P + poff) : (const void*)((const char*)io->shadow + soff * d.tsz); };
+  const int rf = d.rlow ? 0 : 1;                           // "C is float32" of the GEMMs that write residual-stream rows
+  // patch embedding (PatchEmbed.forward :145-153) and token assembly with the mode-1 token mask (:434-471)
+  if (!io->patches_in) TRY(uvc_patchify(io->x, w.patches, d.B, d.C, d.S, d.P, d.dtype, stream));
+  TRY(nt(c, w.patches, 0, wm(o.patch_w, so.patch_w), w.pe, 1, d.B * d.np, d.D, d.K0, UVC_EPI_BIAS, P + o.patch_b));
+  TRY(uvc_assemble_tokens(w.pe, P + o.cls_token, d.ntok == 2 ? P + o.dist_token : nullptr, P + o.pos_embed, io->patch_mask, w.x0, d.B, d.np,
+                          d.D, d.ntok, d.rlow, stream));
+  bool ones_ready = false;
+  // a bias-only branch (no kept head / unit): rows += 1 * bias, in place -- the GEMM epilogue's acc + bias + R with acc = 0
+  auto add_bias = [&](void* x, const float* bias) -> int {
+    if (!ones_ready) {
+      const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)w.ones, 0x3f800000, (size_t)d.M, (hipStream_t)stream);
+      if (e != hipSuccess) return uvc_set_error(e, __FILE__, __LINE__);
+      ones_ready = true;
+    }
+    return uvc_add_outer(x, w.ones, bias, d.M, d.D, d.dtype, rf, stream);
+  };
+  const Chain ch = chain_of(w, blocks, nblocks);
+  for (int k = 0; k < nblocks; ++k) {
+    const uvc_compact_block& bk = blocks[k];
+    const BlockBufs& b = w.blk[k];
+    const int64_t* q = o.blk[k];
+    void* xin = ch.xin[k];
+    void* x1 = ch.x1[k];
+    if (bk.heads > 0) {
+      TRY(ln_fwd(c, xin, P + q[0], P + q[1], b.h1, b.mean1, b.rstd1, d.M, 1, d.D));
+      TRY(nt(c, b.h1, 0, wm(q[2], so.blk_w[k][0]), b.qkv, 0, d.M, qkv_rows(bk), d.D, UVC_EPI_BIAS, P + q[3]));
+      uvc_attn_args a;
+      memset(&a, 0, sizeof(a));
+      a.qkv = b.qkv; a.o = b.o; a.lse = b.lse; a.B = d.B; a.N = d.N; a.H = bk.heads; a.head_dim = 64; a.dtype = d.dtype; a.scale = 0.125f;
+      a.v_dim = bk.v_dim;
+      TRY(uvc_attention_fwd(&a, stream));
+      TRY(nt(c, b.o, 0, wm(q[4], so.blk_w[k][1]), x1, rf, d.M, d.D, attn_cols(bk), UVC_EPI_BIAS_RESID, P + q[5], xin));
+    } else {
+      TRY(add_bias(x1, P + q[5]));
+    }
+    if (bk.hidden > 0) {
+      TRY(ln_fwd(c, x1, P + q[6], P + q[7], b.h2, b.mean2, b.rstd2, d.M, 1, d.D));
+      if (training)      // gp = GELU'(pre-activation), all the backward needs of it; u = GELU
+        TRY(nt(c, b.h2, 0, wm(q[8], so.blk_w[k][2]), b.gp, 0, d.M, bk.hidden, d.D, UVC_EPI_BIAS_GELU_GRAD, P + q[9], nullptr, nullptr, b.u));
+      else
+        TRY(nt(c, b.h2, 0, wm(q[8], so.blk_w[k][2]), b.u, 0, d.M, bk.hidden, d.D, UVC_EPI_BIAS_GELU_OUT, P + q[9]));
+      TRY(nt(c, b.u, 0, wm(q[10], so.blk_w[k][3]), b.xo, rf, d.M, d.D, bk.hidden, UVC_EPI_BIAS_RESID, P + q[11], x1));
+    } else {
+      TRY(add_bias(x1, P + q[11]));
+    }
+  }
+  // final norm on the class (/ distillation) token rows (:507-508), then the head(s) (:522-526)
+  TRY(ln_fwd(c, ch.xin[nblocks], P + o.norm_w, P + o.norm_b, w.hc, w.meanf, w.rstdf, d.B * d.ntok, d.ntok, (int64_t)d.N * d.D));
+  TRY(nt(c, w.hc, 0, wm(o.head_w, so.head_w), io->logits, 1, d.B, d.NC, d.D, UVC_EPI_BIAS, P + o.head_b, nullptr, nullptr, nullptr, d.ntok * d.D));
+  if (d.ntok == 2)
+    TRY(nt(c, (const char*)w.hc + (size_t)d.D * d.tsz, 0, wm(o.headd_w, so.headd_w), io->logits_dist, 1, d.B, d.NC, d.D, UVC_EPI_BIAS, P + o.headd_b,
+           nullptr, nullptr, nullptr, d.ntok * d.D));
   return UVC_OK;
 }
 
 }  // namespace
+
+// ---- layouts, workspace sizes, shadow refresh -----------------------------------------------------------------------------------------
+extern "C" int uvc_vit_compact_layout(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, uvc_vit_offsets* off,
+                                      uvc_vit_shadow_offsets* soff) {
+  TRY(check_blocks(cfg, blocks, nblocks));
+  const CDims d = cdims_of(*cfg, blocks, nblocks, 1);
+  if (off) {
+    memset(off, 0xff, sizeof(*off));
+    Slots put{0, 4};
+    layout_embed(d, off, put);
+    for (int k = 0; k < nblocks; ++k) {
+      const int64_t nq = qkv_rows(blocks[k]), no = attn_cols(blocks[k]), F = blocks[k].hidden;
+      int64_t* b = off->blk[k];
+      put(b[0], d.D); put(b[1], d.D); put(b[2], nq * d.D); put(b[3], nq); put(b[4], d.D * no); put(b[5], d.D);
+      put(b[6], d.D); put(b[7], d.D); put(b[8], F * d.D); put(b[9], F); put(b[10], d.D * F); put(b[11], d.D);
+    }
+    layout_heads(d, off, put);
+    put(off->patch_gating, d.np);
+    off->n_total = put.o;
+  }
+  if (soff) {
+    memset(soff, 0xff, sizeof(*soff));
+    Slots put{0, 8};
+    put(soff->patch_w, (int64_t)d.D * d.K0);
+    for (int k = 0; k < nblocks; ++k) {
+      const Mats m = mats_of(blocks[k], d.D);
+      for (int j = 0; j < 4; ++j) put(soff->blk_w[k][j], m.R[j] * m.C[j]);
+    }
+    put(soff->head_w, (int64_t)d.NC * d.D);
+    if (d.ntok == 2) put(soff->headd_w, (int64_t)d.NC * d.D);
+    soff->n_total = put.o;
+  }
+  return UVC_OK;
+}
 
 extern "C" int uvc_vit_compact_train_layout(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, uvc_vit_offsets* off,
                                             uvc_vit_shadow_offsets* soff) {
@@ -425,24 +356,29 @@ extern "C" int uvc_vit_compact_train_layout(const uvc_vit_cfg* cfg, const uvc_co
   TRY(uvc_vit_compact_layout(cfg, blocks, nblocks, off, soff));
   if (soff) {      // the [out, in] copies keep the eval layout's offsets; the transposed copies follow them
     const CDims d = cdims_of(*cfg, blocks, nblocks, 1);
-    int64_t o = soff->n_total;
-    auto put = [&](int64_t& slot, int64_t n) { slot = o; o += (n + 7) & ~(int64_t)7; };
+    Slots put{soff->n_total, 8};
     for (int k = 0; k < nblocks; ++k) {
-      const int64_t nq = (int64_t)blocks[k].heads * (128 + blocks[k].v_dim), no = (int64_t)blocks[k].heads * blocks[k].v_dim, F = blocks[k].hidden;
-      put(soff->blk_wt[k][0], nq * d.D); put(soff->blk_wt[k][1], d.D * no); put(soff->blk_wt[k][2], F * d.D); put(soff->blk_wt[k][3], d.D * F);
+      const Mats m = mats_of(blocks[k], d.D);
+      for (int j = 0; j < 4; ++j) put(soff->blk_wt[k][j], m.R[j] * m.C[j]);
     }
     put(soff->head_wt, (int64_t)d.NC * d.D);
     if (d.ntok == 2) put(soff->headd_wt, (int64_t)d.NC * d.D);
-    soff->n_total = o;
+    soff->n_total = put.o;
   }
   return UVC_OK;
+}
+
+extern "C" int64_t uvc_vit_compact_workspace_bytes(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int32_t batch) {
+  if (check_blocks(cfg, blocks, nblocks) || batch <= 0) return -1;
+  Work w;
+  return carve(cdims_of(*cfg, blocks, nblocks, batch), blocks, nblocks, 0, nullptr, w);
 }
 
 extern "C" int64_t uvc_vit_compact_train_workspace_bytes(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int32_t batch) {
   if (check_train(cfg, blocks, nblocks)) return -1;
   if (batch <= 0) { uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_train_workspace_bytes: batch <= 0"); return -1; }
-  TWork w;
-  return carve_train(cdims_of(*cfg, blocks, nblocks, batch), blocks, nblocks, nullptr, w);
+  Work w;
+  return carve(cdims_of(*cfg, blocks, nblocks, batch), blocks, nblocks, 1, nullptr, w);
 }
 
 extern "C" int uvc_vit_compact_frozen_ranges(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int64_t* ranges, int32_t cap,
@@ -461,107 +397,45 @@ extern "C" int uvc_vit_compact_frozen_ranges(const uvc_vit_cfg* cfg, const uvc_c
   return n > cap ? uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_frozen_ranges: more ranges than `cap` (count holds the number)") : UVC_OK;
 }
 
+extern "C" int uvc_vit_compact_update_shadows(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const float* params, void* shadow,
+                                              void* stream) {
+  TRY(check_blocks(cfg, blocks, nblocks));
+  if (cfg->dtype == UVC_F32) return UVC_OK;                 // the GEMMs read the float32 master weights
+  if (!params || !shadow) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_update_shadows: null pointer");
+  return update_shadows(cfg, blocks, nblocks, params, shadow, stream, false);
+}
+
 extern "C" int uvc_vit_compact_train_update_shadows(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const float* params,
                                                     void* shadow, void* stream) {
   TRY(check_train(cfg, blocks, nblocks));
   if (!params || !shadow) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_train_update_shadows: null pointer");
-  const CDims d = cdims_of(*cfg, blocks, nblocks, 1);
-  uvc_vit_offsets off; uvc_vit_shadow_offsets so;
-  TRY(uvc_vit_compact_train_layout(cfg, blocks, nblocks, &off, &so));
-  const bool f32 = d.dtype == UVC_F32;             // float32 mode: the GEMMs read the master weights; only the transposed copies are needed
-  int64_t srcs[64], ws[64], wts[64];
-  int32_t Rs[64], Cs[64];
-  int n = 0;
-  auto flush = [&]() -> int {
-    if (n == 0) return UVC_OK;
-    const int e = uvc_cast_transpose_multi(params, shadow, n, srcs, Rs, Cs, ws, wts, d.dtype, stream);
-    n = 0;
-    return e;
-  };
-  auto one = [&](int64_t p, int R, int C, int64_t sw, int64_t swt) -> int {
-    if (R == 0 || C == 0 || (f32 && swt < 0)) return UVC_OK;
-    srcs[n] = p; Rs[n] = R; Cs[n] = C; ws[n] = f32 ? -1 : sw; wts[n] = swt; ++n;
-    return n == 64 ? flush() : UVC_OK;
-  };
-  TRY(one(off.patch_w, d.D, d.K0, so.patch_w, -1));
-  for (int k = 0; k < nblocks; ++k) {
-    const int nq = blocks[k].heads * (128 + blocks[k].v_dim), no = blocks[k].heads * blocks[k].v_dim, F = blocks[k].hidden;
-    TRY(one(off.blk[k][2], nq, d.D, so.blk_w[k][0], so.blk_wt[k][0])); TRY(one(off.blk[k][4], d.D, no, so.blk_w[k][1], so.blk_wt[k][1]));
-    TRY(one(off.blk[k][8], F, d.D, so.blk_w[k][2], so.blk_wt[k][2])); TRY(one(off.blk[k][10], d.D, F, so.blk_w[k][3], so.blk_wt[k][3]));
-  }
-  TRY(one(off.head_w, d.NC, d.D, so.head_w, so.head_wt));
-  if (d.ntok == 2) TRY(one(off.headd_w, d.NC, d.D, so.headd_w, so.headd_wt));
-  return flush();
+  return update_shadows(cfg, blocks, nblocks, params, shadow, stream, true);
+}
+
+// ---- forward (eval, training) and backward -------------------------------------------------------------------------------------------
+extern "C" int uvc_vit_compact_forward(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* stream) {
+  TRY(check_blocks(cfg, blocks, nblocks));
+  if (!io || !io->params || !io->workspace || io->batch <= 0 || !io->x || !io->logits || (cfg->ntok == 2 && !io->logits_dist))
+    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_forward: null io member");
+  if (cfg->dtype == UVC_BF16 && !io->shadow) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_forward: bf16 mode needs the shadow buffer");
+  Ctx c;
+  if (!bind(c, cfg, blocks, nblocks, io, stream, 0)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_forward: workspace too small");
+  return forward(c, cfg, blocks, nblocks, 0);
 }
 
 extern "C" int uvc_vit_compact_train_forward(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* stream) {
-  TCtx c;
+  Ctx c;
   TRY(setup_train(c, cfg, blocks, nblocks, io, stream));
   if (!io->x || !io->logits || (cfg->ntok == 2 && !io->logits_dist)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_train_forward: null io member");
-  const CDims& d = c.d;
-  TWork& w = c.w;
-  uvc_vit_offsets o; uvc_vit_shadow_offsets so;
-  TRY(uvc_vit_compact_train_layout(cfg, blocks, nblocks, &o, &so));
-  const float* P = io->params;
-  auto wm = [&](int64_t poff, int64_t soff) -> const void* { return d.dtype == UVC_F32 ? (const void*)(P + poff) : (const void*)((const char*)io->shadow + soff * d.tsz); };
-  const int rf = d.rlow ? 0 : 1;
-  if (!io->patches_in) TRY(uvc_patchify(io->x, w.patches, d.B, d.C, d.S, d.P, d.dtype, stream));
-  TRY(ntx(c, w.patches, 0, wm(o.patch_w, so.patch_w), w.pe, 1, d.B * d.np, d.D, d.K0, UVC_EPI_BIAS, P + o.patch_b));
-  TRY(uvc_assemble_tokens(w.pe, P + o.cls_token, d.ntok == 2 ? P + o.dist_token : nullptr, P + o.pos_embed, io->patch_mask, w.x0, d.B, d.np,
-                          d.D, d.ntok, d.rlow, stream));
-  bool ones_ready = false;
-  auto add_bias = [&](void* x, const float* bias) -> int {
-    if (!ones_ready) {
-      const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)w.ones, 0x3f800000, (size_t)d.M, (hipStream_t)stream);
-      if (e != hipSuccess) return uvc_set_error(e, __FILE__, __LINE__);
-      ones_ready = true;
-    }
-    return uvc_add_outer(x, w.ones, bias, d.M, d.D, d.dtype, rf, stream);
-  };
-  const Chain ch = chain_of(w, blocks, nblocks);
-  for (int k = 0; k < nblocks; ++k) {
-    const uvc_compact_block& bk = blocks[k];
-    const TBlock& b = w.blk[k];
-    const int64_t* q = o.blk[k];
-    const int nq = bk.heads * (128 + bk.v_dim), no = bk.heads * bk.v_dim;
-    void* xin = ch.xin[k];
-    void* x1 = ch.x1[k];
-    if (bk.heads > 0) {
-      TRY(ln_fwd_t(c, xin, P + q[0], P + q[1], b.h1, b.mean1, b.rstd1, d.M, 1, d.D));
-      TRY(ntx(c, b.h1, 0, wm(q[2], so.blk_w[k][0]), b.qkv, 0, d.M, nq, d.D, UVC_EPI_BIAS, P + q[3]));
-      uvc_attn_args a;
-      memset(&a, 0, sizeof(a));
-      a.qkv = b.qkv; a.o = b.o; a.lse = b.lse; a.B = d.B; a.N = d.N; a.H = bk.heads; a.head_dim = 64; a.dtype = d.dtype; a.scale = 0.125f;
-      a.v_dim = bk.v_dim;
-      TRY(uvc_attention_fwd(&a, stream));
-      TRY(ntx(c, b.o, 0, wm(q[4], so.blk_w[k][1]), x1, rf, d.M, d.D, no, UVC_EPI_BIAS_RESID, P + q[5], xin));
-    } else {
-      TRY(add_bias(x1, P + q[5]));
-    }
-    if (bk.hidden > 0) {
-      TRY(ln_fwd_t(c, x1, P + q[6], P + q[7], b.h2, b.mean2, b.rstd2, d.M, 1, d.D));
-      // gp = GELU'(pre-activation), all the backward needs of it; u = GELU
-      TRY(ntx(c, b.h2, 0, wm(q[8], so.blk_w[k][2]), b.gp, 0, d.M, bk.hidden, d.D, UVC_EPI_BIAS_GELU_GRAD, P + q[9], nullptr, nullptr, b.u));
-      TRY(ntx(c, b.u, 0, wm(q[10], so.blk_w[k][3]), b.xo, rf, d.M, d.D, bk.hidden, UVC_EPI_BIAS_RESID, P + q[11], x1));
-    } else {
-      TRY(add_bias(x1, P + q[11]));
-    }
-  }
-  void* xL = ch.xin[nblocks];
-  TRY(ln_fwd_t(c, xL, P + o.norm_w, P + o.norm_b, w.hc, w.meanf, w.rstdf, d.B * d.ntok, d.ntok, (int64_t)d.N * d.D));
-  TRY(ntx(c, w.hc, 0, wm(o.head_w, so.head_w), io->logits, 1, d.B, d.NC, d.D, UVC_EPI_BIAS, P + o.head_b, nullptr, nullptr, nullptr, d.ntok * d.D));
-  if (d.ntok == 2)
-    TRY(ntx(c, (const char*)w.hc + (size_t)d.D * d.tsz, 0, wm(o.headd_w, so.headd_w), io->logits_dist, 1, d.B, d.NC, d.D, UVC_EPI_BIAS, P + o.headd_b,
-            nullptr, nullptr, nullptr, d.ntok * d.D));
-  return UVC_OK;
+  return forward(c, cfg, blocks, nblocks, 1);
 }
 
 extern "C" int uvc_vit_compact_backward(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* stream) {
-  TCtx c;
+  Ctx c;
   TRY(setup_train(c, cfg, blocks, nblocks, io, stream));
   if (!io->grads || !io->d_logits || (cfg->ntok == 2 && !io->d_logits_dist)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_backward: null io member");
   const CDims& d = c.d;
-  TWork& w = c.w;
+  Work& w = c.w;
   uvc_vit_offsets o; uvc_vit_shadow_offsets so;
   TRY(uvc_vit_compact_train_layout(cfg, blocks, nblocks, &o, &so));
   const float* P = io->params;
@@ -572,12 +446,12 @@ extern "C" int uvc_vit_compact_backward(const uvc_vit_cfg* cfg, const uvc_compac
   const int rh = d.B * d.ntok;
   const Chain ch = chain_of(w, blocks, nblocks);
   // heads: dhc = dlogits . W, dW = dlogits^T . hc, db = colsum(dlogits)
-  TRY(ntx(c, io->d_logits, 1, wt(so.head_wt), w.dhc, 0, d.B, d.D, d.NC, UVC_EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, d.ntok * d.D));
-  TRY(tnx(c, io->d_logits, 1, w.hc, G + o.head_w, G + o.head_b, d.B, d.NC, d.D, 0, d.ntok * d.D));
+  TRY(nt(c, io->d_logits, 1, wt(so.head_wt), w.dhc, 0, d.B, d.D, d.NC, UVC_EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, d.ntok * d.D));
+  TRY(tn(c, io->d_logits, 1, w.hc, G + o.head_w, G + o.head_b, d.B, d.NC, d.D, 0, d.ntok * d.D));
   if (d.ntok == 2) {
-    TRY(ntx(c, io->d_logits_dist, 1, wt(so.headd_wt), (char*)w.dhc + (size_t)d.D * d.tsz, 0, d.B, d.D, d.NC, UVC_EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0,
+    TRY(nt(c, io->d_logits_dist, 1, wt(so.headd_wt), (char*)w.dhc + (size_t)d.D * d.tsz, 0, d.B, d.D, d.NC, UVC_EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0,
             d.ntok * d.D));
-    TRY(tnx(c, io->d_logits_dist, 1, (const char*)w.hc + (size_t)d.D * d.tsz, G + o.headd_w, G + o.headd_b, d.B, d.NC, d.D, 0, d.ntok * d.D));
+    TRY(tn(c, io->d_logits_dist, 1, (const char*)w.hc + (size_t)d.D * d.tsz, G + o.headd_w, G + o.headd_b, d.B, d.NC, d.D, 0, d.ntok * d.D));
   }
   // final norm on the token rows: dL/dx_L is zero on every other row
   int cur = 0, slot = 0;
@@ -585,20 +459,20 @@ extern "C" int uvc_vit_compact_backward(const uvc_vit_cfg* cfg, const uvc_compac
     const hipError_t he = hipMemsetAsync(w.g[cur], 0, (size_t)d.M * d.D * d.tsz, hs);
     if (he != hipSuccess) return uvc_set_error(he, __FILE__, __LINE__);
   }
-  TRY(ln_bwd_t(c, slot++, w.dhc, ch.xin[nblocks], P + o.norm_w, G + o.norm_w, G + o.norm_b, w.meanf, w.rstdf, w.g[cur], nullptr, rh, d.ntok, (int64_t)d.N * d.D));
+  TRY(ln_bwd(c, slot++, w.dhc, ch.xin[nblocks], P + o.norm_w, G + o.norm_w, G + o.norm_b, w.meanf, w.rstdf, w.g[cur], nullptr, rh, d.ntok, (int64_t)d.N * d.D));
   for (int k = nblocks - 1; k >= 0; --k) {
     const uvc_compact_block& bk = blocks[k];
-    const TBlock& b = w.blk[k];
+    const BlockBufs& b = w.blk[k];
     const int64_t* q = o.blk[k];
-    const int nq = bk.heads * (128 + bk.v_dim), no = bk.heads * bk.v_dim, F = bk.hidden;
+    const int nq = qkv_rows(bk), no = attn_cols(bk), F = bk.hidden;
     // MLP branch: g = dL/d(block output)
     if (F > 0) {
       void* g = w.g[cur];
-      TRY(ntx(c, g, gf, wt(so.blk_wt[k][3]), w.dA, 0, d.M, F, d.D, UVC_EPI_MUL_AUX, nullptr, nullptr, b.gp));      // dA = (g . W2) * GELU'
-      TRY(tnx(c, g, gf, b.u, G + q[10], G + q[11], d.M, d.D, F));
-      TRY(ntx(c, w.dA, 0, wt(so.blk_wt[k][2]), w.dH, 0, d.M, d.D, F, UVC_EPI_NONE));
-      TRY(tnx(c, w.dA, 0, b.h2, G + q[8], G + q[9], d.M, F, d.D));
-      TRY(ln_bwd_t(c, slot++, w.dH, ch.x1[k], P + q[6], G + q[6], G + q[7], b.mean2, b.rstd2, w.g[cur ^ 1], g, d.M, 1, d.D));      // dL/dx1
+      TRY(nt(c, g, gf, wt(so.blk_wt[k][3]), w.dA, 0, d.M, F, d.D, UVC_EPI_MUL_AUX, nullptr, nullptr, b.gp));      // dA = (g . W2) * GELU'
+      TRY(tn(c, g, gf, b.u, G + q[10], G + q[11], d.M, d.D, F));
+      TRY(nt(c, w.dA, 0, wt(so.blk_wt[k][2]), w.dH, 0, d.M, d.D, F, UVC_EPI_NONE));
+      TRY(tn(c, w.dA, 0, b.h2, G + q[8], G + q[9], d.M, F, d.D));
+      TRY(ln_bwd(c, slot++, w.dH, ch.x1[k], P + q[6], G + q[6], G + q[7], b.mean2, b.rstd2, w.g[cur ^ 1], g, d.M, 1, d.D));      // dL/dx1
       cur ^= 1;
     } else {      // the branch is fc2.bias: its gradient is the column sum of the stream, which passes through; norm2 is never read
       TRY(uvc_colsum(w.g[cur], d.M, d.D, d.D, d.dtype, gf, w.cs_partial, G + q[11], 1.0f, nullptr, 0.f, nullptr, stream));
@@ -607,26 +481,26 @@ extern "C" int uvc_vit_compact_backward(const uvc_vit_cfg* cfg, const uvc_compac
     // attention branch: gB = dL/dx1
     if (bk.heads > 0) {
       void* gB = w.g[cur];
-      TRY(ntx(c, gB, gf, wt(so.blk_wt[k][1]), w.dO, 0, d.M, no, d.D, UVC_EPI_NONE));
-      TRY(tnx(c, gB, gf, b.o, G + q[4], G + q[5], d.M, d.D, no));
+      TRY(nt(c, gB, gf, wt(so.blk_wt[k][1]), w.dO, 0, d.M, no, d.D, UVC_EPI_NONE));
+      TRY(tn(c, gB, gf, b.o, G + q[4], G + q[5], d.M, d.D, no));
       uvc_attn_args a;
       memset(&a, 0, sizeof(a));
       a.qkv = b.qkv; a.o = b.o; a.lse = b.lse; a.dout = w.dO; a.dqkv = w.dqkv; a.delta = w.delta;
       a.B = d.B; a.N = d.N; a.H = bk.heads; a.head_dim = 64; a.dtype = d.dtype; a.scale = 0.125f; a.v_dim = bk.v_dim;
       TRY(uvc_attention_bwd_vdim(&a, stream));
-      TRY(ntx(c, w.dqkv, 0, wt(so.blk_wt[k][0]), w.dH, 0, d.M, d.D, nq, UVC_EPI_NONE));
-      TRY(tnx(c, w.dqkv, 0, b.h1, G + q[2], G + q[3], d.M, nq, d.D));
-      TRY(ln_bwd_t(c, slot++, w.dH, ch.xin[k], P + q[0], G + q[0], G + q[1], b.mean1, b.rstd1, w.g[cur ^ 1], gB, d.M, 1, d.D));      // dL/dx_k
+      TRY(nt(c, w.dqkv, 0, wt(so.blk_wt[k][0]), w.dH, 0, d.M, d.D, nq, UVC_EPI_NONE));
+      TRY(tn(c, w.dqkv, 0, b.h1, G + q[2], G + q[3], d.M, nq, d.D));
+      TRY(ln_bwd(c, slot++, w.dH, ch.xin[k], P + q[0], G + q[0], G + q[1], b.mean1, b.rstd1, w.g[cur ^ 1], gB, d.M, 1, d.D));      // dL/dx_k
       cur ^= 1;
     } else {
       TRY(uvc_colsum(w.g[cur], d.M, d.D, d.D, d.dtype, gf, w.cs_partial, G + q[5], 1.0f, nullptr, 0.f, nullptr, stream));
       TRY(zero_f32(c, G + q[0], q[5] - q[0]));
     }
   }
-  TRY(flush_ln_t(c));
+  TRY(flush_ln(c));
   // token assembly (the mode-1 token mask is a constant: no d_patch_mask) and the patch-embedding weight gradient
   TRY(uvc_assemble_tokens_bwd(w.g[cur], w.pe, io->patch_mask, w.dpe, G + o.pos_embed, G + o.cls_token, d.ntok == 2 ? G + o.dist_token : nullptr,
                               nullptr, d.B, d.np, d.D, d.ntok, d.dtype, 0, d.dtype == UVC_BF16, 0.f, stream));
-  TRY(tnx(c, w.dpe, 0, w.patches, G + o.patch_w, G + o.patch_b, d.B * d.np, d.D, d.K0));
+  TRY(tn(c, w.dpe, 0, w.patches, G + o.patch_w, G + o.patch_b, d.B * d.np, d.D, d.K0));
   return UVC_OK;
 }

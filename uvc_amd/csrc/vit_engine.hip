@@ -1,31 +1,9 @@
 // DeiT forward / backward sequencer: enqueues the fixed kernel sequence of one
 // DistilledVisionTransformer pass (UVC/models/model_distilled.py:429-531) on a HIP stream.
 // Host code only; every arithmetic step is one of the kernels behind uvc_kernels.h.
-#include "common.h"
-#include "../../include/uvc_kernels.h"
-#include "../../include/uvc_vit.h"
-#include <string.h>
+#include "engine_host.h"
 
 namespace {
-
-struct Dims {
-  int B, S, P, C, D, L, H, F, NC, ntok, np, N, M, K0, dtype, qkv_bias;
-  int rlow;              // the residual stream (x_l, x1 of every block, the final rows) is bf16: the throughput mode unless uvc_vit_cfg.resid_f32
-  float eps;
-  size_t tsz, rsz;       // bytes per operand element (T); per residual-stream element
-};
-Dims dims_of(const uvc_vit_cfg& c, int B) {
-  Dims d;
-  d.B = B; d.S = c.img_size; d.P = c.patch_size; d.C = c.in_chans; d.D = c.embed_dim; d.L = c.depth; d.H = c.num_heads;
-  d.F = c.hidden; d.NC = c.num_classes; d.ntok = c.ntok; d.np = (c.img_size / c.patch_size) * (c.img_size / c.patch_size);
-  d.N = d.np + d.ntok; d.M = B * d.N; d.K0 = c.in_chans * c.patch_size * c.patch_size; d.dtype = c.dtype;
-  d.tsz = c.dtype == UVC_F32 ? 4 : 2;
-  d.rlow = (c.dtype == UVC_BF16 && !c.resid_f32) ? 1 : 0;
-  d.rsz = d.rlow ? 2 : 4;
-  d.eps = c.ln_eps > 0.f ? c.ln_eps : 1e-6f;
-  d.qkv_bias = c.no_qkv_bias ? 0 : 1;
-  return d;
-}
 
 int check_cfg(const uvc_vit_cfg* c) {
   if (!c) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit: null cfg");
@@ -41,14 +19,7 @@ int check_cfg(const uvc_vit_cfg* c) {
   return UVC_OK;
 }
 
-inline int64_t al4(int64_t n) { return (n + 3) & ~(int64_t)3; }
-
 // ---- workspace carving ---------------------------------------------------------------------------
-struct Carver {
-  char* base; int64_t off;
-  void* take(int64_t bytes) { void* p = base ? base + off : nullptr; off += (bytes + 255) & ~(int64_t)255; return p; }
-};
-
 struct BlockBufs {      // x, x1: residual-stream rows (float32, or bf16 when Dims::rlow)
   void* x; void* h1; void* qkv; void* o; float* lse; float* mean1; float* rstd1;
   void* x1; void* h2; float* mean2; float* rstd2; void* a; void* u;
@@ -329,8 +300,6 @@ int tail_block(const Ctx& c) {
   return last;
 }
 
-#define TRY(x) do { if (int e_ = (x)) return e_; } while (0)
-
 int setup(Ctx& c, const uvc_vit_cfg* cfg, const uvc_vit_io* io, void* stream, bool bwd) {
   TRY(check_cfg(cfg));
   if (!io || !io->params || !io->workspace || io->batch <= 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit: null io member");
@@ -357,38 +326,30 @@ extern "C" int uvc_vit_layout(const uvc_vit_cfg* cfg, uvc_vit_offsets* off, uvc_
   const Dims d = dims_of(*cfg, 1);
   if (off) {
     memset(off, 0xff, sizeof(*off));
-    int64_t o = 0;
-    auto put = [&](int64_t& slot, int64_t n) { slot = o; o += al4(n); };
-    put(off->cls_token, d.D);
-    if (d.ntok == 2) put(off->dist_token, d.D);
-    put(off->pos_embed, (int64_t)d.N * d.D);
-    put(off->patch_w, (int64_t)d.D * d.K0); put(off->patch_b, d.D);
+    Slots put{0, 4};
+    layout_embed(d, off, put);
     for (int l = 0; l < d.L; ++l) {
       int64_t* b = off->blk[l];
       put(b[0], d.D); put(b[1], d.D); put(b[2], (int64_t)3 * d.D * d.D); put(b[3], 3 * d.D); put(b[4], (int64_t)d.D * d.D); put(b[5], d.D);
       put(b[6], d.D); put(b[7], d.D); put(b[8], (int64_t)d.F * d.D); put(b[9], d.F); put(b[10], (int64_t)d.D * d.F); put(b[11], d.D);
     }
-    put(off->norm_w, d.D); put(off->norm_b, d.D);
-    put(off->head_w, (int64_t)d.NC * d.D); put(off->head_b, d.NC);
-    if (d.ntok == 2) { put(off->headd_w, (int64_t)d.NC * d.D); put(off->headd_b, d.NC); }
-    off->n_main = o;
+    layout_heads(d, off, put);
     put(off->gate, 2 * d.L);
     put(off->gumbel_w, d.D); put(off->gumbel_b, 1);
     put(off->patch_gating, d.np);
     for (int l = 0; l < d.L; ++l) { put(off->skip[l][0], 2); put(off->skip[l][1], 2); }
-    off->n_total = o;
+    off->n_total = put.o;
   }
   if (soff) {
     memset(soff, 0xff, sizeof(*soff));
-    int64_t o = 0;
-    auto put = [&](int64_t& slot, int64_t n) { slot = o; o += (n + 7) & ~(int64_t)7; };
+    Slots put{0, 8};
     put(soff->patch_w, (int64_t)d.D * d.K0);
     const int64_t sz[4] = {(int64_t)3 * d.D * d.D, (int64_t)d.D * d.D, (int64_t)d.F * d.D, (int64_t)d.D * d.F};
     for (int l = 0; l < d.L; ++l)
       for (int j = 0; j < 4; ++j) { put(soff->blk_w[l][j], sz[j]); put(soff->blk_wt[l][j], sz[j]); }
     put(soff->head_w, (int64_t)d.NC * d.D); put(soff->head_wt, (int64_t)d.NC * d.D);
     if (d.ntok == 2) { put(soff->headd_w, (int64_t)d.NC * d.D); put(soff->headd_wt, (int64_t)d.NC * d.D); }
-    soff->n_total = o;
+    soff->n_total = put.o;
   }
   return UVC_OK;
 }
@@ -432,27 +393,16 @@ extern "C" int uvc_vit_update_shadows(const uvc_vit_cfg* cfg, const float* param
   uvc_vit_offsets off; uvc_vit_shadow_offsets so;
   TRY(uvc_vit_layout(cfg, &off, &so));
   const bool f32 = d.dtype == UVC_F32;           // float32 mode: only the transposed copies are needed
-  int64_t srcs[64], ws[64], wts[64];
-  int32_t Rs[64], Cs[64];
-  int n = 0;
-  auto flush = [&]() -> int {
-    if (n == 0) return UVC_OK;
-    const int e = uvc_cast_transpose_multi(params, shadow, n, srcs, Rs, Cs, ws, wts, d.dtype, stream);
-    n = 0;
-    return e;
-  };
-  auto one = [&](int64_t p, int R, int C, int64_t sw, int64_t swt) -> int {
-    srcs[n] = p; Rs[n] = R; Cs[n] = C; ws[n] = f32 ? -1 : sw; wts[n] = swt; ++n;
-    return n == 64 ? flush() : UVC_OK;
-  };
-  if (!f32) TRY(one(off.patch_w, d.D, d.K0, so.patch_w, -1));
+  ShadowBatch sb{params, shadow, d.dtype, stream};
+  auto one = [&](int64_t p, int R, int C, int64_t sw, int64_t swt) { return sb.add(p, R, C, f32 ? -1 : sw, swt); };
+  TRY(one(off.patch_w, d.D, d.K0, so.patch_w, -1));
   const int RC[4][2] = {{3 * d.D, d.D}, {d.D, d.D}, {d.F, d.D}, {d.D, d.F}};
   const int pi[4] = {2, 4, 8, 10};
   for (int l = 0; l < d.L; ++l)
     for (int j = 0; j < 4; ++j) TRY(one(off.blk[l][pi[j]], RC[j][0], RC[j][1], so.blk_w[l][j], so.blk_wt[l][j]));
   TRY(one(off.head_w, d.NC, d.D, so.head_w, so.head_wt));
   if (d.ntok == 2) TRY(one(off.headd_w, d.NC, d.D, so.headd_w, so.headd_wt));
-  return flush();
+  return sb.flush();
 }
 
 // ------------------------------------------------------------------------------------------------
