@@ -65,6 +65,43 @@ int uvc_image_prep_workspace(uvc_image_desc* desc, int32_t B, int32_t S, int64_t
 /* Three launches whatever B is: coefficient tables, first pass, second pass + flip + normalise. */
 int uvc_image_prep(const uvc_image_prep_args* args, void* stream);
 
+/* ---- crop windows of a resident store.
+ * A dataset that stays in device memory (uvc_amd/packed.py: every image HWC uint8, rows of img_w*3 bytes, back to back) is resampled
+ * without copying its crops out: each descriptor names a stored image and a window inside it, and the passes read the window's rows
+ * at the stored image's row stride.  The output is, bit for bit, uvc_image_prep's on the same crops copied out contiguously; the
+ * vertical-first rule is evaluated on the crop's size, as Image.resize does after crop().  All store addressing is 64-bit. */
+typedef struct uvc_image_crop_desc {
+  int64_t src_offset;            /* in: byte offset of the stored image's first pixel in the store */
+  int32_t img_h, img_w;          /* in: stored size, >= 1; rows of img_w*3 bytes */
+  int32_t crop_y, crop_x;        /* in: top-left of the crop window inside the stored image */
+  int32_t crop_h, crop_w;        /* in: crop size, >= 1, crop_y + crop_h <= img_h, crop_x + crop_w <= img_w */
+  int32_t resize_h, resize_w;    /* in: size the crop is resampled to, >= S */
+  int32_t win_y, win_x;          /* in: top-left of the S x S output window in the resized crop */
+  int32_t flip;                  /* in: 1 = mirror the output columns */
+  int32_t kh, kv;                /* out: as in uvc_image_desc */
+  int32_t span0, span;           /* out: crop rows (order 0) or crop columns (order 1) the first pass covers */
+  int32_t order;                 /* out */
+  int64_t ws_offset;             /* out */
+} uvc_image_crop_desc;
+
+typedef struct uvc_image_prep_crops_args {
+  const uint8_t* src;            /* the store */
+  int64_t src_bytes;             /* bytes of the store: a stored image reaching past it is not read (its output is left untouched) */
+  const uvc_image_crop_desc* desc; /* [B] device copy of the descriptors completed by uvc_image_prep_crops_workspace */
+  void* workspace;               /* >= the bytes uvc_image_prep_crops_workspace returned, 16-byte aligned */
+  int64_t workspace_bytes;
+  void* out;                     /* [B, 3, S, S]: float32 (UVC_IMAGE_OUT_F32) or uint8 (UVC_IMAGE_OUT_U8) */
+  float mean[3], std[3];
+  int32_t B, S, out_dtype, reserved;
+} uvc_image_prep_crops_args;
+
+/* Host only: checks that every crop lies inside its image and every image inside the store (store_bytes), applies the limits of
+ * uvc_image_prep_workspace on sides, S and B, fills the "out" fields and writes the workspace size to *bytes. */
+int uvc_image_prep_crops_workspace(uvc_image_crop_desc* desc, int32_t B, int32_t S, int64_t store_bytes, int64_t* bytes);
+
+/* The same three launches, reading crop windows of the store; no host sync, no allocation. */
+int uvc_image_prep_crops(const uvc_image_prep_crops_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,16 @@ class uvc_image_prep_args(C.Structure):      # include/uvc_data.h
                [(n, C.c_int32) for n in ("B", "S", "out_dtype", "reserved")]
 
 
+class uvc_image_crop_desc(C.Structure):      # include/uvc_data.h
+    _fields_ = [("src_offset", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("img_h", "img_w", "crop_y", "crop_x", "crop_h", "crop_w", "resize_h", "resize_w", "win_y", "win_x", "flip",
+                                         "kh", "kv", "span0", "span", "order")] + [("ws_offset", C.c_int64)]
+
+
+class uvc_image_prep_crops_args(C.Structure):   # include/uvc_data.h
+    _fields_ = uvc_image_prep_args._fields_
+
+
 UVC_F32, UVC_BF16 = 0, 1
 UVC_IMAGE_OUT_F32, UVC_IMAGE_OUT_U8 = 0, 1
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_RESID_GATE, EPI_DGELU, EPI_BIAS_GELU_OUT, EPI_BIAS_GELU_GRAD, EPI_MUL_AUX = range(9)
@@ -221,6 +231,8 @@ _SIGNATURES = {
     # include/uvc_data.h
     "uvc_image_prep_workspace": [VP, I32, I32, I64, C.POINTER(I64)],
     "uvc_image_prep": [C.POINTER(uvc_image_prep_args), VP],
+    "uvc_image_prep_crops_workspace": [VP, I32, I32, I64, C.POINTER(I64)],
+    "uvc_image_prep_crops": [C.POINTER(uvc_image_prep_crops_args), VP],
     # include/uvc_t2t.h
     "uvc_unfold_ln_fwd": [C.POINTER(uvc_unfold_args), VP],
     "uvc_unfold_ln_bwd": [C.POINTER(uvc_unfold_args), VP],

@@ -1,5 +1,7 @@
 // Image input step (include/uvc_data.h): PIL's antialiased bilinear resample of a ragged batch of uint8 HWC images, then
-// ToTensor + Normalize, into a [B, 3, S, S] batch.  Three launches per batch:
+// ToTensor + Normalize, into a [B, 3, S, S] batch.  The sources are contiguous uploads (uvc_image_prep) or crop windows inside the
+// images of a store that stays in device memory (uvc_image_prep_crops); the kernels are templates on the args struct, whose
+// descriptor type says which.  Three launches per batch:
 //   k_prep_coeffs   one thread per (image, output column or row): PIL's precompute_coeffs + normalize_coeffs_8bpc in float64
 //   k_prep_pass1    the first pass into a uint8 intermediate: horizontal, one thread per (covered source row, output column), or, for
 //                   the tall sources Image.resize shrinks vertically first, vertical, one thread per (output row, covered source column)
@@ -67,29 +69,61 @@ __host__ __device__ inline WsLayout ws_layout(int S, int kh, int kv, int span) {
   return L;
 }
 
+// Source accessors: what the passes resample is a window of src_h x src_w pixels whose first byte is src_base() into `src` and whose
+// rows lie src_row_bytes() apart.  uvc_image_desc: the whole contiguous upload.  uvc_image_crop_desc: a crop window inside an image
+// of a resident store, rows at the stored image's stride.  Everything else (resize, window, flip, the "out" fields) has the same
+// names in both descriptors, so one set of kernels serves both.
+__host__ __device__ inline int src_h(const uvc_image_desc& d) { return d.src_h; }
+__host__ __device__ inline int src_w(const uvc_image_desc& d) { return d.src_w; }
+__host__ __device__ inline int64_t src_base(const uvc_image_desc& d) { return d.src_offset; }
+__host__ __device__ inline int64_t src_row_bytes(const uvc_image_desc& d) { return (int64_t)d.src_w * 3; }
+__host__ __device__ inline bool src_sides_ok(const uvc_image_desc& d) {
+  return d.src_h >= 1 && d.src_w >= 1 && d.src_h <= kMaxSide && d.src_w <= kMaxSide;
+}
+__host__ __device__ inline bool src_fits(const uvc_image_desc& d, int64_t src_bytes) {
+  return d.src_offset >= 0 && d.src_offset <= src_bytes - (int64_t)d.src_h * d.src_w * 3;
+}
+
+__host__ __device__ inline int src_h(const uvc_image_crop_desc& d) { return d.crop_h; }
+__host__ __device__ inline int src_w(const uvc_image_crop_desc& d) { return d.crop_w; }
+__host__ __device__ inline int64_t src_base(const uvc_image_crop_desc& d) {
+  return d.src_offset + ((int64_t)d.crop_y * d.img_w + d.crop_x) * 3;
+}
+__host__ __device__ inline int64_t src_row_bytes(const uvc_image_crop_desc& d) { return (int64_t)d.img_w * 3; }
+__host__ __device__ inline bool src_sides_ok(const uvc_image_crop_desc& d) {   // the crop lies inside its image
+  if (d.img_h < 1 || d.img_w < 1 || d.img_h > kMaxSide || d.img_w > kMaxSide) return false;
+  if (d.crop_h < 1 || d.crop_w < 1 || d.crop_y < 0 || d.crop_x < 0) return false;
+  return d.crop_y <= d.img_h - d.crop_h && d.crop_x <= d.img_w - d.crop_w;
+}
+__host__ __device__ inline bool src_fits(const uvc_image_crop_desc& d, int64_t src_bytes) {   // the image lies inside the store
+  return d.src_offset >= 0 && d.src_offset <= src_bytes - (int64_t)d.img_h * d.img_w * 3;
+}
+
 // The device trusts nothing it did not check: an image whose descriptor does not fit the buffers it was given is skipped.
-__device__ inline bool desc_ok(const uvc_image_desc& d, const uvc_image_prep_args& a) {
-  if (d.src_h < 1 || d.src_w < 1 || d.src_h > kMaxSide || d.src_w > kMaxSide) return false;
+template <class Desc, class Args>
+__device__ inline bool desc_ok(const Desc& d, const Args& a) {
+  if (!src_sides_ok(d)) return false;
   if (d.resize_h < a.S || d.resize_w < a.S || d.resize_h > kMaxSide || d.resize_w > kMaxSide) return false;
   if (d.win_y < 0 || d.win_x < 0 || d.win_y > d.resize_h - a.S || d.win_x > d.resize_w - a.S) return false;
   if (d.kh < 1 || d.kv < 1 || d.span < 1 || d.span0 < 0 || (d.order != 0 && d.order != 1)) return false;
-  if (d.span0 > (d.order ? d.src_w : d.src_h) - d.span) return false;
-  if (d.src_offset < 0 || d.src_offset > a.src_bytes - (int64_t)d.src_h * d.src_w * 3) return false;
+  if (d.span0 > (d.order ? src_w(d) : src_h(d)) - d.span) return false;
+  if (!src_fits(d, a.src_bytes)) return false;
   const WsLayout L = ws_layout(a.S, d.kh, d.kv, d.span);
   if (d.ws_offset < 0 || (d.ws_offset & 15) || d.ws_offset > a.workspace_bytes - L.total) return false;
   return true;
 }
 
-__global__ void __launch_bounds__(256) k_prep_coeffs(uvc_image_prep_args a) {
+template <class Args>
+__global__ void __launch_bounds__(256) k_prep_coeffs(Args a) {
   const int b = blockIdx.y;
-  const uvc_image_desc d = a.desc[b];
+  const auto d = a.desc[b];
   if (!desc_ok(d, a)) return;
   const int S = a.S;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= 2 * S) return;
   const bool horiz = t < S;
   const int i = horiz ? t : t - S;
-  const int in_size = horiz ? d.src_w : d.src_h;
+  const int in_size = horiz ? src_w(d) : src_h(d);
   const int out_size = horiz ? d.resize_w : d.resize_h;
   const int k = horiz ? d.kh : d.kv;
   const AxisFilter f = axis_filter(in_size, out_size);
@@ -145,16 +179,17 @@ __device__ inline void mac3(const uint8_t* s, int64_t stride, const int32_t* k, 
   u[2] = clip8(a2);
 }
 
-__global__ void __launch_bounds__(256) k_prep_pass1(uvc_image_prep_args a) {
+template <class Args>
+__global__ void __launch_bounds__(256) k_prep_pass1(Args a) {
   const int b = blockIdx.y;
-  const uvc_image_desc d = a.desc[b];
+  const auto d = a.desc[b];
   if (!desc_ok(d, a)) return;
   const int S = a.S;
   const WsLayout L = ws_layout(S, d.kh, d.kv, d.span);
   uint8_t* ws = (uint8_t*)a.workspace + d.ws_offset;
   uint8_t* inter = ws + L.inter;
-  const uint8_t* src = a.src + d.src_offset;
-  const int64_t row_bytes = (int64_t)d.src_w * 3;
+  const uint8_t* src = a.src + src_base(d);
+  const int64_t row_bytes = src_row_bytes(d);
   const int64_t total = (int64_t)d.span * S;
   if (d.order == 0) {                  // horizontal: intermediate [span rows][S][3], row r = source row span0 + r
     const int32_t* hb = (const int32_t*)(ws + L.hb);
@@ -173,9 +208,10 @@ __global__ void __launch_bounds__(256) k_prep_pass1(uvc_image_prep_args a) {
   }
 }
 
-__global__ void __launch_bounds__(256) k_prep_pass2(uvc_image_prep_args a) {
+template <class Args>
+__global__ void __launch_bounds__(256) k_prep_pass2(Args a) {
   const int b = blockIdx.y;
-  const uvc_image_desc d = a.desc[b];
+  const auto d = a.desc[b];
   if (!desc_ok(d, a)) return;
   const int S = a.S;
   const WsLayout L = ws_layout(S, d.kh, d.kv, d.span);
@@ -213,27 +249,28 @@ inline int pass_blocks(int S) {
   return (int)(g < 1 ? 1 : (g > 1024 ? 1024 : g));
 }
 
-}  // namespace
+// The host query of both entries: checks, the "out" fields, the workspace layout.  `msg` holds the entry's own wording of the refusals.
+struct WorkspaceMsgs {
+  const char *arg, *sides, *resize, *window, *fits, *span;
+};
 
-extern "C" int uvc_image_prep_workspace(uvc_image_desc* desc, int32_t B, int32_t S, int64_t src_bytes, int64_t* bytes) {
-  if (!desc || !bytes || B < 1 || B > 65535 || S < 1 || S > kMaxS || src_bytes < 0)
-    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep_workspace: bad argument (1 <= B <= 65535, 1 <= S <= 4096)");
+template <class Desc>
+int prep_workspace(Desc* desc, int32_t B, int32_t S, int64_t src_bytes, int64_t* bytes, const WorkspaceMsgs& msg) {
+  if (!desc || !bytes || B < 1 || B > 65535 || S < 1 || S > kMaxS || src_bytes < 0) return uvc_set_error_msg(UVC_ERR_ARG, msg.arg);
   int64_t off = 0;
   for (int32_t b = 0; b < B; ++b) {
-    uvc_image_desc& d = desc[b];
-    if (d.src_h < 1 || d.src_w < 1 || d.src_h > kMaxSide || d.src_w > kMaxSide)
-      return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep_workspace: source sides must lie in [1, 65536]");
-    if (d.resize_h < S || d.resize_w < S || d.resize_h > kMaxSide || d.resize_w > kMaxSide)
-      return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep_workspace: resize sides must lie in [S, 65536]");
-    if (d.win_y < 0 || d.win_x < 0 || d.win_y > d.resize_h - S || d.win_x > d.resize_w - S)
-      return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep_workspace: the S x S window leaves the resized image");
-    if (d.src_offset < 0 || d.src_offset > src_bytes - (int64_t)d.src_h * d.src_w * 3)
-      return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep_workspace: an image reaches past the source buffer");
-    const AxisFilter fh = axis_filter(d.src_w, d.resize_w), fv = axis_filter(d.src_h, d.resize_h);
+    Desc& d = desc[b];
+    if (!src_sides_ok(d)) return uvc_set_error_msg(UVC_ERR_ARG, msg.sides);
+    if (d.resize_h < S || d.resize_w < S || d.resize_h > kMaxSide || d.resize_w > kMaxSide) return uvc_set_error_msg(UVC_ERR_ARG, msg.resize);
+    if (d.win_y < 0 || d.win_x < 0 || d.win_y > d.resize_h - S || d.win_x > d.resize_w - S) return uvc_set_error_msg(UVC_ERR_ARG, msg.window);
+    if (!src_fits(d, src_bytes)) return uvc_set_error_msg(UVC_ERR_ARG, msg.fits);
+    const int h = src_h(d), w = src_w(d);
+    const AxisFilter fh = axis_filter(w, d.resize_w), fv = axis_filter(h, d.resize_h);
     // Image.resize: `if self.size[1] > self.size[0] * 100 and size[1] < self.size[1]` resizes vertically, then horizontally
-    d.order = (d.src_h > (int64_t)d.src_w * 100 && d.resize_h < d.src_h) ? 1 : 0;
+    // (on the size of what is resized: for a crop window, the crop's, as after Image.crop)
+    d.order = (h > (int64_t)w * 100 && d.resize_h < h) ? 1 : 0;
     const AxisFilter& f1 = d.order ? fh : fv;          // the first pass covers the lines the SECOND pass's window reads
-    const int in1 = d.order ? d.src_w : d.src_h, w1 = d.order ? d.win_x : d.win_y;
+    const int in1 = d.order ? w : h, w1 = d.order ? d.win_x : d.win_y;
     double c;
     int y0, n0, y1, n1;
     axis_bounds(f1, in1, w1, c, y0, n0);
@@ -242,7 +279,7 @@ extern "C" int uvc_image_prep_workspace(uvc_image_desc* desc, int32_t B, int32_t
     d.kv = fv.ksize;
     d.span0 = y0;
     d.span = y1 + n1 - y0;
-    if (d.span < 1 || d.span0 + d.span > in1) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep_workspace: empty span");
+    if (d.span < 1 || d.span0 + d.span > in1) return uvc_set_error_msg(UVC_ERR_ARG, msg.span);
     d.ws_offset = off;
     off += ws_layout(S, d.kh, d.kv, d.span).total;
   }
@@ -250,17 +287,49 @@ extern "C" int uvc_image_prep_workspace(uvc_image_desc* desc, int32_t B, int32_t
   return UVC_OK;
 }
 
-extern "C" int uvc_image_prep(const uvc_image_prep_args* a, void* stream) {
-  if (!a || !a->src || !a->desc || !a->workspace || !a->out) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep: null pointer");
+template <class Args>
+int prep_launch(const Args* a, void* stream, const char* null_msg, const char* arg_msg, const char* align_msg) {
+  if (!a || !a->src || !a->desc || !a->workspace || !a->out) return uvc_set_error_msg(UVC_ERR_ARG, null_msg);
   if (a->B < 1 || a->B > 65535 || a->S < 1 || a->S > kMaxS || (a->out_dtype != UVC_IMAGE_OUT_F32 && a->out_dtype != UVC_IMAGE_OUT_U8))
-    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep: bad B, S or out_dtype");
-  if (((uintptr_t)a->workspace & 15) || a->workspace_bytes < 0 || a->src_bytes < 0)
-    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep: workspace must be 16-byte aligned");
+    return uvc_set_error_msg(UVC_ERR_ARG, arg_msg);
+  if (((uintptr_t)a->workspace & 15) || a->workspace_bytes < 0 || a->src_bytes < 0) return uvc_set_error_msg(UVC_ERR_ARG, align_msg);
   hipStream_t st = (hipStream_t)stream;
-  const uvc_image_prep_args args = *a;
-  k_prep_coeffs<<<dim3((2 * args.S + 255) / 256, args.B), 256, 0, st>>>(args);
-  k_prep_pass1<<<dim3(pass_blocks(args.S), args.B), 256, 0, st>>>(args);
-  k_prep_pass2<<<dim3(pass_blocks(args.S), args.B), 256, 0, st>>>(args);
+  const Args args = *a;
+  k_prep_coeffs<Args><<<dim3((2 * args.S + 255) / 256, args.B), 256, 0, st>>>(args);
+  k_prep_pass1<Args><<<dim3(pass_blocks(args.S), args.B), 256, 0, st>>>(args);
+  k_prep_pass2<Args><<<dim3(pass_blocks(args.S), args.B), 256, 0, st>>>(args);
   UVC_CHECK_LAUNCH();
   return UVC_OK;
+}
+
+}  // namespace
+
+extern "C" int uvc_image_prep_workspace(uvc_image_desc* desc, int32_t B, int32_t S, int64_t src_bytes, int64_t* bytes) {
+  static const WorkspaceMsgs msg = {"uvc_image_prep_workspace: bad argument (1 <= B <= 65535, 1 <= S <= 4096)",
+                                    "uvc_image_prep_workspace: source sides must lie in [1, 65536]",
+                                    "uvc_image_prep_workspace: resize sides must lie in [S, 65536]",
+                                    "uvc_image_prep_workspace: the S x S window leaves the resized image",
+                                    "uvc_image_prep_workspace: an image reaches past the source buffer",
+                                    "uvc_image_prep_workspace: empty span"};
+  return prep_workspace(desc, B, S, src_bytes, bytes, msg);
+}
+
+extern "C" int uvc_image_prep(const uvc_image_prep_args* a, void* stream) {
+  return prep_launch(a, stream, "uvc_image_prep: null pointer", "uvc_image_prep: bad B, S or out_dtype",
+                     "uvc_image_prep: workspace must be 16-byte aligned");
+}
+
+extern "C" int uvc_image_prep_crops_workspace(uvc_image_crop_desc* desc, int32_t B, int32_t S, int64_t store_bytes, int64_t* bytes) {
+  static const WorkspaceMsgs msg = {"uvc_image_prep_crops_workspace: bad argument (1 <= B <= 65535, 1 <= S <= 4096)",
+                                    "uvc_image_prep_crops_workspace: image sides must lie in [1, 65536] and the crop inside its image",
+                                    "uvc_image_prep_crops_workspace: resize sides must lie in [S, 65536]",
+                                    "uvc_image_prep_crops_workspace: the S x S window leaves the resized crop",
+                                    "uvc_image_prep_crops_workspace: an image reaches past the store",
+                                    "uvc_image_prep_crops_workspace: empty span"};
+  return prep_workspace(desc, B, S, store_bytes, bytes, msg);
+}
+
+extern "C" int uvc_image_prep_crops(const uvc_image_prep_crops_args* a, void* stream) {
+  return prep_launch(a, stream, "uvc_image_prep_crops: null pointer", "uvc_image_prep_crops: bad B, S or out_dtype",
+                     "uvc_image_prep_crops: workspace must be 16-byte aligned");
 }

@@ -8,6 +8,7 @@ decoded array, so only the crop's pixels are uploaded; resampling, flip, ToTenso
     read_cifar(root, name, train) the local python-pickle CIFAR-10 / CIFAR-100 layout, nothing is downloaded -> ArrayDataset
     ArrayDataset(images, labels) uint8 [N, H, W, 3] in memory
     DeviceLoader(...)            (x float32 [B, 3, S, S] cuda, target int64 cuda) batches, DistributedSampler order
+    (uvc_amd/packed.py: PackedDataset, a dataset decoded once into one file, and ResidentLoader, the same batches from pixels that stay on the GPU)
     build_loaders(args, ...)     the reference's train / test loaders for --dataset cifar10 | cifar100 | imagenet
 
 Deviations from the reference, on purpose (DESIGN.md "Real image data"): the training order is reshuffled every epoch (the
@@ -349,18 +350,42 @@ class DeviceLoader:
         except BaseException as e:                      # noqa: BLE001 (re-raised in the consumer)
             ready.put(e)
 
-    def __iter__(self):
+    # -- device side: the upload of one slot and the launches that read it (ResidentLoader in uvc_amd/packed.py replaces these four)
+    def _new_slot(self):
+        return _Slot()
+
+    def _new_copy_stream(self):
+        return torch.cuda.Stream(self.device)
+
+    def _upload(self, slot):
+        """With the copy stream current: allocates the slot's device buffers and starts their copies.  Returns the buffers."""
+        B = slot.n
+        target = torch.empty(B, dtype=torch.int64, device=self.device)
+        src = torch.empty(max(slot.src_bytes, 1), dtype=torch.uint8, device=self.device)
+        desc = torch.empty(B * 64, dtype=torch.uint8, device=self.device)
+        src[:slot.src_bytes].copy_(slot.pixels[:slot.src_bytes], non_blocking=True)
+        desc.copy_(slot.desc[:B * 64], non_blocking=True)
+        target.copy_(slot.labels[:B], non_blocking=True)
+        return target, src, desc
+
+    def _launch(self, slot, up, ws, x):
+        """With the consumer's stream current, after the upload: the three launches into x.  Returns the batch's target."""
         from . import ops
+        target, src, desc = up
+        ops.image_prep(src[:max(slot.src_bytes, 1)], desc, ws, x, self.mean, self.std)
+        return target
+
+    def __iter__(self):
         idx = self.indices()
         batches = [idx[o:o + self.batch_size] for o in range(0, len(idx), self.batch_size)]
         if not batches:
             return
         if self._copy_stream is None:
-            self._copy_stream = torch.cuda.Stream(self.device)
+            self._copy_stream = self._new_copy_stream()
         main = torch.cuda.current_stream(self.device)
         free, ready, stop = queue.Queue(), queue.Queue(), threading.Event()
         for _ in range(self.ahead + 1):
-            free.put(_Slot())
+            free.put(self._new_slot())
         t = threading.Thread(target=self._producer, args=(batches, free, ready, stop), daemon=True)
         t.start()
         try:
@@ -374,22 +399,16 @@ class DeviceLoader:
                 # everything the copy stream writes is allocated on the copy stream and handed to `main` with record_stream: a block the
                 # allocator gives out on `main` may still be in use by kernels queued there, which the copy stream does not wait for
                 with torch.cuda.stream(self._copy_stream):
-                    target = torch.empty(B, dtype=torch.int64, device=self.device)
-                    src = torch.empty(max(slot.src_bytes, 1), dtype=torch.uint8, device=self.device)
-                    desc = torch.empty(B * 64, dtype=torch.uint8, device=self.device)
-                    src[:slot.src_bytes].copy_(slot.pixels[:slot.src_bytes], non_blocking=True)
-                    desc.copy_(slot.desc[:B * 64], non_blocking=True)
-                    target.copy_(slot.labels[:B], non_blocking=True)
+                    up = self._upload(slot)
                     uploaded = torch.cuda.Event()
                     uploaded.record(self._copy_stream)
                 main.wait_event(uploaded)
                 ws = torch.empty(max(slot.ws_bytes, 16), dtype=torch.uint8, device=self.device)
                 x = torch.empty(B, 3, self.S, self.S, dtype=torch.float32, device=self.device)
                 with torch.cuda.stream(main):
-                    ops.image_prep(src[:max(slot.src_bytes, 1)], desc, ws, x, self.mean, self.std)
-                src.record_stream(main)
-                desc.record_stream(main)
-                target.record_stream(main)
+                    target = self._launch(slot, up, ws, x)
+                for buf in up:
+                    buf.record_stream(main)
                 slot.done = torch.cuda.Event()
                 slot.done.record(main)
                 free.put(slot)
@@ -430,32 +449,52 @@ def host_reference_batch(dataset, indices, S, train, seed, epoch, mean, std, sca
 
 # ---------------------------------------------------------------------------------------------------------------- drivers
 
-def build_loaders(args, rank=0, world=1):
+def build_loaders(args, rank=0, world=1, splits=("train", "test")):
     """get_loader (data_utils.py:13-105) for --dataset cifar10 | cifar100 | imagenet under --data_dir: (train, test) DeviceLoaders.
+    A loader whose split is not in ``splits`` is None (compact eval asks for "test" alone, so --resident 1 uploads no train store).
+    --packed_dir DIR reads DIR/train.uvcpack and DIR/val.uvcpack (uvc_amd/packed.py) in place of the folders or pickles; --resident 1
+    returns ResidentLoaders, which keep the pixels on the device (CIFAR's in-memory arrays, or a pack).
     Sets args.data_classes to the dataset's class count: 10 / 100 for CIFAR, as in the reference, args.num_classes for ImageNet (the folder's
     class count must fit it).  The model head is args.num_classes wide, a multiple of 8 for the engine: for CIFAR it becomes 16 / 104; the
     soft targets cover the data classes and are zero on the padded logits (soft_batches)."""
     S = args.img_size
     nw = getattr(args, "num_workers", 4)
     seed = getattr(args, "seed", 0)
+    packed_dir = getattr(args, "packed_dir", None)
+    resident = bool(int(getattr(args, "resident", 0) or 0))
+    Loader = DeviceLoader
+    if packed_dir or resident:
+        from .packed import EXTENSION, PackedDataset, ResidentLoader
+        if resident:
+            Loader = ResidentLoader
+    if args.dataset not in ("cifar10", "cifar100", "imagenet"):
+        raise ValueError(args.dataset)
+    if packed_dir:
+        train_ds, test_ds = (PackedDataset(os.path.join(packed_dir, split + EXTENSION)) for split in ("train", "val"))
+    elif args.dataset == "imagenet":
+        if resident:
+            raise ValueError("--resident 1 keeps decoded pixels on the device and image folders are not decoded: pack first "
+                             "(python -m uvc_amd.packed pack --dataset imagenet --data_dir D --split train|val --output P/train|val.uvcpack) "
+                             "and pass --packed_dir P")
+        train_ds, test_ds = ImageFolder(os.path.join(args.data_dir, "train")), ImageFolder(os.path.join(args.data_dir, "val"))
+    else:
+        train_ds, test_ds = read_cifar(args.data_dir, args.dataset, True), read_cifar(args.data_dir, args.dataset, False)
     if args.dataset in ("cifar10", "cifar100"):
         args.data_classes = 10 if args.dataset == "cifar10" else 100
         args.num_classes = 16 if args.dataset == "cifar10" else 104
-        train_ds, test_ds = read_cifar(args.data_dir, args.dataset, True), read_cifar(args.data_dir, args.dataset, False)
         kw = dict(mean=CIFAR_MEAN, std=CIFAR_STD, num_workers=nw)
-        train = DeviceLoader(train_ds, args.train_batch_size, S, train=True, scale=(0.05, 1.0), flip=False, seed=seed, rank=rank,
-                             world=world, **kw)
-        test = DeviceLoader(test_ds, args.eval_batch_size, S, train=False, eval="square", **kw)
-    elif args.dataset == "imagenet":
-        train_ds, test_ds = ImageFolder(os.path.join(args.data_dir, "train")), ImageFolder(os.path.join(args.data_dir, "val"))
-        if len(train_ds.classes) > args.num_classes:
-            raise ValueError(f"{len(train_ds.classes)} class folders under {args.data_dir}/train but --num_classes {args.num_classes}")
+        train = Loader(train_ds, args.train_batch_size, S, train=True, scale=(0.05, 1.0), flip=False, seed=seed, rank=rank,
+                       world=world, **kw) if "train" in splits else None
+        test = Loader(test_ds, args.eval_batch_size, S, train=False, eval="square", **kw) if "test" in splits else None
+    else:
+        n_classes = len(train_ds.classes) if train_ds.classes is not None else train_ds.num_classes()
+        if n_classes > args.num_classes:
+            where = f"classes in {os.path.join(packed_dir, 'train' + EXTENSION)}" if packed_dir else f"class folders under {args.data_dir}/train"
+            raise ValueError(f"{n_classes} {where} but --num_classes {args.num_classes}")
         args.data_classes = args.num_classes
         kw = dict(mean=IMAGENET_MEAN, std=IMAGENET_STD, num_workers=nw)
-        train = DeviceLoader(train_ds, args.train_batch_size, S, train=True, seed=seed, rank=rank, world=world, **kw)
-        test = DeviceLoader(test_ds, args.eval_batch_size, S, train=False, eval="center", **kw)
-    else:
-        raise ValueError(args.dataset)
+        train = Loader(train_ds, args.train_batch_size, S, train=True, seed=seed, rank=rank, world=world, **kw) if "train" in splits else None
+        test = Loader(test_ds, args.eval_batch_size, S, train=False, eval="center", **kw) if "test" in splits else None
     return train, test
 
 

@@ -482,22 +482,52 @@ def image_prep_workspace(desc, S: int, src_bytes: int) -> int:
     return int(out.value)
 
 
-def image_prep(src, desc_dev, workspace, out, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0)):
-    """out[B, 3, S, S] (float32: (u8 / 255 - mean) / std, or uint8) = PIL-bilinear resample of the B packed uint8 HWC images in ``src``
-    described by ``desc_dev`` (uint8 device tensor holding the descriptors image_prep_workspace completed) -- three launches."""
+def _image_prep_args(name, args_type, desc_type, src, desc_dev, workspace, out, mean, std):
     _chk(src, desc_dev, workspace, out)
     if src.dtype != torch.uint8 or desc_dev.dtype != torch.uint8 or workspace.dtype != torch.uint8:
-        raise L.UvcHipError("image_prep: src, desc and workspace are byte tensors")
+        raise L.UvcHipError(f"{name}: src, desc and workspace are byte tensors")
     if out.dim() != 4 or out.shape[1] != 3 or out.shape[2] != out.shape[3] or out.dtype not in (torch.float32, torch.uint8):
-        raise L.UvcHipError("image_prep: out must be [B, 3, S, S] float32 or uint8")
+        raise L.UvcHipError(f"{name}: out must be [B, 3, S, S] float32 or uint8")
     B, S = out.shape[0], out.shape[2]
-    if desc_dev.numel() != B * C.sizeof(L.uvc_image_desc):
-        raise L.UvcHipError("image_prep: desc holds a different number of images than out")
-    a = L.uvc_image_prep_args()
+    if desc_dev.numel() != B * C.sizeof(desc_type):
+        raise L.UvcHipError(f"{name}: desc holds a different number of images than out")
+    a = args_type()
     a.src, a.src_bytes, a.desc = L.ptr(src), src.numel(), L.ptr(desc_dev)
     a.workspace, a.workspace_bytes, a.out = L.ptr(workspace), workspace.numel(), L.ptr(out)
     a.mean[:], a.std[:] = [float(v) for v in mean], [float(v) for v in std]
     a.B, a.S = B, S
     a.out_dtype = L.UVC_IMAGE_OUT_U8 if out.dtype == torch.uint8 else L.UVC_IMAGE_OUT_F32
+    return a
+
+
+def image_prep(src, desc_dev, workspace, out, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0)):
+    """out[B, 3, S, S] (float32: (u8 / 255 - mean) / std, or uint8) = PIL-bilinear resample of the B packed uint8 HWC images in ``src``
+    described by ``desc_dev`` (uint8 device tensor holding the descriptors image_prep_workspace completed) -- three launches."""
+    a = _image_prep_args("image_prep", L.uvc_image_prep_args, L.uvc_image_desc, src, desc_dev, workspace, out, mean, std)
     L.check(L.lib().uvc_image_prep(C.byref(a), L.cur_stream()), "uvc_image_prep")
+    return out
+
+
+def image_crop_desc_dtype():
+    """numpy dtype with the layout of uvc_image_crop_desc: a crop window inside an image of a resident store."""
+    import numpy as np
+    return np.dtype(L.uvc_image_crop_desc)
+
+
+def image_prep_crops_workspace(desc, S: int, store_bytes: int) -> int:
+    """image_prep_workspace for crop descriptors (numpy array of image_crop_desc_dtype()): every crop must lie inside its image and
+    every image inside the ``store_bytes`` of the store (uvc_image_prep_crops_workspace: host only)."""
+    if desc.dtype != image_crop_desc_dtype() or not desc.flags.c_contiguous:
+        raise L.UvcHipError("image_prep_crops_workspace: desc must be a C-contiguous array of image_crop_desc_dtype()")
+    out = C.c_int64(0)
+    L.check(L.lib().uvc_image_prep_crops_workspace(desc.ctypes.data, len(desc), int(S), int(store_bytes), C.byref(out)),
+            "uvc_image_prep_crops_workspace")
+    return int(out.value)
+
+
+def image_prep_crops(store, desc_dev, workspace, out, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0)):
+    """image_prep reading crop windows of ``store`` (uint8 device tensor: stored images back to back) in place: bit for bit image_prep
+    on the crops copied out contiguously -- three launches."""
+    a = _image_prep_args("image_prep_crops", L.uvc_image_prep_crops_args, L.uvc_image_crop_desc, store, desc_dev, workspace, out, mean, std)
+    L.check(L.lib().uvc_image_prep_crops(C.byref(a), L.cur_stream()), "uvc_image_prep_crops")
     return out
