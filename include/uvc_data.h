@@ -14,6 +14,20 @@
  * A pass whose axis is unchanged has the identity weights (1, 0), which return the input exactly: PIL skipping such a pass
  * and this library running it give the same bytes.
  *
+ * The filter is a property of the launch (the `filter` field of the args structs; 0 = bilinear, as above).  UVC_IMAGE_FILTER_BICUBIC
+ * is Image.resize(size, BICUBIC), what the released DeiT and T2T-ViT checkpoints were trained and evaluated with: PIL's bicubic_filter
+ * with a = -0.5,
+ *     ((a + 2)|x| - (a + 3)) x^2 + 1   for |x| < 1,      (((|x| - 5)|x| + 8)|x| - 4) a   for |x| < 2,      0 otherwise,
+ * evaluated in float64, so support = 2 max(scale, 1) and ksize = 2 ceil(support) + 1; everything else (bounds, normalisation by the
+ * sum, the rounding of a negative weight as (int)(-0.5 + w 2^22), pass order, spans) is the same code.  Its weights are negative in
+ * places, so a sum can leave 0 .. 255 << 22: each pass clamps to 0 or 255 exactly where PIL's clip8 does, and the second pass reads
+ * the first's clamped bytes.  The sums stay in int32, as PIL's `int`: |sum| <= 255 * 2^22 * sum|w| + 2^21 < 2^31 while sum|w| <
+ * 2.007, and the normalised bicubic weights of one output pixel have sum|w| = 1.25 at phase 1/2 of an upscale (-1/16, 9/16, 9/16,
+ * -1/16) and stay below 1.3 at other scales and at the edges.
+ * The workspace depends on the filter (kh, kv, span0, span): complete the descriptors with the _filter query of the filter the launch
+ * will name.  An image whose kh / kv are not those of the launch's filter is skipped on the device like every other descriptor that
+ * fails its checks: its output is left untouched and its workspace is neither read nor written.
+ *
  * Each image resamples its WHOLE source (box = (0, 0, src_w, src_h)) to resize_h x resize_w and keeps the S x S window at
  * (win_y, win_x): a random resized crop is a host-side slice of the decoded array (only the crop is uploaded) resized to
  * S x S with window (0, 0); Resize(256) + CenterCrop(224) is a resize to the torchvision size with the centre window.
@@ -46,6 +60,7 @@ typedef struct uvc_image_desc {
 } uvc_image_desc;
 
 enum { UVC_IMAGE_OUT_F32 = 0, UVC_IMAGE_OUT_U8 = 1 };
+enum { UVC_IMAGE_FILTER_BILINEAR = 0, UVC_IMAGE_FILTER_BICUBIC = 1 };
 
 typedef struct uvc_image_prep_args {
   const uint8_t* src;            /* packed uint8 HWC sources of all B images */
@@ -55,12 +70,16 @@ typedef struct uvc_image_prep_args {
   int64_t workspace_bytes;
   void* out;                     /* [B, 3, S, S]: float32 (UVC_IMAGE_OUT_F32) or uint8 (UVC_IMAGE_OUT_U8) */
   float mean[3], std[3];         /* float32 per channel (F32 output only) */
-  int32_t B, S, out_dtype, reserved;
+  int32_t B, S, out_dtype;
+  int32_t filter;                /* UVC_IMAGE_FILTER_*: 0 (a zeroed struct) is bilinear; anything else unknown is UVC_ERR_ARG */
 } uvc_image_prep_args;
 
 /* Host only (no device access): checks the B descriptors against S and src_bytes, fills kh, kv, span0, span, order and ws_offset,
  * and writes the workspace size the batch needs to *bytes. */
 int uvc_image_prep_workspace(uvc_image_desc* desc, int32_t B, int32_t S, int64_t src_bytes, int64_t* bytes);
+
+/* The same query for a launch with `filter` (UVC_IMAGE_FILTER_*; 0 equals the function above, an unknown value is UVC_ERR_ARG). */
+int uvc_image_prep_workspace_filter(uvc_image_desc* desc, int32_t B, int32_t S, int64_t src_bytes, int32_t filter, int64_t* bytes);
 
 /* Three launches whatever B is: coefficient tables, first pass, second pass + flip + normalise. */
 int uvc_image_prep(const uvc_image_prep_args* args, void* stream);
@@ -92,12 +111,14 @@ typedef struct uvc_image_prep_crops_args {
   int64_t workspace_bytes;
   void* out;                     /* [B, 3, S, S]: float32 (UVC_IMAGE_OUT_F32) or uint8 (UVC_IMAGE_OUT_U8) */
   float mean[3], std[3];
-  int32_t B, S, out_dtype, reserved;
+  int32_t B, S, out_dtype;
+  int32_t filter;                /* UVC_IMAGE_FILTER_* */
 } uvc_image_prep_crops_args;
 
 /* Host only: checks that every crop lies inside its image and every image inside the store (store_bytes), applies the limits of
  * uvc_image_prep_workspace on sides, S and B, fills the "out" fields and writes the workspace size to *bytes. */
 int uvc_image_prep_crops_workspace(uvc_image_crop_desc* desc, int32_t B, int32_t S, int64_t store_bytes, int64_t* bytes);
+int uvc_image_prep_crops_workspace_filter(uvc_image_crop_desc* desc, int32_t B, int32_t S, int64_t store_bytes, int32_t filter, int64_t* bytes);
 
 /* The same three launches, reading crop windows of the store; no host sync, no allocation. */
 int uvc_image_prep_crops(const uvc_image_prep_crops_args* args, void* stream);

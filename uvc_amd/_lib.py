@@ -147,7 +147,7 @@ class uvc_image_desc(C.Structure):           # include/uvc_data.h
 class uvc_image_prep_args(C.Structure):      # include/uvc_data.h
     _fields_ = [("src", C.c_void_p), ("src_bytes", C.c_int64), ("desc", C.c_void_p), ("workspace", C.c_void_p),
                 ("workspace_bytes", C.c_int64), ("out", C.c_void_p), ("mean", C.c_float * 3), ("std", C.c_float * 3)] + \
-               [(n, C.c_int32) for n in ("B", "S", "out_dtype", "reserved")]
+               [(n, C.c_int32) for n in ("B", "S", "out_dtype", "filter")]
 
 
 class uvc_image_crop_desc(C.Structure):      # include/uvc_data.h
@@ -162,6 +162,7 @@ class uvc_image_prep_crops_args(C.Structure):   # include/uvc_data.h
 
 UVC_F32, UVC_BF16 = 0, 1
 UVC_IMAGE_OUT_F32, UVC_IMAGE_OUT_U8 = 0, 1
+UVC_IMAGE_FILTER_BILINEAR, UVC_IMAGE_FILTER_BICUBIC = 0, 1
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_RESID_GATE, EPI_DGELU, EPI_BIAS_GELU_OUT, EPI_BIAS_GELU_GRAD, EPI_MUL_AUX = range(9)
 EPI_BIAS_GELU_GRAD_Q8, EPI_MUL_AUX_Q8 = 9, 10      # GELU'(a) as one byte per activation (include/uvc_kernels.h)
 Q8_LO, Q8_STEP = -0.13, 1.26 / 255.0               # UVC_Q8_LO, UVC_Q8_STEP
@@ -230,8 +231,10 @@ _SIGNATURES = {
     "uvc_gate_grad": [VP, VP, VP, VP, I32, I32, F32, F32, VP],
     # include/uvc_data.h
     "uvc_image_prep_workspace": [VP, I32, I32, I64, C.POINTER(I64)],
+    "uvc_image_prep_workspace_filter": [VP, I32, I32, I64, I32, C.POINTER(I64)],
     "uvc_image_prep": [C.POINTER(uvc_image_prep_args), VP],
     "uvc_image_prep_crops_workspace": [VP, I32, I32, I64, C.POINTER(I64)],
+    "uvc_image_prep_crops_workspace_filter": [VP, I32, I32, I64, I32, C.POINTER(I64)],
     "uvc_image_prep_crops": [C.POINTER(uvc_image_prep_crops_args), VP],
     # include/uvc_t2t.h
     "uvc_unfold_ln_fwd": [C.POINTER(uvc_unfold_args), VP],

@@ -35,6 +35,8 @@ def build_parser():
     a("--data_dir", default="/ssd1/shixing/imagenet2012"); a("--num_workers", default=4, type=int)
     a("--packed_dir", default=None, help="DIR/train.uvcpack and DIR/val.uvcpack (python -m uvc_amd.packed pack) replace the folders or pickles under --data_dir")
     a("--resident", type=int, default=0, choices=[0, 1], help="1: upload the dataset to the GPU once and crop it there (CIFAR, or any dataset with --packed_dir); in data-parallel runs every rank holds the whole store, because the sampler hands any image to any rank")
+    from .data import add_image_args
+    add_image_args(p)
     a("--model_type", choices=list(CONFIGS) + ["t2t_vit_14", "custom", "custom_t2t"], default="deit_tiny_patch16_224")
     a("--model_path", default=None); a("--pretrained_dir", type=str, default="../ViT-pytorch/pretrain/ViT-B_16.npz"); a("--pretrained", type=int, default=1)
     a("--output_dir", default="../result/output/uvc_train", type=str); a("--img_size", default=224, type=int)

@@ -504,6 +504,8 @@ def _parser():
     e.add_argument("--num_workers", type=int, default=8)
     e.add_argument("--packed_dir", default=None, help="DIR/train.uvcpack and DIR/val.uvcpack (python -m uvc_amd.packed pack) replace the folders or pickles under --data_dir")
     e.add_argument("--resident", type=int, default=0, choices=[0, 1], help="1: upload the dataset to the GPU once and crop it there (CIFAR, or any dataset with --packed_dir); in data-parallel runs every rank holds the whole store, because the sampler hands any image to any rank")
+    from .data import add_image_args
+    add_image_args(e)
     # fine-tune a compact file at its kept widths: Stage 2's training, distillation, teacher, data and Mixup flags (post_train's names and defaults)
     from .post_train import add_stage2_flags
     f = sub.add_parser("finetune")
@@ -619,7 +621,7 @@ def main(argv=None):
     from .post_train import default_args, loader_valid_fn, synthetic_valid_fn
     cm = CompactVisionTransformer(export, precision=args.precision, device=dev)
     vargs = default_args(img_size=export["cfg"]["img_size"], num_classes=export["cfg"]["num_classes"], seed=args.seed)
-    for k in ("eval_batch_size", "eval_steps", "dataset", "data_dir", "num_workers", "packed_dir", "resident"):
+    for k in ("eval_batch_size", "eval_steps", "dataset", "data_dir", "num_workers", "packed_dir", "resident", "interpolation", "crop_pct"):
         setattr(vargs, k, getattr(args, k))
     if args.synthetic:
         acc = synthetic_valid_fn(vargs, dev)(cm)

@@ -1,4 +1,4 @@
-// Image input step (include/uvc_data.h): PIL's antialiased bilinear resample of a ragged batch of uint8 HWC images, then
+// Image input step (include/uvc_data.h): PIL's antialiased bilinear or bicubic resample of a ragged batch of uint8 HWC images, then
 // ToTensor + Normalize, into a [B, 3, S, S] batch.  The sources are contiguous uploads (uvc_image_prep) or crop windows inside the
 // images of a store that stays in device memory (uvc_image_prep_crops); the kernels are templates on the args struct, whose
 // descriptor type says which.  Three launches per batch:
@@ -7,6 +7,13 @@
 //                   the tall sources Image.resize shrinks vertically first, vertical, one thread per (output row, covered source column)
 //   k_prep_pass2    one thread per (image, output row, output column): the other axis, flip, normalise, NCHW store
 // Built with -ffp-contract=off (uvc_amd/build.py): the float64 coefficient arithmetic must round like the C it mirrors.
+//
+// The launch's filter (args.filter) picks the weight function and its support in k_prep_coeffs and the tap count desc_ok expects;
+// the passes are the same code for both.  Bicubic weights are negative in places, so an accumulator can leave [0, 255 << 22] and
+// clip8 between and after the passes does work.  int32 holds every partial sum, as PIL's `int` does: |partial sum| <= 255 * 2^22 *
+// sum|w| + 2^21, which stays below 2^31 while sum|w| < 2.007, and the normalised bicubic weights of one output pixel have sum|w| = 1.25
+// at phase 1/2 of an upscale (-1/16, 9/16, 9/16, -1/16) and stay below 1.3 at the other scales and at the edges that cut taps off
+// (tests/test_image_bicubic_cpu.py sweeps them).
 #include "common.h"
 #include "uvc_data.h"
 
@@ -24,11 +31,16 @@ struct AxisFilter {
   int ksize;
 };
 
-__host__ __device__ inline AxisFilter axis_filter(int in_size, int out_size) {
+__host__ __device__ inline bool filter_ok(int filter) { return filter == UVC_IMAGE_FILTER_BILINEAR || filter == UVC_IMAGE_FILTER_BICUBIC; }
+
+// PIL's filter support: BILINEAR 1.0, BICUBIC 2.0
+__host__ __device__ inline int filter_support(int filter) { return filter == UVC_IMAGE_FILTER_BICUBIC ? 2 : 1; }
+
+__host__ __device__ inline AxisFilter axis_filter(int in_size, int out_size, int filter) {
   AxisFilter f;
   f.scale = (double)in_size / (double)out_size;
   const double fs = f.scale > 1.0 ? f.scale : 1.0;
-  f.support = 1.0 * fs;                // bilinear filter support 1.0
+  f.support = (double)filter_support(filter) * fs;
   f.ksize = (int)ceil(f.support) * 2 + 1;
   f.ss = 1.0 / fs;
   return f;
@@ -48,6 +60,25 @@ __device__ inline double tri(double x) {
   if (x < 0.0) x = -x;
   if (x < 1.0) return 1.0 - x;
   return 0.0;
+}
+
+// PIL Resample.c bicubic_filter (a = -0.5), in its order of operations
+__device__ inline double cubic(double x) {
+  const double a = -0.5;
+  if (x < 0.0) x = -x;
+  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+  return 0.0;
+}
+
+// Is k the ksize = 2 ceil(support) + 1 of this axis under this filter?  In integers: with f = the filter's support, ceil(f max(in / out,
+// 1)) = max(f, ceil(f in / out)), and the float64 quotient cannot cross an integer the exact one does not (f in / out is an integer
+// or at least 1 / out >= 2^-16 away from one).  The host query holds its own float64 ksize to this before it hands it out.
+__host__ __device__ inline bool ksize_ok(int k, int in_size, int out_size, int filter) {
+  const int64_t f = filter_support(filter), c = (k - 1) >> 1;
+  if (k < 1 || !(k & 1) || c < f) return false;
+  if (f * in_size > c * out_size) return false;
+  return c == f || (c - 1) * out_size < f * in_size;
 }
 
 __host__ __device__ inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
@@ -99,13 +130,15 @@ __host__ __device__ inline bool src_fits(const uvc_image_crop_desc& d, int64_t s
   return d.src_offset >= 0 && d.src_offset <= src_bytes - (int64_t)d.img_h * d.img_w * 3;
 }
 
-// The device trusts nothing it did not check: an image whose descriptor does not fit the buffers it was given is skipped.
+// The device trusts nothing it did not check: an image whose descriptor does not fit the buffers it was given, or whose tap counts
+// are not those of the launch's filter (descriptors completed for the other one), is skipped.
 template <class Desc, class Args>
 __device__ inline bool desc_ok(const Desc& d, const Args& a) {
   if (!src_sides_ok(d)) return false;
   if (d.resize_h < a.S || d.resize_w < a.S || d.resize_h > kMaxSide || d.resize_w > kMaxSide) return false;
   if (d.win_y < 0 || d.win_x < 0 || d.win_y > d.resize_h - a.S || d.win_x > d.resize_w - a.S) return false;
-  if (d.kh < 1 || d.kv < 1 || d.span < 1 || d.span0 < 0 || (d.order != 0 && d.order != 1)) return false;
+  if (!ksize_ok(d.kh, src_w(d), d.resize_w, a.filter) || !ksize_ok(d.kv, src_h(d), d.resize_h, a.filter)) return false;   // tables of another filter
+  if (d.span < 1 || d.span0 < 0 || (d.order != 0 && d.order != 1)) return false;
   if (d.span0 > (d.order ? src_w(d) : src_h(d)) - d.span) return false;
   if (!src_fits(d, a.src_bytes)) return false;
   const WsLayout L = ws_layout(a.S, d.kh, d.kv, d.span);
@@ -126,7 +159,8 @@ __global__ void __launch_bounds__(256) k_prep_coeffs(Args a) {
   const int in_size = horiz ? src_w(d) : src_h(d);
   const int out_size = horiz ? d.resize_w : d.resize_h;
   const int k = horiz ? d.kh : d.kv;
-  const AxisFilter f = axis_filter(in_size, out_size);
+  const AxisFilter f = axis_filter(in_size, out_size, a.filter);
+  const bool bicubic = a.filter == UVC_IMAGE_FILTER_BICUBIC;
   double center;
   int xmin, n;
   axis_bounds(f, in_size, (horiz ? d.win_x : d.win_y) + i, center, xmin, n);
@@ -137,11 +171,15 @@ __global__ void __launch_bounds__(256) k_prep_coeffs(Args a) {
   int32_t* bounds = (int32_t*)(ws + (horiz ? L.hb : L.vb)) + 2 * i;
   int32_t* kk = (int32_t*)(ws + (horiz ? L.hk : L.vk)) + (int64_t)i * k;
   double ww = 0.0;
-  for (int x = 0; x < n; ++x) ww += tri((x + xmin - center + 0.5) * f.ss);
+  for (int x = 0; x < n; ++x) {
+    const double t = (x + xmin - center + 0.5) * f.ss;
+    ww += bicubic ? cubic(t) : tri(t);
+  }
   for (int x = 0; x < k; ++x) {
     int32_t q = 0;
     if (x < n) {
-      double w = tri((x + xmin - center + 0.5) * f.ss);
+      const double t = (x + xmin - center + 0.5) * f.ss;
+      double w = bicubic ? cubic(t) : tri(t);
       if (ww != 0.0) w /= ww;
       q = w < 0 ? (int32_t)(-0.5 + w * (1 << kPrecisionBits)) : (int32_t)(0.5 + w * (1 << kPrecisionBits));
     }
@@ -251,12 +289,13 @@ inline int pass_blocks(int S) {
 
 // The host query of both entries: checks, the "out" fields, the workspace layout.  `msg` holds the entry's own wording of the refusals.
 struct WorkspaceMsgs {
-  const char *arg, *sides, *resize, *window, *fits, *span;
+  const char *arg, *sides, *resize, *window, *fits, *span, *ksize;
 };
 
 template <class Desc>
-int prep_workspace(Desc* desc, int32_t B, int32_t S, int64_t src_bytes, int64_t* bytes, const WorkspaceMsgs& msg) {
-  if (!desc || !bytes || B < 1 || B > 65535 || S < 1 || S > kMaxS || src_bytes < 0) return uvc_set_error_msg(UVC_ERR_ARG, msg.arg);
+int prep_workspace(Desc* desc, int32_t B, int32_t S, int64_t src_bytes, int32_t filter, int64_t* bytes, const WorkspaceMsgs& msg) {
+  if (!desc || !bytes || B < 1 || B > 65535 || S < 1 || S > kMaxS || src_bytes < 0 || !filter_ok(filter))
+    return uvc_set_error_msg(UVC_ERR_ARG, msg.arg);
   int64_t off = 0;
   for (int32_t b = 0; b < B; ++b) {
     Desc& d = desc[b];
@@ -265,7 +304,9 @@ int prep_workspace(Desc* desc, int32_t B, int32_t S, int64_t src_bytes, int64_t*
     if (d.win_y < 0 || d.win_x < 0 || d.win_y > d.resize_h - S || d.win_x > d.resize_w - S) return uvc_set_error_msg(UVC_ERR_ARG, msg.window);
     if (!src_fits(d, src_bytes)) return uvc_set_error_msg(UVC_ERR_ARG, msg.fits);
     const int h = src_h(d), w = src_w(d);
-    const AxisFilter fh = axis_filter(w, d.resize_w), fv = axis_filter(h, d.resize_h);
+    const AxisFilter fh = axis_filter(w, d.resize_w, filter), fv = axis_filter(h, d.resize_h, filter);
+    if (!ksize_ok(fh.ksize, w, d.resize_w, filter) || !ksize_ok(fv.ksize, h, d.resize_h, filter))   // cannot happen (see ksize_ok)
+      return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, msg.ksize);
     // Image.resize: `if self.size[1] > self.size[0] * 100 and size[1] < self.size[1]` resizes vertically, then horizontally
     // (on the size of what is resized: for a crop window, the crop's, as after Image.crop)
     d.order = (h > (int64_t)w * 100 && d.resize_h < h) ? 1 : 0;
@@ -290,7 +331,8 @@ int prep_workspace(Desc* desc, int32_t B, int32_t S, int64_t src_bytes, int64_t*
 template <class Args>
 int prep_launch(const Args* a, void* stream, const char* null_msg, const char* arg_msg, const char* align_msg) {
   if (!a || !a->src || !a->desc || !a->workspace || !a->out) return uvc_set_error_msg(UVC_ERR_ARG, null_msg);
-  if (a->B < 1 || a->B > 65535 || a->S < 1 || a->S > kMaxS || (a->out_dtype != UVC_IMAGE_OUT_F32 && a->out_dtype != UVC_IMAGE_OUT_U8))
+  if (a->B < 1 || a->B > 65535 || a->S < 1 || a->S > kMaxS || (a->out_dtype != UVC_IMAGE_OUT_F32 && a->out_dtype != UVC_IMAGE_OUT_U8) ||
+      !filter_ok(a->filter))
     return uvc_set_error_msg(UVC_ERR_ARG, arg_msg);
   if (((uintptr_t)a->workspace & 15) || a->workspace_bytes < 0 || a->src_bytes < 0) return uvc_set_error_msg(UVC_ERR_ARG, align_msg);
   hipStream_t st = (hipStream_t)stream;
@@ -302,34 +344,53 @@ int prep_launch(const Args* a, void* stream, const char* null_msg, const char* a
   return UVC_OK;
 }
 
-}  // namespace
-
-extern "C" int uvc_image_prep_workspace(uvc_image_desc* desc, int32_t B, int32_t S, int64_t src_bytes, int64_t* bytes) {
-  static const WorkspaceMsgs msg = {"uvc_image_prep_workspace: bad argument (1 <= B <= 65535, 1 <= S <= 4096)",
+int image_workspace(uvc_image_desc* desc, int32_t B, int32_t S, int64_t src_bytes, int32_t filter, int64_t* bytes) {
+  static const WorkspaceMsgs msg = {"uvc_image_prep_workspace: bad argument (1 <= B <= 65535, 1 <= S <= 4096, filter bilinear or bicubic)",
                                     "uvc_image_prep_workspace: source sides must lie in [1, 65536]",
                                     "uvc_image_prep_workspace: resize sides must lie in [S, 65536]",
                                     "uvc_image_prep_workspace: the S x S window leaves the resized image",
                                     "uvc_image_prep_workspace: an image reaches past the source buffer",
-                                    "uvc_image_prep_workspace: empty span"};
-  return prep_workspace(desc, B, S, src_bytes, bytes, msg);
+                                    "uvc_image_prep_workspace: empty span",
+                                    "uvc_image_prep_workspace: tap count disagrees with its integer form"};
+  return prep_workspace(desc, B, S, src_bytes, filter, bytes, msg);
 }
 
-extern "C" int uvc_image_prep(const uvc_image_prep_args* a, void* stream) {
-  return prep_launch(a, stream, "uvc_image_prep: null pointer", "uvc_image_prep: bad B, S or out_dtype",
-                     "uvc_image_prep: workspace must be 16-byte aligned");
-}
-
-extern "C" int uvc_image_prep_crops_workspace(uvc_image_crop_desc* desc, int32_t B, int32_t S, int64_t store_bytes, int64_t* bytes) {
-  static const WorkspaceMsgs msg = {"uvc_image_prep_crops_workspace: bad argument (1 <= B <= 65535, 1 <= S <= 4096)",
+int crops_workspace(uvc_image_crop_desc* desc, int32_t B, int32_t S, int64_t store_bytes, int32_t filter, int64_t* bytes) {
+  static const WorkspaceMsgs msg = {"uvc_image_prep_crops_workspace: bad argument (1 <= B <= 65535, 1 <= S <= 4096, filter bilinear or bicubic)",
                                     "uvc_image_prep_crops_workspace: image sides must lie in [1, 65536] and the crop inside its image",
                                     "uvc_image_prep_crops_workspace: resize sides must lie in [S, 65536]",
                                     "uvc_image_prep_crops_workspace: the S x S window leaves the resized crop",
                                     "uvc_image_prep_crops_workspace: an image reaches past the store",
-                                    "uvc_image_prep_crops_workspace: empty span"};
-  return prep_workspace(desc, B, S, store_bytes, bytes, msg);
+                                    "uvc_image_prep_crops_workspace: empty span",
+                                    "uvc_image_prep_crops_workspace: tap count disagrees with its integer form"};
+  return prep_workspace(desc, B, S, store_bytes, filter, bytes, msg);
+}
+
+}  // namespace
+
+extern "C" int uvc_image_prep_workspace(uvc_image_desc* desc, int32_t B, int32_t S, int64_t src_bytes, int64_t* bytes) {
+  return image_workspace(desc, B, S, src_bytes, UVC_IMAGE_FILTER_BILINEAR, bytes);
+}
+
+extern "C" int uvc_image_prep_workspace_filter(uvc_image_desc* desc, int32_t B, int32_t S, int64_t src_bytes, int32_t filter, int64_t* bytes) {
+  return image_workspace(desc, B, S, src_bytes, filter, bytes);
+}
+
+extern "C" int uvc_image_prep(const uvc_image_prep_args* a, void* stream) {
+  return prep_launch(a, stream, "uvc_image_prep: null pointer", "uvc_image_prep: bad B, S, out_dtype or filter",
+                     "uvc_image_prep: workspace must be 16-byte aligned");
+}
+
+extern "C" int uvc_image_prep_crops_workspace(uvc_image_crop_desc* desc, int32_t B, int32_t S, int64_t store_bytes, int64_t* bytes) {
+  return crops_workspace(desc, B, S, store_bytes, UVC_IMAGE_FILTER_BILINEAR, bytes);
+}
+
+extern "C" int uvc_image_prep_crops_workspace_filter(uvc_image_crop_desc* desc, int32_t B, int32_t S, int64_t store_bytes, int32_t filter,
+                                                     int64_t* bytes) {
+  return crops_workspace(desc, B, S, store_bytes, filter, bytes);
 }
 
 extern "C" int uvc_image_prep_crops(const uvc_image_prep_crops_args* a, void* stream) {
-  return prep_launch(a, stream, "uvc_image_prep_crops: null pointer", "uvc_image_prep_crops: bad B, S or out_dtype",
+  return prep_launch(a, stream, "uvc_image_prep_crops: null pointer", "uvc_image_prep_crops: bad B, S, out_dtype or filter",
                      "uvc_image_prep_crops: workspace must be 16-byte aligned");
 }

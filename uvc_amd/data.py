@@ -2,7 +2,9 @@
 
 Decoding stays on the CPU (PIL, in threads: PIL releases the GIL while it decodes); the random resized crop is a slice of the
 decoded array, so only the crop's pixels are uploaded; resampling, flip, ToTensor and Normalize run in one ragged HIP batch
-(``uvc_image_prep``, include/uvc_data.h), bit for bit what torchvision's transforms give on the PIL image.
+(``uvc_image_prep``, include/uvc_data.h), bit for bit what torchvision's transforms give on the PIL image.  The resampling filter is
+bilinear, torchvision's default and the reference's, or bicubic (``interpolation``), what the released DeiT and T2T-ViT checkpoints
+were trained and evaluated with; ``crop_pct`` sets the eval resize by timm's rule (eval_resize_side).
 
     ImageFolder(root)            torchvision.datasets.ImageFolder indexing (sorted classes, os.walk(followlinks=True), IMG_EXTENSIONS)
     read_cifar(root, name, train) the local python-pickle CIFAR-10 / CIFAR-100 layout, nothing is downloaded -> ArrayDataset
@@ -193,6 +195,27 @@ def resize_short_side(h, w, size):
     return (new_long, new_short) if w <= h else (new_short, new_long)
 
 
+INTERPOLATIONS = ("bilinear", "bicubic")
+
+
+def eval_resize_side(S, crop_pct=None):
+    """Short side the eval transform resizes to before CenterCrop(S).  crop_pct None: the reference's S * 256 // 224 (256 at 224);
+    otherwise timm's int(math.floor(S / crop_pct)): 0.875 -> 256, 0.9 -> 248, 1.0 -> S at 224.  crop_pct must lie in (0, 1]."""
+    if crop_pct is None:
+        return S * 256 // 224
+    crop_pct = float(crop_pct)
+    if not 0.0 < crop_pct <= 1.0:                       # (nan fails both comparisons)
+        raise ValueError(f"crop_pct must lie in (0, 1], not {crop_pct}")
+    return int(math.floor(S / crop_pct))
+
+
+def _pil_filter(interpolation):
+    from PIL import Image
+    if interpolation not in INTERPOLATIONS:
+        raise ValueError(f"interpolation must be one of {INTERPOLATIONS}, not {interpolation!r}")
+    return Image.BICUBIC if interpolation == "bicubic" else Image.BILINEAR
+
+
 def center_crop_offset(h, w, S):
     """torchvision CenterCrop(S) top-left: int(round((h - S) / 2.0)), Python's round half to even."""
     return int(round((h - S) / 2.0)), int(round((w - S) / 2.0))
@@ -224,16 +247,22 @@ class DeviceLoader:
 
     train=True : RandomResizedCrop(S, scale, ratio) [+ RandomHorizontalFlip] + Normalize, DistributedSampler order (rank, world,
                  reshuffled by set_epoch), drop_last=False: the last batch is short.
-    train=False: every sample in order; eval="center": Resize(S * 256 // 224) + CenterCrop(S) (ImageNet: 256 / 224),
-                 eval="square": Resize((S, S)) (CIFAR test).
+    train=False: every sample in order; eval="center": Resize(eval_resize_side(S, crop_pct)) + CenterCrop(S) (ImageNet: 256 / 224
+                 by default), eval="square": Resize((S, S)) (CIFAR test; crop_pct does not apply).
+    interpolation: "bilinear" (default) or "bicubic", the filter of the training crop's resize and of the eval resize alike.
     A thread pool of min(num_workers, 16) threads decodes and crops into a pinned staging slot, about ``ahead`` batches ahead of
     the consumer; the pixels and descriptors go up on a side copy stream; the current stream waits on its event and runs the
     three uvc_image_prep launches into a freshly allocated x."""
 
     def __init__(self, dataset, batch_size, img_size, train=True, mean=IMAGENET_MEAN, std=IMAGENET_STD, scale=(0.08, 1.0),
-                 ratio=(3.0 / 4.0, 4.0 / 3.0), flip=True, eval="center", seed=0, rank=0, world=1, num_workers=4, device=None, ahead=2):
+                 ratio=(3.0 / 4.0, 4.0 / 3.0), flip=True, eval="center", seed=0, rank=0, world=1, num_workers=4, device=None, ahead=2,
+                 interpolation="bilinear", crop_pct=None):
+        from . import ops
         if eval not in ("center", "square"):
             raise ValueError(eval)
+        self.interpolation, self.crop_pct = interpolation, crop_pct
+        self.filter = ops.image_filter(interpolation)
+        self.eval_side = eval_resize_side(int(img_size), crop_pct)
         self.dataset, self.batch_size, self.S, self.train = dataset, int(batch_size), int(img_size), bool(train)
         self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
         self.scale, self.ratio, self.flip, self.eval = tuple(scale), tuple(ratio), bool(flip), eval
@@ -290,7 +319,7 @@ class DeviceLoader:
                 if self.eval == "square":
                     rh, rw, wy, wx = S, S, 0, 0
                 else:
-                    rh, rw = resize_short_side(h, w, S * 256 // 224)
+                    rh, rw = resize_short_side(h, w, self.eval_side)
                     wy, wx = center_crop_offset(rh, rw, S)
                 g[b, 4:8] = rh, rw, wy, wx
         return g
@@ -327,7 +356,7 @@ class DeviceLoader:
         desc["src_offset"] = offs[:-1]
         desc["src_h"], desc["src_w"] = g[:, 2], g[:, 3]
         desc["resize_h"], desc["resize_w"], desc["win_y"], desc["win_x"], desc["flip"] = g[:, 4], g[:, 5], g[:, 6], g[:, 7], g[:, 8]
-        slot.ws_bytes = ops.image_prep_workspace(desc, self.S, total)
+        slot.ws_bytes = ops.image_prep_workspace(desc, self.S, total, self.filter)
         nb = desc.nbytes
         if slot.desc is None or slot.desc.numel() < nb:
             slot.desc = torch.empty(max(nb, 64 * 512), dtype=torch.uint8).pin_memory()
@@ -372,7 +401,7 @@ class DeviceLoader:
         """With the consumer's stream current, after the upload: the three launches into x.  Returns the batch's target."""
         from . import ops
         target, src, desc = up
-        ops.image_prep(src[:max(slot.src_bytes, 1)], desc, ws, x, self.mean, self.std)
+        ops.image_prep(src[:max(slot.src_bytes, 1)], desc, ws, x, self.mean, self.std, self.filter)
         return target
 
     def __iter__(self):
@@ -420,10 +449,12 @@ class DeviceLoader:
 
 
 def host_reference_batch(dataset, indices, S, train, seed, epoch, mean, std, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip=True,
-                         eval="center"):
-    """The same batch the loader yields, built the reference's way on the host: PIL crop().resize(BILINEAR), flip, ToTensor, Normalize
-    (float32 [B, 3, S, S] on the CPU).  Tests and tools hold the device path to it."""
+                         eval="center", interpolation="bilinear", crop_pct=None):
+    """The same batch the loader yields, built the reference's way on the host: PIL crop().resize(BILINEAR or BICUBIC), flip, ToTensor,
+    Normalize (float32 [B, 3, S, S] on the CPU).  Tests and tools hold the device path to it."""
     from PIL import Image
+    resample = _pil_filter(interpolation)
+    side = eval_resize_side(S, crop_pct)
     xs = []
     u = sample_uniforms(seed, epoch, indices, RRC_DRAWS) if train else None
     for b, k in enumerate(indices):
@@ -432,14 +463,14 @@ def host_reference_batch(dataset, indices, S, train, seed, epoch, mean, std, sca
         h, w = a.shape[:2]
         if train:
             i, j, ch, cw = (int(v[0]) for v in rrc_params([h], [w], u[b:b + 1], scale, ratio))
-            im = im.crop((j, i, j + cw, i + ch)).resize((S, S), Image.BILINEAR)
+            im = im.crop((j, i, j + cw, i + ch)).resize((S, S), resample)
             if flip and u[b, 40] < 0.5:
                 im = im.transpose(Image.FLIP_LEFT_RIGHT)
         elif eval == "square":
-            im = im.resize((S, S), Image.BILINEAR)
+            im = im.resize((S, S), resample)
         else:
-            rh, rw = resize_short_side(h, w, S * 256 // 224)
-            im = im.resize((rw, rh), Image.BILINEAR)
+            rh, rw = resize_short_side(h, w, side)
+            im = im.resize((rw, rh), resample)
             y0, x0 = center_crop_offset(rh, rw, S)
             im = im.crop((x0, y0, x0 + S, y0 + S))
         t = torch.from_numpy(np.array(im, dtype=np.uint8)).permute(2, 0, 1).float().div(255)
@@ -454,6 +485,8 @@ def build_loaders(args, rank=0, world=1, splits=("train", "test")):
     A loader whose split is not in ``splits`` is None (compact eval asks for "test" alone, so --resident 1 uploads no train store).
     --packed_dir DIR reads DIR/train.uvcpack and DIR/val.uvcpack (uvc_amd/packed.py) in place of the folders or pickles; --resident 1
     returns ResidentLoaders, which keep the pixels on the device (CIFAR's in-memory arrays, or a pack).
+    --interpolation bilinear | bicubic is the resampling filter of every loader, train and test; --crop_pct P resizes ImageNet's eval
+    images to floor(img_size / P) before the centre crop (eval_resize_side; CIFAR's square eval resize ignores it).
     Sets args.data_classes to the dataset's class count: 10 / 100 for CIFAR, as in the reference, args.num_classes for ImageNet (the folder's
     class count must fit it).  The model head is args.num_classes wide, a multiple of 8 for the engine: for CIFAR it becomes 16 / 104; the
     soft targets cover the data classes and are zero on the padded logits (soft_batches)."""
@@ -462,6 +495,10 @@ def build_loaders(args, rank=0, world=1, splits=("train", "test")):
     seed = getattr(args, "seed", 0)
     packed_dir = getattr(args, "packed_dir", None)
     resident = bool(int(getattr(args, "resident", 0) or 0))
+    interpolation = getattr(args, "interpolation", None) or "bilinear"
+    crop_pct = getattr(args, "crop_pct", None)
+    _pil_filter(interpolation)
+    eval_resize_side(S, crop_pct)                       # refuses a crop_pct outside (0, 1] before a dataset is opened
     Loader = DeviceLoader
     if packed_dir or resident:
         from .packed import EXTENSION, PackedDataset, ResidentLoader
@@ -482,7 +519,7 @@ def build_loaders(args, rank=0, world=1, splits=("train", "test")):
     if args.dataset in ("cifar10", "cifar100"):
         args.data_classes = 10 if args.dataset == "cifar10" else 100
         args.num_classes = 16 if args.dataset == "cifar10" else 104
-        kw = dict(mean=CIFAR_MEAN, std=CIFAR_STD, num_workers=nw)
+        kw = dict(mean=CIFAR_MEAN, std=CIFAR_STD, num_workers=nw, interpolation=interpolation)
         train = Loader(train_ds, args.train_batch_size, S, train=True, scale=(0.05, 1.0), flip=False, seed=seed, rank=rank,
                        world=world, **kw) if "train" in splits else None
         test = Loader(test_ds, args.eval_batch_size, S, train=False, eval="square", **kw) if "test" in splits else None
@@ -492,10 +529,20 @@ def build_loaders(args, rank=0, world=1, splits=("train", "test")):
             where = f"classes in {os.path.join(packed_dir, 'train' + EXTENSION)}" if packed_dir else f"class folders under {args.data_dir}/train"
             raise ValueError(f"{n_classes} {where} but --num_classes {args.num_classes}")
         args.data_classes = args.num_classes
-        kw = dict(mean=IMAGENET_MEAN, std=IMAGENET_STD, num_workers=nw)
+        kw = dict(mean=IMAGENET_MEAN, std=IMAGENET_STD, num_workers=nw, interpolation=interpolation, crop_pct=crop_pct)
         train = Loader(train_ds, args.train_batch_size, S, train=True, seed=seed, rank=rank, world=world, **kw) if "train" in splits else None
         test = Loader(test_ds, args.eval_batch_size, S, train=False, eval="center", **kw) if "test" in splits else None
     return train, test
+
+
+def add_image_args(p):
+    """--interpolation / --crop_pct on a driver's parser (build_loaders reads them)."""
+    p.add_argument("--interpolation", choices=list(INTERPOLATIONS), default="bilinear",
+                   help="resampling filter of the training crops and the eval resize: bilinear is the reference's (torchvision's default); "
+                        "the released DeiT and T2T-ViT checkpoints were trained and evaluated with bicubic")
+    p.add_argument("--crop_pct", type=float, default=None,
+                   help="ImageNet eval: resize the short side to floor(img_size / crop_pct) before the centre crop (timm's rule; 0.875 -> 256 and "
+                        "0.9 -> 248 at 224, T2T-ViT uses 0.9); default: img_size * 256 // 224")
 
 
 def real_mixup(args):

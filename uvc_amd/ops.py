@@ -472,17 +472,32 @@ def image_desc_dtype():
     return np.dtype(L.uvc_image_desc)
 
 
-def image_prep_workspace(desc, S: int, src_bytes: int) -> int:
+IMAGE_FILTERS = {"bilinear": L.UVC_IMAGE_FILTER_BILINEAR, "bicubic": L.UVC_IMAGE_FILTER_BICUBIC}
+
+
+def image_filter(interpolation) -> int:
+    """UVC_IMAGE_FILTER_* of an interpolation name ("bilinear" | "bicubic")."""
+    if interpolation not in IMAGE_FILTERS:
+        raise ValueError(f"interpolation must be one of {sorted(IMAGE_FILTERS)}, not {interpolation!r}")
+    return IMAGE_FILTERS[interpolation]
+
+
+def image_prep_workspace(desc, S: int, src_bytes: int, filter=None) -> int:
     """Completes the host descriptors ``desc`` (numpy array of image_desc_dtype(), C-contiguous) in place and returns the workspace
-    bytes the batch needs (uvc_image_prep_workspace: host only, no device access)."""
+    bytes the batch needs (host only, no device access).  ``filter`` None: uvc_image_prep_workspace (bilinear); a UVC_IMAGE_FILTER_*
+    value: uvc_image_prep_workspace_filter, for a launch with that filter."""
     if desc.dtype != image_desc_dtype() or not desc.flags.c_contiguous:
         raise L.UvcHipError("image_prep_workspace: desc must be a C-contiguous array of image_desc_dtype()")
     out = C.c_int64(0)
-    L.check(L.lib().uvc_image_prep_workspace(desc.ctypes.data, len(desc), int(S), int(src_bytes), C.byref(out)), "uvc_image_prep_workspace")
+    if filter is None:
+        L.check(L.lib().uvc_image_prep_workspace(desc.ctypes.data, len(desc), int(S), int(src_bytes), C.byref(out)), "uvc_image_prep_workspace")
+    else:
+        L.check(L.lib().uvc_image_prep_workspace_filter(desc.ctypes.data, len(desc), int(S), int(src_bytes), int(filter), C.byref(out)),
+                "uvc_image_prep_workspace_filter")
     return int(out.value)
 
 
-def _image_prep_args(name, args_type, desc_type, src, desc_dev, workspace, out, mean, std):
+def _image_prep_args(name, args_type, desc_type, src, desc_dev, workspace, out, mean, std, filter):
     _chk(src, desc_dev, workspace, out)
     if src.dtype != torch.uint8 or desc_dev.dtype != torch.uint8 or workspace.dtype != torch.uint8:
         raise L.UvcHipError(f"{name}: src, desc and workspace are byte tensors")
@@ -497,13 +512,15 @@ def _image_prep_args(name, args_type, desc_type, src, desc_dev, workspace, out, 
     a.mean[:], a.std[:] = [float(v) for v in mean], [float(v) for v in std]
     a.B, a.S = B, S
     a.out_dtype = L.UVC_IMAGE_OUT_U8 if out.dtype == torch.uint8 else L.UVC_IMAGE_OUT_F32
+    a.filter = int(filter)
     return a
 
 
-def image_prep(src, desc_dev, workspace, out, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0)):
-    """out[B, 3, S, S] (float32: (u8 / 255 - mean) / std, or uint8) = PIL-bilinear resample of the B packed uint8 HWC images in ``src``
-    described by ``desc_dev`` (uint8 device tensor holding the descriptors image_prep_workspace completed) -- three launches."""
-    a = _image_prep_args("image_prep", L.uvc_image_prep_args, L.uvc_image_desc, src, desc_dev, workspace, out, mean, std)
+def image_prep(src, desc_dev, workspace, out, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), filter=0):
+    """out[B, 3, S, S] (float32: (u8 / 255 - mean) / std, or uint8) = PIL resample (``filter``: UVC_IMAGE_FILTER_*, 0 = bilinear) of the B
+    packed uint8 HWC images in ``src`` described by ``desc_dev`` (uint8 device tensor holding the descriptors image_prep_workspace
+    completed for the same filter; an image completed for another one is left untouched) -- three launches."""
+    a = _image_prep_args("image_prep", L.uvc_image_prep_args, L.uvc_image_desc, src, desc_dev, workspace, out, mean, std, filter)
     L.check(L.lib().uvc_image_prep(C.byref(a), L.cur_stream()), "uvc_image_prep")
     return out
 
@@ -514,20 +531,26 @@ def image_crop_desc_dtype():
     return np.dtype(L.uvc_image_crop_desc)
 
 
-def image_prep_crops_workspace(desc, S: int, store_bytes: int) -> int:
+def image_prep_crops_workspace(desc, S: int, store_bytes: int, filter=None) -> int:
     """image_prep_workspace for crop descriptors (numpy array of image_crop_desc_dtype()): every crop must lie inside its image and
-    every image inside the ``store_bytes`` of the store (uvc_image_prep_crops_workspace: host only)."""
+    every image inside the ``store_bytes`` of the store (host only).  ``filter`` None: uvc_image_prep_crops_workspace (bilinear); a
+    UVC_IMAGE_FILTER_* value: uvc_image_prep_crops_workspace_filter."""
     if desc.dtype != image_crop_desc_dtype() or not desc.flags.c_contiguous:
         raise L.UvcHipError("image_prep_crops_workspace: desc must be a C-contiguous array of image_crop_desc_dtype()")
     out = C.c_int64(0)
-    L.check(L.lib().uvc_image_prep_crops_workspace(desc.ctypes.data, len(desc), int(S), int(store_bytes), C.byref(out)),
-            "uvc_image_prep_crops_workspace")
+    if filter is None:
+        L.check(L.lib().uvc_image_prep_crops_workspace(desc.ctypes.data, len(desc), int(S), int(store_bytes), C.byref(out)),
+                "uvc_image_prep_crops_workspace")
+    else:
+        L.check(L.lib().uvc_image_prep_crops_workspace_filter(desc.ctypes.data, len(desc), int(S), int(store_bytes), int(filter), C.byref(out)),
+                "uvc_image_prep_crops_workspace_filter")
     return int(out.value)
 
 
-def image_prep_crops(store, desc_dev, workspace, out, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0)):
+def image_prep_crops(store, desc_dev, workspace, out, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), filter=0):
     """image_prep reading crop windows of ``store`` (uint8 device tensor: stored images back to back) in place: bit for bit image_prep
     on the crops copied out contiguously -- three launches."""
-    a = _image_prep_args("image_prep_crops", L.uvc_image_prep_crops_args, L.uvc_image_crop_desc, store, desc_dev, workspace, out, mean, std)
+    a = _image_prep_args("image_prep_crops", L.uvc_image_prep_crops_args, L.uvc_image_crop_desc, store, desc_dev, workspace, out, mean, std,
+                         filter)
     L.check(L.lib().uvc_image_prep_crops(C.byref(a), L.cur_stream()), "uvc_image_prep_crops")
     return out

@@ -21,7 +21,8 @@ Nothing in it is executable or pickled.
 
 ``max_side = m > 0`` stores an image whose short side exceeds m as ``Image.resize(resize_short_side(h, w, m), BILINEAR)``: training then
 draws its crops from a downscaled image, a deviation from the reference whose effect on accuracy is unmeasured.  Pack validation
-splits with ``max_side 0``: Resize(256) of a smaller stored image would upsample.
+splits with ``max_side 0``: Resize(256) of a smaller stored image would upsample.  That downscale is bilinear whatever ``interpolation``
+the loaders later resample with: the file records no filter.
 """
 from __future__ import annotations
 
@@ -314,7 +315,7 @@ class ResidentLoader(DeviceLoader):
         desc["img_h"], desc["img_w"] = hw[:, 0], hw[:, 1]
         desc["crop_y"], desc["crop_x"], desc["crop_h"], desc["crop_w"] = g[:, 0], g[:, 1], g[:, 2], g[:, 3]
         desc["resize_h"], desc["resize_w"], desc["win_y"], desc["win_x"], desc["flip"] = g[:, 4], g[:, 5], g[:, 6], g[:, 7], g[:, 8]
-        slot.ws_bytes = ops.image_prep_crops_workspace(desc, self.S, self.store_bytes)
+        slot.ws_bytes = ops.image_prep_crops_workspace(desc, self.S, self.store_bytes, self.filter)
         nd = desc.nbytes
         if slot.buf is None or slot.buf.numel() < nd + 8 * B:
             slot.buf = torch.empty(max(nd + 8 * B, 88 * 512), dtype=torch.uint8).pin_memory()
@@ -345,7 +346,7 @@ class ResidentLoader(DeviceLoader):
         from . import ops
         nd = slot.n * self._dsize
         target = self._labels.index_select(0, up[0][nd:].view(torch.int64))
-        ops.image_prep_crops(self._store, up[0][:nd], ws, x, self.mean, self.std)
+        ops.image_prep_crops(self._store, up[0][:nd], ws, x, self.mean, self.std, self.filter)
         return target
 
 

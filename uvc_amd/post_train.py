@@ -265,6 +265,8 @@ def add_stage2_flags(p, skip=()):
     add("--num_workers", type=int, default=8, help="decode threads (at most 16)")                   # post_train.py:417
     add("--packed_dir", default=None, help="DIR/train.uvcpack and DIR/val.uvcpack (python -m uvc_amd.packed pack) replace the folders or pickles under --data_dir")
     add("--resident", type=int, default=0, choices=[0, 1], help="1: upload the dataset to the GPU once and crop it there (CIFAR, or any dataset with --packed_dir); in data-parallel runs every rank holds the whole store, because the sampler hands any image to any rank")
+    from .data import add_image_args
+    add_image_args(p)
     # Stage-2 Mixup / CutMix and smoothing (post_train.py:502,539-550): applied on the real-data path only
     add("--smoothing", type=float, default=0.1)
     add("--mixup", type=float, default=0.8); add("--cutmix", type=float, default=1.0)
