@@ -185,12 +185,23 @@ def test_flags_reach_the_loaders_through_build_loaders(driver, tmp_path, monkeyp
         assert (train.kw["interpolation"], train.kw["crop_pct"]) == want == (test.kw["interpolation"], test.kw["crop_pct"])
 
 
-def test_compact_eval_copies_the_flags_to_the_loader_namespace():
-    """compact eval builds its loader from a fresh namespace: the two flags are among the names it copies over."""
-    import inspect
+def test_compact_eval_hands_the_flags_to_build_loaders(monkeypatch):
+    """compact eval builds its loader from its own parsed namespace, at the export's image size and classes: the two flags reach
+    build_loaders on it."""
     from uvc_amd import compact
-    src = inspect.getsource(compact.main)
-    assert '"interpolation"' in src and '"crop_pct"' in src
+    seen = {}
+
+    def spy(args, **kw):
+        seen.update(vars(args), splits=kw.get("splits"))
+        raise KeyboardInterrupt                                  # the loader itself is test_flags_reach_the_loaders_through_build_loaders' matter
+
+    monkeypatch.setattr(compact, "load_compact", lambda path: dict(cfg=dict(img_size=96, num_classes=24)))
+    monkeypatch.setattr(compact, "CompactVisionTransformer", lambda *a, **k: None)
+    monkeypatch.setattr(D, "build_loaders", spy)
+    with pytest.raises(KeyboardInterrupt):
+        compact.main(["eval", "--compact", "c.pt", "--synthetic", "0", "--interpolation", "bicubic", "--crop_pct", "0.9", "--eval_batch_size", "4"])
+    assert (seen["interpolation"], seen["crop_pct"], seen["eval_batch_size"], seen["splits"]) == ("bicubic", 0.9, 4, ("test",))
+    assert (seen["img_size"], seen["num_classes"]) == (96, 24)
 
 
 # ---------------------------------------------------------------------------------------------------------------- host reference

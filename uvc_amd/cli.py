@@ -19,11 +19,12 @@ import json
 import os
 import time
 
-import numpy as np
 import torch
 import torch.distributed as dist
 
+from .driver import add_data_flags, add_mixup_flags, add_teacher_flags, init_distributed, seeded_mixup, train_loaders
 from .joint_train import count_mask, save_model
+from .mixup import build_mixup  # noqa: F401  (tools import it from here)
 from .stage1 import CONFIGS, Stage1Trainer
 from .uvc_utils import prune_w_mask
 
@@ -31,12 +32,8 @@ from .uvc_utils import prune_w_mask
 def build_parser():
     p = argparse.ArgumentParser()
     a = p.add_argument
-    a("--name", default="debug"); a("--dataset", choices=["cifar10", "cifar100", "imagenet"], default="imagenet")
-    a("--data_dir", default="/ssd1/shixing/imagenet2012"); a("--num_workers", default=4, type=int)
-    a("--packed_dir", default=None, help="DIR/train.uvcpack and DIR/val.uvcpack (python -m uvc_amd.packed pack) replace the folders or pickles under --data_dir")
-    a("--resident", type=int, default=0, choices=[0, 1], help="1: upload the dataset to the GPU once and crop it there (CIFAR, or any dataset with --packed_dir); in data-parallel runs every rank holds the whole store, because the sampler hands any image to any rank")
-    from .data import add_image_args
-    add_image_args(p)
+    a("--name", default="debug")
+    add_data_flags(p, data_dir="/ssd1/shixing/imagenet2012", num_workers=4)
     a("--model_type", choices=list(CONFIGS) + ["t2t_vit_14", "custom", "custom_t2t"], default="deit_tiny_patch16_224")
     a("--model_path", default=None); a("--pretrained_dir", type=str, default="../ViT-pytorch/pretrain/ViT-B_16.npz"); a("--pretrained", type=int, default=1)
     a("--output_dir", default="../result/output/uvc_train", type=str); a("--img_size", default=224, type=int)
@@ -54,10 +51,8 @@ def build_parser():
     a("--rlr", default=0.02, type=float); a("--glr", default=1e-3, type=float); a("--log_interval", default=2000, type=int)
     a("--save_budgets", default="0.6, 0.5, 0.4"); a("--budget", default=0.5); a("--sl2wd", default=0.0, type=float)
     a("--verbose", default=True, action="store_true")
-    a("--mixup", type=float, default=0.8); a("--cutmix", type=float, default=1.0)
-    a("--cutmix-minmax", type=float, nargs="+", default=None); a("--mixup-prob", type=float, default=0.8)
-    a("--mixup-switch-prob", type=float, default=0.5); a("--mixup-mode", type=str, default="batch")
-    a("--teacher-model", default=None, type=str); a("--teacher-path", type=str, default=None)
+    add_mixup_flags(p)
+    add_teacher_flags(p, default=None)
     a("--distillation-type", default="hard", choices=["none", "soft", "hard"], type=str)
     a("--distillation-alpha", default=0.5, type=float); a("--distillation-tau", default=1.0, type=float)
     a("--smoothing", type=float, default=0.1)
@@ -88,16 +83,6 @@ def build_parser():
     a("--teacher_cfg", type=str, default=None, help="with --teacher-model custom / custom_t2t: the teacher's JSON dims (its own size)")
     a("--eval_steps", type=int, default=2, help="synthetic validation batches per epoch (valid(), joint_train.py:199-246)")
     return p
-
-
-def build_mixup(args):
-    """joint_train.py:922-933."""
-    from .mixup import Mixup
-    mixup_active = args.mixup > 0 or args.cutmix > 0. or args.cutmix_minmax is not None
-    if not mixup_active:
-        return None
-    return Mixup(mixup_alpha=args.mixup, cutmix_alpha=args.cutmix, cutmix_minmax=args.cutmix_minmax, prob=args.mixup_prob,
-                 switch_prob=args.mixup_switch_prob, mode=args.mixup_mode, label_smoothing=args.smoothing, num_classes=args.num_classes)
 
 
 def iterate_batches(args, device, rank, mixup_fn=None, epoch=0):
@@ -146,27 +131,13 @@ def main(argv=None):
         if not args.model_cfg:
             raise SystemExit("--model_type custom needs --model_cfg '<json>'")
         args.model_cfg = json.loads(args.model_cfg)
-    world = int(os.environ.get("WORLD_SIZE", 1))
-    rank = int(os.environ.get("RANK", 0))
-    torch.cuda.set_device(args.local_rank)
+    rank, _, world = init_distributed(args.local_rank)
     device = torch.device("cuda", args.local_rank)
-    if world > 1:
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        dist.init_process_group(backend="nccl")
     torch.manual_seed(args.seed)                      # same seed on every rank (joint_train.py:191-196,914)
     args.train_batch_size = args.train_batch_size // args.gradient_accumulation_steps
-    train_loader = test_loader = None
-    if not args.synthetic:                            # get_loader (joint_train.py:272); t_total = len(train_loader) * num_epochs (:274)
-        from .data import build_loaders
-        train_loader, test_loader = build_loaders(args, rank=rank, world=world)
-        args.steps_per_epoch = train_loader.train_steps()
+    train_loader, test_loader = train_loaders(args, rank, world)    # t_total = len(train_loader) * num_epochs (:274)
     tr = Stage1Trainer(args, device=device, distributed=world > 1)
-    np.random.seed(args.seed)                         # Mixup draws from numpy's global RNG (set_seed, joint_train.py:191-196)
-    if train_loader is None:
-        mixup_fn = build_mixup(args)
-    else:                                             # over the dataset's classes; a padded head's extra columns get zero targets
-        from .data import real_mixup
-        mixup_fn = real_mixup(args)
+    mixup_fn = seeded_mixup(args, real=train_loader is not None)
     if rank == 0:
         print(f"mixup active: {mixup_fn is not None}")
     out_dir = os.path.join(args.output_dir, args.name)

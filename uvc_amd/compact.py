@@ -499,13 +499,8 @@ def _parser():
     e.add_argument("--eval_batch_size", type=int, default=64)
     e.add_argument("--eval_steps", type=int, default=2, help="synthetic validation batches")
     e.add_argument("--synthetic", type=int, default=1, help="synthetic batches; 0 = read --dataset under --data_dir")
-    e.add_argument("--dataset", choices=["cifar10", "cifar100", "imagenet"], default="imagenet")
-    e.add_argument("--data_dir", default="/ssd1/xinyu/dataset/imagenet2012")
-    e.add_argument("--num_workers", type=int, default=8)
-    e.add_argument("--packed_dir", default=None, help="DIR/train.uvcpack and DIR/val.uvcpack (python -m uvc_amd.packed pack) replace the folders or pickles under --data_dir")
-    e.add_argument("--resident", type=int, default=0, choices=[0, 1], help="1: upload the dataset to the GPU once and crop it there (CIFAR, or any dataset with --packed_dir); in data-parallel runs every rank holds the whole store, because the sampler hands any image to any rank")
-    from .data import add_image_args
-    add_image_args(e)
+    from .driver import add_data_flags
+    add_data_flags(e, data_dir="/ssd1/xinyu/dataset/imagenet2012", num_workers=8)
     # fine-tune a compact file at its kept widths: Stage 2's training, distillation, teacher, data and Mixup flags (post_train's names and defaults)
     from .post_train import add_stage2_flags
     f = sub.add_parser("finetune")
@@ -518,19 +513,14 @@ def _parser():
 def _dense_model(args, dev):
     """The Stage-2 eval model of post_train.eval_model, with patch-gating mode 1 when asked for."""
     from .checkpoints import load_pretrained
-    from .model_distilled import DistilledVisionTransformer
+    from .joint_train import register_masks
     from .pos_embed import match_pos_embed
-    from .post_train import register_masks
-    from .stage1 import CONFIGS
+    from .trainer import build_model
     if "t2t" in args.model_type:
         raise NotImplementedError("compact export of T2T-ViT models (their tokens-to-token front end) is not supported")
     if not args.checkpoint_dir and not args.model_path:
         raise SystemExit("need --checkpoint_dir or --model_path")
-    cfg = dict(CONFIGS[args.model_type]) if args.model_type in CONFIGS else dict(json.loads(args.model_cfg))
-    model = DistilledVisionTransformer(enable_dist=args.enable_deit, enable_patch_gating=args.enable_patch_gating, patch_hard=bool(args.patch_hard),
-                                       gumbel_hard=True, patch_size=cfg["patch_size"], embed_dim=cfg["embed_dim"], depth=cfg["depth"],
-                                       num_heads=cfg["num_heads"], mlp_ratio=cfg.get("mlp_ratio", 4), img_size=args.img_size,
-                                       num_classes=args.num_classes, precision=args.precision, device=dev)
+    model = build_model(args, dev, enable_patch_gating=args.enable_patch_gating, patch_hard=bool(args.patch_hard), gumbel_hard=True)
     register_masks(model)
     if args.checkpoint_dir:
         model.load_state_dict(match_pos_embed(torch.load(args.checkpoint_dir, map_location="cpu"), model))
@@ -549,55 +539,23 @@ def _report(export, B=1):
 
 
 def finetune(args, dev):
-    """``finetune``: Stage 2's epoch loop (post_train.py:326-403) on a compact file; the model with the best validation top-1 is saved."""
-    import numpy as np
+    """``finetune``: Stage 2's epoch loop (post_train.post_training) on a compact file; the model with the best validation top-1 is saved."""
     from .compact_train import CompactTrainer
-    from .post_train import loader_valid_fn, synthetic_valid_fn
-    from .stage1 import Stage1Trainer
+    from .driver import seeded_mixup, train_loaders
+    from .post_train import post_training, train_batches, valid_fn_of
     export = load_compact(args.compact)
     c = export["cfg"]
     args.img_size, args.num_classes, args.enable_deit = c["img_size"], c["num_classes"], c["enable_dist"]
-    train_loader = test_loader = None
-    if not args.synthetic:
-        from .data import build_loaders, real_mixup, soft_batches
-        train_loader, test_loader = build_loaders(args, rank=0, world=1)
-        args.steps_per_epoch = train_loader.train_steps()
-        np.random.seed(args.seed)                         # Mixup draws from numpy's global RNG
-        mixup_fn = real_mixup(args)
+    train_loader, test_loader = train_loaders(args, rank=0, world=1)
+    mixup_fn = seeded_mixup(args, real=True) if train_loader is not None else None
     tr = CompactTrainer(args, export, device=dev)
-    g = torch.Generator(device=dev).manual_seed(args.seed)
-
-    def batches(epoch):
-        if train_loader is not None:
-            yield from soft_batches(train_loader, epoch, mixup_fn, args.smoothing, args.data_classes, args.num_classes)
-            return
-        for _ in range(args.steps):
-            x = torch.randn(args.train_batch_size, 3, args.img_size, args.img_size, device=dev, generator=g)
-            yield x, torch.softmax(torch.randn(args.train_batch_size, args.num_classes, device=dev, generator=g), -1)
-
-    def trimmed(epoch):
-        for x, y in batches(epoch):
-            yield (x[:-1], y[:-1]) if len(x) % 2 else (x, y)                                       # post_train.py:348-350
-
-    valid_fn = None
-    if args.eval_steps > 0:
-        valid_fn = loader_valid_fn(test_loader) if test_loader is not None else synthetic_valid_fn(args, dev)
+    valid_fn = valid_fn_of(args, dev, test_loader)
     before = valid_fn(tr.model) if valid_fn else None
-    best = 0.0
-    for epoch in range(args.epochs):
-        tr.begin_epoch(epoch)
-        last = None
-        for (x, y), next_x in Stage1Trainer.lookahead(trimmed(epoch)):
-            last = tr.step(x, y, next_x=next_x)
-        if last is not None:
-            print(f"[compact finetune] epoch {epoch} steps {tr.global_step} lr {tr.scheduler.get_epoch_values(epoch)[0]:.6g} loss {float(last['loss']):.4f}")
-        if valid_fn is not None:
-            acc = valid_fn(tr.model)
-            if best < acc:                                                                          # save-best (:393-399)
-                torch.save(tr.export(), args.output)
-                best = acc
+    save = lambda tr: torch.save(tr.export(), args.output)
+    best = post_training(tr, train_batches(args, dev, train_loader, mixup_fn, args.seed), epochs=args.epochs, valid_fn=valid_fn,
+                         save_best=save, prefix="[compact finetune]")
     if valid_fn is None:
-        torch.save(tr.export(), args.output)
+        save(tr)
     print(json.dumps(dict(output=args.output, top1_before=before, top1_after=best if valid_fn else None, epochs=args.epochs, steps=tr.global_step,
                           **_report(export))))
     return tr
@@ -618,17 +576,14 @@ def main(argv=None):
         torch.save(export, args.output)
         print(json.dumps(dict(output=args.output, **_report(export))))
         return export
-    from .post_train import default_args, loader_valid_fn, synthetic_valid_fn
+    from .post_train import loader_valid_fn, synthetic_valid_fn
     cm = CompactVisionTransformer(export, precision=args.precision, device=dev)
-    vargs = default_args(img_size=export["cfg"]["img_size"], num_classes=export["cfg"]["num_classes"], seed=args.seed)
-    for k in ("eval_batch_size", "eval_steps", "dataset", "data_dir", "num_workers", "packed_dir", "resident", "interpolation", "crop_pct"):
-        setattr(vargs, k, getattr(args, k))
+    args.img_size, args.num_classes = export["cfg"]["img_size"], export["cfg"]["num_classes"]
     if args.synthetic:
-        acc = synthetic_valid_fn(vargs, dev)(cm)
+        acc = synthetic_valid_fn(args, dev)(cm)
     else:
-        from .data import build_loaders
-        vargs.train_batch_size = args.eval_batch_size
-        _, test_loader = build_loaders(vargs, rank=0, world=1, splits=("test",))
+        from . import data
+        _, test_loader = data.build_loaders(args, rank=0, world=1, splits=("test",))
         acc = loader_valid_fn(test_loader)(cm)
     print(json.dumps(dict(top1=acc, **_report(export))))
     return acc

@@ -24,6 +24,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import compact as CP
+from .trainer import _Trainer
 
 MAX_TOKENS = 256
 _bind = CP._bind
@@ -236,9 +237,10 @@ def _refuse(args, precision):
         raise NotImplementedError("compact models train in 'bf16' or 'fp32' (the float32 residual rows of 'bf16_f32resid' are a dense-model mode)")
 
 
-class CompactTrainer:
+class CompactTrainer(_Trainer):
     """``Stage2Trainer``'s surface on a compact model: ``begin_epoch``, ``step(x, y, next_x=None)`` -> loss, outputs, gnorm;
     ``state_dict`` / ``load_state_dict`` resume bit for bit."""
+    STATE_FORMAT, NOT_A_STATE = "uvc_amd.compact_train.v1", "not a uvc_amd compact training state"
 
     def __init__(self, args: Namespace, export: dict, device="cuda", teacher_state=None):
         from .losses import DistillationLoss, SoftTargetCrossEntropy
@@ -264,46 +266,12 @@ class CompactTrainer:
         self.optimizer = create_optimizer(args, self.model)
         self.scheduler, self.num_epochs = create_scheduler(args, self.optimizer)
         self.model.train()
-        self.global_step = 0
-        self.epoch = 0
+        self._start()
 
     def begin_epoch(self, epoch: int):
         self.epoch = epoch
         self.model.train()
         self.scheduler.step(epoch)
 
-    def step(self, x, y, zero_grad=True, next_x=None):
-        from .losses import unit_gradient
-        from .optim import clip_grad_norm_
-        a = self.args
-        overlap = bool(getattr(a, "overlap_teacher", 1))
-        if overlap and not self.criterion.has_prefetch(x):
-            self.criterion.prefetch(x)
-        outputs, _ = self.model(x)
-        loss = self.criterion(x, outputs, y)
-        loss.backward(unit_gradient(loss.device))
-        if overlap and next_x is not None:
-            self.criterion.prefetch(next_x)
-        gnorm = clip_grad_norm_(self.model, a.max_grad_norm)
-        self.optimizer.step()
-        self.global_step += 1
-        if zero_grad:
-            self.optimizer.zero_grad()
-        return dict(loss=loss.detach(), outputs=outputs, gnorm=gnorm, stepped=True)
-
     def export(self) -> dict:
         return self.model.export()
-
-    def state_dict(self):
-        o = self.optimizer
-        return dict(format="uvc_amd.compact_train.v1", model=self.model.state_dict(),
-                    adamw=dict(exp_avg=o.exp_avg.clone(), exp_avg_sq=o.exp_avg_sq.clone(), steps=dict(o.steps), lr=o.param_groups[0]["lr"]),
-                    progress=dict(global_step=self.global_step, epoch=self.epoch))
-
-    def load_state_dict(self, sd):
-        if sd.get("format") != "uvc_amd.compact_train.v1":
-            raise ValueError("not a uvc_amd compact training state")
-        self.model.load_state_dict(sd["model"])
-        a, o = sd["adamw"], self.optimizer
-        o.exp_avg.copy_(a["exp_avg"]); o.exp_avg_sq.copy_(a["exp_avg_sq"]); o.steps = dict(a["steps"]); o.param_groups[0]["lr"] = a["lr"]
-        self.global_step, self.epoch = int(sd["progress"]["global_step"]), int(sd["progress"]["epoch"])

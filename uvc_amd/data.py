@@ -548,7 +548,7 @@ def add_image_args(p):
 def real_mixup(args):
     """The reference's Mixup / CutMix (or None) over the dataset's classes (args.data_classes, set by build_loaders)."""
     import argparse
-    from .cli import build_mixup
+    from .mixup import build_mixup
     return build_mixup(argparse.Namespace(**{**vars(args), "num_classes": args.data_classes}))
 
 

@@ -117,3 +117,12 @@ class Mixup:
                                          float(np.float32(1.0 - lam)), float(np.float32(on_value)), float(np.float32(off_value)),
                                          L.cur_stream()), "uvc_mixup_target")
         return x, y
+
+
+def build_mixup(args):
+    """joint_train.py:922-933: the Mixup / CutMix of a run's flags, or None when they switch it off."""
+    mixup_active = args.mixup > 0 or args.cutmix > 0. or args.cutmix_minmax is not None
+    if not mixup_active:
+        return None
+    return Mixup(mixup_alpha=args.mixup, cutmix_alpha=args.cutmix, cutmix_minmax=args.cutmix_minmax, prob=args.mixup_prob,
+                 switch_prob=args.mixup_switch_prob, mode=args.mixup_mode, label_smoothing=args.smoothing, num_classes=args.num_classes)

@@ -5,35 +5,20 @@ build_minimax_model / uvc_optimizer, DDP) exactly in the reference's order.
 """
 from __future__ import annotations
 
-import json
 from argparse import Namespace
-from typing import Optional
 
 import torch
 
-from . import _lib as L
 from .checkpoints import load_pretrained
 from .ddp import DistributedDataParallel
 from .joint_train import count_mask, get_uvc_layers, register_masks
-from .losses import DistillationLoss, SoftTargetCrossEntropy, unit_gradient
-from .model_distilled import DistilledVisionTransformer
-from .optim import FusedAdamW, clip_grad_norm_
+from .losses import DistillationLoss, SoftTargetCrossEntropy
+from .optim import FusedAdamW
 from .pos_embed import match_pos_embed
 from .scheduler import PresetLRScheduler, WarmupCosineSchedule, WarmupLinearSchedule
+from .trainer import CONFIGS, T2T_CONFIGS, _Trainer, adamw_state, build_model, load_adamw_state, model_config, model_kwargs  # noqa: F401  (the model tables are read from here too)
 from .uvc_optimizer import build_minimax_model, uvc_optimizer
 from .uvc_utils import prune_w_mask
-
-# models/configs.py:112-165 -- dims of the DeiT family the reference instantiates
-CONFIGS = {
-    "deit_tiny_patch16_224": dict(patch_size=16, embed_dim=192, depth=12, num_heads=3),
-    "deit_small_patch16_224": dict(patch_size=16, embed_dim=384, depth=12, num_heads=6),
-    "deit_base_patch16_224": dict(patch_size=16, embed_dim=768, depth=12, num_heads=12),
-}
-
-
-# T2TViT/models/t2t_vit.py:244-249 (models/configs.py:159-165); BASELINE config 5
-T2T_CONFIGS = {"t2t_vit_14": dict(embed_dim=384, depth=14, num_heads=6, mlp_ratio=3.0)}
-
 
 def default_args(**over) -> Namespace:
     """The argparse defaults of joint_train.py:684-879 overlaid with the README command
@@ -49,28 +34,6 @@ def default_args(**over) -> Namespace:
              warmup_reset=0, local_rank=-1, steps_per_epoch=5005, precision="bf16", output_dir="output", name="debug")
     a.update(over)
     return Namespace(**a)
-
-
-def model_config(name, custom_cfg=None):
-    """(is_t2t, dims) of a --model_type / --teacher-model: its CONFIGS / T2T_CONFIGS entry, else ``custom_cfg`` (custom, custom_t2t:
-    a dict or its JSON)."""
-    t2t = "t2t" in name
-    table = T2T_CONFIGS if t2t else CONFIGS
-    if name in table:
-        return t2t, dict(table[name])
-    if not custom_cfg:
-        raise ValueError(f"model type {name!r} is not in this engine's configs; custom / custom_t2t take their dims as JSON")
-    return t2t, dict(json.loads(custom_cfg) if isinstance(custom_cfg, str) else custom_cfg)
-
-
-def model_kwargs(t2t, cfg, args, device):
-    """Constructor keywords of DistilledVisionTransformer / T2T_ViT for the dims ``cfg`` at the run's img_size, classes and precision."""
-    if t2t:
-        return dict(embed_dim=cfg["embed_dim"], depth=cfg["depth"], num_heads=cfg["num_heads"], mlp_ratio=cfg.get("mlp_ratio", 3.0),
-                    img_size=args.img_size, num_classes=args.num_classes, precision=args.precision, device=device)
-    return dict(patch_size=cfg["patch_size"], embed_dim=cfg["embed_dim"], depth=cfg["depth"], num_heads=cfg["num_heads"],
-                mlp_ratio=cfg.get("mlp_ratio", 4), qkv_bias=True, drop_rate=0, img_size=args.img_size,
-                num_classes=args.num_classes, precision=args.precision, device=device)
 
 
 def build_teacher(args, device, state=None, verbose=True):
@@ -93,12 +56,7 @@ def build_teacher(args, device, state=None, verbose=True):
                          f"the distillation loss needs both models' logits for the same images")
     if state is None and path is None and (t2t, cfg) != student:
         raise ValueError(f"teacher {name} differs from the student ({args.model_type}) and has no weights: pass --teacher-path")
-    kw = model_kwargs(t2t, cfg, args, device)
-    if t2t:
-        from .t2t_vit import T2T_ViT
-        teacher = T2T_ViT(**kw)                                                                     # joint_train.py:963-964
-    else:
-        teacher = DistilledVisionTransformer(enable_dist=args.enable_deit, **kw)                    # :957-958
+    teacher = build_model(args, device, name=name, cfg=cfg)                                         # joint_train.py:957-964
     if state is not None:
         teacher.load_state_dict(match_pos_embed(state, teacher), strict=False)
         path = None
@@ -124,7 +82,7 @@ def _bits_fingerprint(t, chunk=1 << 22):
     return acc
 
 
-class Stage1Trainer:
+class Stage1Trainer(_Trainer):
     def __init__(self, args: Namespace, device="cuda", student_state=None, teacher_state=None, distributed=False):
         if not args.enable_pruning:
             raise TypeError("enable_pruning=0 raises in the reference (uvc_optimizer_gating signature, SURVEY.md Q7)")
@@ -133,18 +91,12 @@ class Stage1Trainer:
         args.head_size = cfg["embed_dim"] // cfg["num_heads"]              # joint_train.py:883-885
         args.num_heads = cfg["num_heads"]
         args.budget = float(args.budget)
-        if t2t:
-            # The reference builds `t2t_vit_14()` with default flags and then calls it as model(x, tau, ratio), which raises
-            # (SURVEY Q8).  Defined here: the same model with DeiT's gate flags (block gating as written at t2t_vit.py:181-189).
-            from .t2t_vit import T2T_ViT
-            if args.enable_deit or args.enable_patch_gating == 1:
-                raise NotImplementedError("T2T-ViT has no distillation token and no patch-gating mode 1 (t2t_vit.py:168-200); "
-                                          "enable_patch_gating=2 is defined in uvc_amd/t2t_vit.py")
-            model = T2T_ViT(gumbel_hard=False, enable_patch_gating=args.enable_patch_gating, **model_kwargs(t2t, cfg, args, device))
-        else:
-            model = DistilledVisionTransformer(enable_dist=args.enable_deit, gumbel_hard=False,
-                                               enable_patch_gating=args.enable_patch_gating,
-                                               **model_kwargs(t2t, cfg, args, device))                   # :135-140
+        # The reference builds `t2t_vit_14()` with default flags and then calls it as model(x, tau, ratio), which raises
+        # (SURVEY Q8).  Defined here: the same model with DeiT's gate flags (block gating as written at t2t_vit.py:181-189).
+        if t2t and (args.enable_deit or args.enable_patch_gating == 1):
+            raise NotImplementedError("T2T-ViT has no distillation token and no patch-gating mode 1 (t2t_vit.py:168-200); "
+                                      "enable_patch_gating=2 is defined in uvc_amd/t2t_vit.py")
+        model = build_model(args, device, gumbel_hard=False, enable_patch_gating=args.enable_patch_gating)      # :135-140
         verbose = getattr(args, "local_rank", -1) in (-1, 0)
         if student_state is not None:
             model.load_state_dict(match_pos_embed(student_state, model), strict=False)
@@ -176,16 +128,12 @@ class Stage1Trainer:
             model, names, self.uvc_layers, ldict, args, flops_list)                                 # :1014
         prune_w_mask(self.minimax)                                                                  # :1026
         # train(): optimiser, schedule, DDP (:271-295)
-        self.accum = max(1, int(getattr(args, "gradient_accumulation_steps", 1)))       # :403-426
-        model.grad_accumulate = self.accum > 1
-        self._micro = 0
+        self._start(accum=max(1, int(getattr(args, "gradient_accumulation_steps", 1))))             # :403-426
         self._build_optimizer()
         self.zlr_scheduler = PresetLRScheduler(getattr(args, "zlr_schedule", {}))
         self.ddp = DistributedDataParallel(model, message_size=250000000, gradient_predivide_factor=1.0,
                                            dual_scalar=self.minimax.z) if distributed else None
         model.train()
-        self.global_step = 0
-        self.epoch = 0
         self.gating_grad_list = []
         # Gumbel noise of the gates / resource samples / patch top-k: keyed by (seed, optimiser step, call number), see ops.KeyedExpSource
         from .ops import KeyedExpSource
@@ -237,59 +185,26 @@ class Stage1Trainer:
             return 0.1 + (10 - 0.1) * self.global_step / self.t_total
         return -1
 
-    # -- one loader iteration (joint_train.py:395-450), x / y already mixed.  With --gradient_accumulation_steps k only every
-    # k-th call is an optimiser step (:417-426): the others return after the backward, which ADDS into the flat gradient
-    # buffer (model.grad_accumulate), and their result carries `stepped=False`.
-    def step(self, x, y, tau=None, zero_grad=True, next_x=None):
-        """One training step on the batch (x, y).  ``next_x`` (optional): the NEXT step's input batch, if the caller already holds it (a prefetching loader does;
-        ``lookahead`` below wraps one): the frozen teacher's forward for it is started on the side stream as soon as this step's backward is enqueued, so it runs
-        under the optimizer / UVC tail of small launches, where the chip is otherwise nearly idle, instead of in front of the next step's student forward (the two
-        forwards are whole-chip kernels that alternate).  Results do not depend on it: the next step picks the forward up only for that very tensor."""
-        a = self.args
+    # -- the hooks of _Trainer.step, one loader iteration (joint_train.py:395-450).  With --gradient_accumulation_steps k only every
+    # k-th call is an optimiser step (:417-426).
+    def _before_forward(self):
         if self._micro % self.accum == 0:
             self.noise.begin_step(self.global_step, resume_window=getattr(self, "_window_carried", False))
             self._window_carried = False
-        overlap = bool(getattr(a, "overlap_teacher", 1))
-        if overlap and not self.criterion.has_prefetch(x):
-            self.criterion.prefetch(x)              # teacher forward on a side stream, under the student forward
-        outputs, _ = self.model(x, self.get_tau() if tau is None else tau, a.patch_ratio)
-        loss = self.criterion(x, outputs, y)
-        if self.accum > 1:
-            loss = loss / self.accum                                                                # :413-414
-        loss.backward(unit_gradient(loss.device))       # d(loss) = 1 without a ones_like fill or a multiply by it (losses.unit_gradient)
-        if overlap and next_x is not None:
-            # (enqueued behind the LOSS instead, the teacher's whole-chip kernels alternate with the backward's: 11.28 against 11.14 ms, profiles/r5zz_ab_next_teacher_at.txt)
-            self.criterion.prefetch(next_x)
-        self._micro += 1
-        if self._micro % self.accum != 0:                                                           # :417
-            return dict(loss=loss.detach() * self.accum, outputs=outputs, stepped=False)
-        gnorm = clip_grad_norm_(self.model, a.max_grad_norm)
-        self.optimizer.step()
+
+    def _forward(self, x, tau):
+        return self.model(x, self.get_tau() if tau is None else tau, self.args.patch_ratio)
+
+    def _after_optimizer_step(self):
+        a = self.args
         self.scheduler.step()
-        self.global_step += 1
         if not self.minimax.model.enable_warmup:
             self.zlr_scheduler(self.dual_opt, self.epoch, "zlr")
         self.minimax.update_gating()
         cur, s, r, g, self.gating_grad_list = uvc_optimizer(
             self.optimizer, self.minimax, self.s_opt, self.r_opt, self.g_opt, self.dual_opt, a, {"global_step": self.global_step},
             [], self.flops_list, a.z_grad_clip, self.global_step, a.gating_interval, self.gating_grad_list)
-        if zero_grad:
-            self.optimizer.zero_grad()
-        return dict(loss=loss.detach() * self.accum if self.accum > 1 else loss.detach(), outputs=outputs, gnorm=gnorm, cur=cur, s=s, r=r, g=g,
-                    stepped=True)
-
-    @staticmethod
-    def lookahead(batches):
-        """(x, y) batches -> ((x, y), next_x or None): what ``step(..., next_x=)`` wants, one batch read ahead."""
-        it = iter(batches)
-        try:
-            cur = next(it)
-        except StopIteration:
-            return
-        for nxt in it:
-            yield cur, nxt[0]
-            cur = nxt
-        yield cur, None
+        return dict(cur=cur, s=s, r=r, g=g)
 
     def check_replicas(self):
         """Data-parallel invariant: every rank holds bit-identical parameters and primal / dual state (the reference assumes it and
@@ -346,8 +261,7 @@ class Stage1Trainer:
                      gate_momentum=mm._gate_momentum.clone(), gate_gsum=mm._gate_gsum.clone(), gate_counters=mm._gate_counters.clone(),
                      gating_list_len=mm.gating_list_len, eps=float(self.model.eps),
                      patch_gating=None if mm.patch_gating is None else mm.patch_gating.data.clone()),
-            adamw=dict(exp_avg=opt.exp_avg.clone(), exp_avg_sq=opt.exp_avg_sq.clone(), steps=dict(opt.steps),
-                       lr=opt.param_groups[0]["lr"]),
+            adamw=adamw_state(opt),
             scheduler=self.scheduler.state_dict(),
             lrs=dict(s=self.s_opt.param_groups[0]["lr"], r=self.r_opt.param_groups[0]["lr"],
                      g=None if self.g_opt is None else self.g_opt.param_groups[0]["lr"],
@@ -390,10 +304,8 @@ class Stage1Trainer:
         self.model.eps = float(u["eps"])
         if u.get("patch_gating") is not None and mm.patch_gating is not None:
             mm.patch_gating.data.copy_(u["patch_gating"])
-        a = sd["adamw"]
-        opt.exp_avg.copy_(a["exp_avg"]); opt.exp_avg_sq.copy_(a["exp_avg_sq"]); opt.steps = dict(a["steps"])
         self.scheduler.load_state_dict(sd["scheduler"])
-        opt.param_groups[0]["lr"] = a["lr"]
+        load_adamw_state(opt, sd["adamw"])
         l = sd["lrs"]
         self.s_opt.param_groups[0]["lr"] = l["s"]; self.r_opt.param_groups[0]["lr"] = l["r"]
         if self.g_opt is not None and l["g"] is not None:
