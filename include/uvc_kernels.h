@@ -257,8 +257,12 @@ int uvc_mlp_fused_fwd(const uvc_mlp_args* args, void* stream);
 /* DistillationLoss over SoftTargetCrossEntropy (UVC/utils/losses.py:25-65, joint_train.py:940):
  * loss = (1-alpha) * mean_b sum_c -y log_softmax(o) + alpha * KL(softmax(t/T) || softmax(o_kd/T)) * T^2 / (B*C)   (kind 1, 'soft')
  *      = (1-alpha) * base + alpha * mean_b CE(o_kd, argmax_c teacher)                                            (kind 2, 'hard', :61-62)
- * All float32 [B,C].  Writes loss[0] and the gradients d_o, d_okd (d_okd may alias d_o when
- * o_kd == o, i.e. enable_deit = 0: the two contributions are summed). */
+ * All float32 [B,C].  Writes loss[0] and the gradients d_o, d_okd.  Aliasing of the gradient buffers:
+ *  - o_kd != o and d_okd != d_o: d_o receives the base term's gradient and d_okd the distillation term's, separately;
+ *  - o_kd == o with d_okd == d_o (enable_deit = 0, one head): d_o receives the sum of the two contributions;
+ *  - o_kd != o with d_okd == d_o: the shared buffer receives the sum of d loss / d o and d loss / d o_kd.
+ * (o_kd == o with a separate d_okd also leaves the sum in d_o, and d_okd is not written.)
+ * kind 0: o_kd, teacher and d_okd are not read and may be NULL; alpha is taken as 0. */
 typedef struct uvc_loss_args {
   const float* o; const float* o_kd; const float* y_soft; const float* teacher;
   float* loss; float* d_o; float* d_okd; float* row_scratch; /* [B] */
@@ -330,7 +334,8 @@ int uvc_mixup_target(const int64_t* labels, float* y, int32_t B, int32_t C, floa
 /* MLP compaction helpers (uvc_vit.h: uvc_mlp_compact).  idx [width]: hidden unit of each compact slot; inv [F]: slot or -1.
  * gather: w1c[s,:] = W1[idx[s],:], w1t = w1c^T, w2c[:,s] = W2[:,idx[s]], w2t = w2c^T (cast to T), b1c[s] = b1[idx[s]].
  * scatter: dW1[j,:] = dw1c[inv[j],:] or 0; db1[j] = db1c[inv[j]] or 0; dW2[:,j] = dw2c[:,inv[j]] or GELU(b1[j]) * db2[:]
- * (GELU as the forward of that precision mode evaluates and stores it); written as beta_acc*old + value. */
+ * (bf16 mode: GELU as the forward evaluates and stores it, approximant and bf16 rounding included; float32 mode: x/2 * erfc(-x/sqrt 2),
+ * which is the forward's value to within its float32 rounding and keeps its relative accuracy for x < 0); written as beta_acc*old + value. */
 int uvc_mlp_gather_shadows(const float* W1, const float* b1, const float* W2, const int32_t* idx, int32_t D, int32_t F, int32_t width,
                            void* w1c, void* w1t, void* w2c, void* w2t, float* b1c, int32_t dtype, void* stream);
 int uvc_mlp_scatter_grads(const float* dw1c, const float* dw2c, const float* db1c, const int32_t* inv, const float* b1, const float* db2,

@@ -465,6 +465,9 @@ __global__ __launch_bounds__(256) void k_mlp_gather(const float* __restrict__ W1
     if (d == 0) b1c[s] = b1[j];
   }
 }
+// float32 GELU of a pruned unit's bias as x/2 * erfc(-x / sqrt 2): the forward's 0.5 x (1 + erff(x / sqrt 2)) is good to float32
+// absolutely (<= 1e-7 |x|) but cancels for x < 0 -- 1e-4 relative at x = -3 -- and this value is a whole gradient column.
+__device__ __forceinline__ float gelu_erfc(float x) { return 0.5f * x * erfcf(x * -0.70710678118654752440f); }
 template <bool LOWP>
 __global__ __launch_bounds__(256) void k_mlp_scatter(const float* __restrict__ dw1c, const float* __restrict__ dw2c, const float* __restrict__ db1c,
                                                      const int* __restrict__ inv, const float* __restrict__ b1, const float* __restrict__ db2, int D,
@@ -483,7 +486,7 @@ __global__ __launch_bounds__(256) void k_mlp_scatter(const float* __restrict__ d
       float v;
       if (sl >= 0) v = dw2c[(size_t)d * Fe + sl];
       else {
-        float u = LOWP ? gelu_fast(b1[j]) : gelu_f(b1[j]);
+        float u = LOWP ? gelu_fast(b1[j]) : gelu_erfc(b1[j]);
         if (LOWP) u = bf16_to_f32(f32_to_bf16(u));        // the forward stores GELU(a) in bf16
         v = u * db2[d];
       }

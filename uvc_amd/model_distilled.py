@@ -494,16 +494,15 @@ class DistilledVisionTransformer(nn.Module):
         self._head_keep = None if bool(keep.all()) else keep.to(self._flat.device)
         return keep
 
-    def _gather_compact(self, stream):
+    def _gather_compact(self):
         """Refresh the gathered operand copies of the compacted MLPs from the (masked) master weights."""
         dt = ops.UVC_F32 if self.precision == "fp32" else ops.UVC_BF16
         cfg = self._cfg
         for blk, b in zip(self.blocks, self._mlp_bufs):
             if b is None:
                 continue
-            L.check(L.lib().uvc_mlp_gather_shadows(L.ptr(blk.mlp.fc1.weight.data), L.ptr(blk.mlp.fc1.bias.data), L.ptr(blk.mlp.fc2.weight.data),
-                                                   L.ptr(b["idx"]), cfg.embed_dim, cfg.hidden, b["width"], L.ptr(b["w1"]), L.ptr(b["w1t"]),
-                                                   L.ptr(b["w2"]), L.ptr(b["w2t"]), L.ptr(b["b1"]), dt, stream), "uvc_mlp_gather_shadows")
+            ops.mlp_gather_shadows(blk.mlp.fc1.weight.data, blk.mlp.fc1.bias.data, blk.mlp.fc2.weight.data, b["idx"], b["w1"], b["w1t"],
+                                   b["w2"], b["w2t"], b["b1"], cfg.embed_dim, cfg.hidden, b["width"], dt)
 
     def apply_masks(self):
         """``for m in modules: m.weight.data *= m.mask`` (post_train.py:343-346) as one launch over the flat buffer."""
@@ -605,7 +604,7 @@ class DistilledVisionTransformer(nn.Module):
         if not (self.frozen_weights and self._shadow_fresh):
             L.check(lib.uvc_vit_update_shadows(C.byref(cfg), L.ptr(self._flat), L.ptr(self._shadow), stream), "uvc_vit_update_shadows")
             if self._mlp_compact is not None:
-                self._gather_compact(stream)
+                self._gather_compact()
             self._shadow_fresh = True
         io = self._io(B, training)
         dev = self._flat.device

@@ -344,6 +344,20 @@ def apply_masks(params, mask):
     L.check(L.lib().uvc_apply_masks(L.ptr(params), L.ptr(mask), params.numel(), L.cur_stream()), "uvc_apply_masks")
 
 
+def mlp_gather_shadows(W1, b1, W2, idx, w1c, w1t, w2c, w2t, b1c, D, F, width, dtype):
+    """Compact operand copies of an MLP (include/uvc_kernels.h: uvc_mlp_gather_shadows): idx int32 [width], copies of type T, b1c float32."""
+    _chk(W1, b1, W2, idx, w1c, w1t, w2c, w2t, b1c)
+    L.check(L.lib().uvc_mlp_gather_shadows(L.ptr(W1), L.ptr(b1), L.ptr(W2), L.ptr(idx), D, F, width, L.ptr(w1c), L.ptr(w1t), L.ptr(w2c),
+                                           L.ptr(w2t), L.ptr(b1c), dtype, L.cur_stream()), "uvc_mlp_gather_shadows")
+
+
+def mlp_scatter_grads(dw1c, dw2c, db1c, inv, b1, db2, dW1, dW2, db1, D, F, width, dtype, beta_acc=0.0):
+    """Compact weight gradients expanded into the full tensors (uvc_mlp_scatter_grads): inv int32 [F] (slot or -1), all else float32."""
+    _chk(dw1c, dw2c, db1c, inv, b1, db2, dW1, dW2, db1)
+    L.check(L.lib().uvc_mlp_scatter_grads(L.ptr(dw1c), L.ptr(dw2c), L.ptr(db1c), L.ptr(inv), L.ptr(b1), L.ptr(db2), D, F, width, L.ptr(dW1),
+                                          L.ptr(dW2), L.ptr(db1), beta_acc, dtype, L.cur_stream()), "uvc_mlp_scatter_grads")
+
+
 def add_outer(X, row_weight, w, rows, D, dtype):
     _chk(X, row_weight, w)
     L.check(L.lib().uvc_add_outer(L.ptr(X), L.ptr(row_weight), L.ptr(w), rows, D, dtype, _is_f32(X), L.cur_stream()), "uvc_add_outer")
