@@ -84,6 +84,18 @@ int uvc_image_prep_workspace_filter(uvc_image_desc* desc, int32_t B, int32_t S, 
 /* Three launches whatever B is: coefficient tables, first pass, second pass + flip + normalise. */
 int uvc_image_prep(const uvc_image_prep_args* args, void* stream);
 
+/* ---- patch rows straight from the resampler.
+ * The same three launches and the same arithmetic as uvc_image_prep with a float32 output, but the last pass stores what uvc_patchify
+ * (uvc_kernels.h) would make of that batch, without the batch itself ever being written: args->out is T [B * (S/P)^2, 3 * P * P], and
+ * output pixel (b, c, y, x) goes to row b (S/P)^2 + (y/P)(S/P) + x/P, column c P P + (y%P) P + x%P, cast to bf16 (dtype UVC_BF16 = 1,
+ * round to nearest even) or kept float32 (UVC_F32 = 0) -- bit for bit uvc_patchify(uvc_image_prep(...)).  These are the rows a ViT
+ * forward takes as uvc_vit_io.patches_in (uvc_vit.h).  args->out_dtype is not read; flip, normalisation, the filter and the descriptor
+ * checks are uvc_image_prep's (a descriptor that does not fit is skipped and its rows are left untouched), and so is the workspace:
+ * complete the descriptors with uvc_image_prep_workspace(_filter).  UVC_ERR_ARG: P <= 0 or S % P != 0, a dtype other than the two,
+ * args->out not 16-byte aligned.  With P % 4 == 0 a thread stores four neighbouring columns at once (8 or 16 bytes); other patch
+ * sizes take one column per thread. */
+int uvc_image_prep_patches(const uvc_image_prep_args* args, int32_t P, int32_t dtype, void* stream);
+
 /* ---- crop windows of a resident store.
  * A dataset that stays in device memory (uvc_amd/packed.py: every image HWC uint8, rows of img_w*3 bytes, back to back) is resampled
  * without copying its crops out: each descriptor names a stored image and a window inside it, and the passes read the window's rows

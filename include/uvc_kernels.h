@@ -271,6 +271,15 @@ typedef struct uvc_loss_args {
 } uvc_loss_args;
 int uvc_distill_loss(const uvc_loss_args* args, void* stream);
 
+/* Softmax + top-k of a batch of logits (python -m uvc_amd.compact predict).  logits float32 [B, ld]; the softmax runs over columns
+ * [0, n_valid) only, so the padding logits of a head wider than its label set (the 16 / 104-wide CIFAR heads) take no part in the sum
+ * and are never chosen.  probs float32 [B, k] receives the k largest probabilities of each row in descending order and index int32 [B, k]
+ * their columns; equal values come out by ascending index.  The order is taken on the logits (the order of the exact probabilities);
+ * prob = exp(logit - row max) / sum, in float32.  1 <= k <= min(n_valid, 16) and 1 <= n_valid <= ld, UVC_ERR_ARG otherwise.
+ * One workgroup per row, fixed reduction trees, no atomics: the same bits on every run, and a row's result does not depend on B.
+ * A NaN logit is never chosen; a row with fewer than k comparable logits reports index -1 and a NaN probability for the rest. */
+int uvc_logits_topk(const float* logits, int32_t B, int32_t ld, int32_t n_valid, int32_t k, float* probs, int32_t* index, void* stream);
+
 /* clip_grad_norm_(max_norm) + AdamW over flat float32 buffers (joint_train.py:428-429;
  * torch.optim.AdamW(lr, betas, eps, weight_decay) semantics, decoupled decay).
  * uvc_grad_sqnorm accumulates sum(g^2) of a segment into sq[0] (accumulate = 0 for the first segment) and leaves sqrt(sq[0]) -- the

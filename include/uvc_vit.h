@@ -125,7 +125,9 @@ typedef struct uvc_vit_io {
                                           against 187), so 0 is the default */
   const void* patches_in;              /* optional T [B * np, C * P * P]: the patch rows of `x` already laid out by uvc_patchify (same image size and
                                           patch size).  The forward uses them instead of running uvc_patchify, the backward reads them for the
-                                          patch-embedding weight gradient.  Lets student and teacher share the one rearrangement of a batch. */
+                                          patch-embedding weight gradient.  Lets student and teacher share the one rearrangement of a batch.
+                                          uvc_vit_compact_forward reads nothing else of the batch: with patches_in, x may be NULL (rows written by
+                                          uvc_image_prep_patches, uvc_data.h). */
   int32_t fuse_next_ln;                /* 1: a kernel that produces a block's output rows (uvc_mlp_fused_fwd; fc2 + residual + gate mix) also writes
                                           norm1 of the NEXT block that runs (model_distilled.py:241) from the rows it holds, and that block skips its
                                           stand-alone LayerNorm pass.  0: every LayerNorm is its own pass. */

@@ -202,6 +202,7 @@ _SIGNATURES = {
     "uvc_gemm_lnbwd_nblocks": [I32],
     "uvc_gemm_nt_lnbwd": [C.POINTER(uvc_gemm_lnbwd_args), VP],
     "uvc_distill_loss": [C.POINTER(uvc_loss_args), VP],
+    "uvc_logits_topk": [VP, I32, I32, I32, I32, VP, VP, VP],
     "uvc_grad_sqnorm": [VP, I64, VP, VP, I32, VP],
     "uvc_adamw_step": [C.POINTER(uvc_adamw_args), VP],
     "uvc_scale_by_clip": [VP, I64, VP, F32, VP],
@@ -233,6 +234,7 @@ _SIGNATURES = {
     "uvc_image_prep_workspace": [VP, I32, I32, I64, C.POINTER(I64)],
     "uvc_image_prep_workspace_filter": [VP, I32, I32, I64, I32, C.POINTER(I64)],
     "uvc_image_prep": [C.POINTER(uvc_image_prep_args), VP],
+    "uvc_image_prep_patches": [C.POINTER(uvc_image_prep_args), I32, I32, VP],
     "uvc_image_prep_crops_workspace": [VP, I32, I32, I64, C.POINTER(I64)],
     "uvc_image_prep_crops_workspace_filter": [VP, I32, I32, I64, I32, C.POINTER(I64)],
     "uvc_image_prep_crops": [C.POINTER(uvc_image_prep_crops_args), VP],

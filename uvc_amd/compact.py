@@ -16,9 +16,11 @@ zero ``b1`` and zero fc2 columns (GELU(0) = 0 meets a zero column).
     python -m uvc_amd.compact export --model_type ... --checkpoint_dir CK --output model.compact.pt
     python -m uvc_amd.compact eval --compact model.compact.pt [--synthetic 0 --dataset ... --data_dir ...]
     python -m uvc_amd.compact finetune --compact model.compact.pt --output tuned.compact.pt [Stage 2's flags]
+    python -m uvc_amd.compact predict --compact model.compact.pt --images PATH [PATH ...] [--output preds.jsonl]
 
 ``reference_forward`` is the written spec of the format (plain PyTorch, CPU or GPU, any dtype); ``CompactVisionTransformer``
-runs it through ``uvc_vit_compact_forward`` (include/uvc_vit.h).  ``reference_logits`` is the same network with the two heads kept
+runs it through ``uvc_vit_compact_forward`` (include/uvc_vit.h).  ``predict`` classifies image files with it (file -> eval transform -> patch rows -> compact forward -> softmax + top-k, all of it
+behind the decode on the device).  ``reference_logits`` is the same network with the two heads kept
 apart: the function ``compact_train.CompactTrainer`` fine-tunes (a fine-tuned file is an ordinary version-1 compact file).
 """
 from __future__ import annotations
@@ -404,6 +406,20 @@ class _CompactModule(nn.Module):
             raise AssertionError(f"Input image size ({x.shape[2]}*{x.shape[3]}) doesn't match model ({c['img_size']}*{c['img_size']}).")
         return x
 
+    def _prep_patches(self, patches):
+        """The batch size of ready-made patch rows ([B * np, C * P * P] in the engine's dtype, ops.patchify's layout), checked."""
+        from . import _lib as L
+        from . import ops
+        L.require_cuda(patches)
+        c = self._export["cfg"]
+        npatch, K = (c["img_size"] // c["patch_size"]) ** 2, c["in_chans"] * c["patch_size"] ** 2
+        want = ops.tdtype(self._cfg.dtype)
+        if patches.dim() != 2 or patches.shape[1] != K or patches.shape[0] % npatch or patches.shape[0] == 0 or not patches.is_contiguous():
+            raise AssertionError(f"patch rows {tuple(patches.shape)} do not match the model: contiguous [B * {npatch}, {K}]")
+        if patches.dtype != want:
+            raise AssertionError(f"patch rows are {patches.dtype} but the model runs in {want}")
+        return patches.shape[0] // npatch
+
     def _workspace(self, B, training):
         """One workspace per mode, for the last batch size seen."""
         key = (B, bool(training))
@@ -435,13 +451,21 @@ class _CompactModule(nn.Module):
         io.x, io.patch_mask, io.batch, io.training = L.ptr(x), L.ptr(mask), B, int(training)
         return io, mask
 
-    def _forward(self, x, training=False):
-        """``(logits, logits_dist or None, what a backward needs of the pass)`` through the eval or the training forward."""
+    def _forward(self, x, training=False, patches=None):
+        """``(logits, logits_dist or None, what a backward needs of the pass)`` through the eval or the training forward.  ``patches``
+        (eval only, in place of ``x``): the batch's patch rows, which the forward then does not make itself."""
         from . import _lib as L
-        x = self._prep(x)
-        B, dev = x.shape[0], self._flat.device
+        dev = self._flat.device
+        if patches is not None:
+            if x is not None or training:
+                raise ValueError("patch rows stand in for the image batch of an eval forward: pass one of x / patches")
+            B = self._prep_patches(patches)
+        else:
+            x = self._prep(x)
+            B = x.shape[0]
         self._refresh_shadows()
         io, mask = self._io(x, B, training)
+        io.patches_in = L.ptr(patches)                  # (None: the forward rearranges x itself)
         nc = self._export["cfg"]["num_classes"]
         logits = torch.empty(B, nc, device=dev)
         logits_dist = torch.empty(B, nc, device=dev) if self.num_tokens == 2 else None
@@ -451,9 +475,9 @@ class _CompactModule(nn.Module):
         return logits, logits_dist, dict(x=x, B=B, mask=mask)
 
     @torch.no_grad()
-    def _eval_logits(self, x):
+    def _eval_logits(self, x, patches=None):
         """The eval logits: ``(x + x_dist) / 2`` with the distillation token."""
-        o, od, _ = self._forward(x)
+        o, od, _ = self._forward(x, patches=patches)
         return o if od is None else (o + od) / 2
 
 
@@ -471,8 +495,146 @@ class CompactVisionTransformer(_CompactModule):
             L.check(self._lib_call("uvc_vit_compact_update_shadows", L.ptr(self._flat), L.ptr(self._shadow), L.cur_stream()), "uvc_vit_compact_update_shadows")
         self.eval()
 
-    def forward(self, x):
-        return self._eval_logits(x), self.macs(x.shape[0])
+    def forward(self, x=None, *, patches=None):
+        """``x`` float32 [B, C, S, S], or ``patches=`` its patch rows [B * np, C * P * P] in the model's dtype (ops.patchify's layout, as
+        ``DeviceLoader(output="patches")`` yields them): they feed ``uvc_vit_io.patches_in`` and the forward skips uvc_patchify."""
+        logits = self._eval_logits(x, patches)
+        return logits, self.macs(logits.shape[0])
+
+
+# ---- classify image files -------------------------------------------------------------------------------------------------------
+MAX_TOPK = 16                                       # uvc_logits_topk's limit
+FUSED_INPUT_DEFAULT = 1                             # decided by tools/predict_time.py's rounds (README "Classify images")
+PRESETS = ("imagenet", "cifar")
+
+
+def read_classes(path) -> List[str]:
+    """Class names from a file: a JSON list, or one name per line (blank lines dropped)."""
+    with open(path, "r", encoding="utf-8") as f:
+        text = f.read()
+    if text.lstrip().startswith("["):
+        names = json.loads(text)
+        if not isinstance(names, list):
+            raise ValueError(f"{path}: a JSON class file holds one list of names")
+        return [str(n) for n in names]
+    return [line.strip() for line in text.splitlines() if line.strip()]
+
+
+def topk_reference(logits, k, n_valid=None):
+    """What ``ops.logits_topk`` computes, in float64 on the host: ``(probs [B, k], index [B, k])`` (numpy) of the softmax over columns
+    ``[:n_valid]``, the k largest first, in the stable order ``(-p, index)``.  Tests hold the kernel to it."""
+    import numpy as np
+    z = np.asarray(logits, dtype=np.float64)
+    z = z.reshape(-1, z.shape[-1])[:, :n_valid]
+    e = np.exp(z - z.max(axis=1, keepdims=True))
+    p = e / e.sum(axis=1, keepdims=True)
+    index = np.stack([np.lexsort((np.arange(p.shape[1]), -row))[:k] for row in p])
+    return np.take_along_axis(p, index, axis=1), index.astype(np.int32)
+
+
+def predict(model, files, *, topk=5, batch_size=64, preset="imagenet", interpolation="bilinear", crop_pct=None, num_labels=None, classes=None,
+            num_workers=8, fused_input=bool(FUSED_INPUT_DEFAULT)):
+    """Classify image files with a ``CompactVisionTransformer``: yields one record per file, in input order,
+    ``{"file", "top": [{"index", "label", "prob"}, ...]}`` with the ``topk`` most probable labels first, or ``{"file", "error"}`` for a file
+    that cannot be read (the run goes on).
+
+    preset "imagenet": Resize(eval_resize_side(S, crop_pct)) + CenterCrop(S) with ImageNet's mean / std, ``build_loaders``' test transform;
+    "cifar": Resize((S, S)) with 0.5 / 0.5.  ``interpolation`` / ``crop_pct`` as the loaders take them.  The softmax runs over the first
+    ``num_labels`` logits (default: ``len(classes)``, else the model's num_classes), so the padding logits of a 16 / 104-wide CIFAR head
+    are never reported; ``classes`` names them (``label`` is None without).  ``fused_input``: the resampler writes the patch rows the
+    forward reads (uvc_image_prep_patches); False: it writes the float32 images and the forward rearranges them (uvc_image_prep +
+    uvc_patchify) -- the same records bit for bit.  ``files``: paths, or a dataset with ``load(i)`` / ``targets`` (records then name indices)."""
+    from . import data, ops
+    if preset not in PRESETS:
+        raise ValueError(f"preset must be one of {PRESETS}, not {preset!r}")
+    c = model._export["cfg"]
+    classes = None if classes is None else list(classes)
+    if num_labels is None:
+        num_labels = len(classes) if classes is not None else c["num_classes"]
+    num_labels, topk = int(num_labels), int(topk)
+    if not 1 <= num_labels <= c["num_classes"]:
+        raise ValueError(f"num_labels {num_labels} must lie in [1, {c['num_classes']}] (the model's head)")
+    if classes is not None and len(classes) < num_labels:
+        raise ValueError(f"{len(classes)} class names for {num_labels} labels")
+    if not 1 <= topk <= min(MAX_TOPK, num_labels):
+        raise ValueError(f"topk {topk} must lie in [1, {min(MAX_TOPK, num_labels)}]")
+    ds = files if hasattr(files, "load") else data.FileListDataset(files, tolerant=True)
+    names = ds.paths if hasattr(ds, "paths") else list(range(len(ds)))
+    errors = getattr(ds, "errors", {})
+    dev = model._flat.device
+    kw = dict(mean=data.IMAGENET_MEAN, std=data.IMAGENET_STD, eval="center") if preset == "imagenet" else \
+        dict(mean=data.CIFAR_MEAN, std=data.CIFAR_STD, eval="square")
+    if fused_input:
+        kw.update(output="patches", patch_size=c["patch_size"], dtype=ops.tdtype(model._cfg.dtype))
+    loader = data.DeviceLoader(ds, int(batch_size), c["img_size"], train=False, num_workers=num_workers, device=dev, interpolation=interpolation,
+                               crop_pct=crop_pct, **kw)
+
+    def records(first, probs, index):
+        for b, (pr, ix) in enumerate(zip(probs.tolist(), index.tolist())):
+            i = first + b
+            if i in errors:
+                yield dict(file=names[i], error=errors[i])
+            else:
+                yield dict(file=names[i], top=[dict(index=j, label=None if classes is None else classes[j], prob=q) for j, q in zip(ix, pr)])
+
+    # the records of a batch are read back after the next batch's launches, so the device does not idle behind the host
+    first, pending = 0, None
+    with torch.cuda.device(dev):
+        for x, _ in loader:
+            logits = model._eval_logits(None, x) if fused_input else model._eval_logits(x)
+            probs, index = ops.logits_topk(logits, topk, num_labels)
+            if pending is not None:
+                yield from records(pending[0], pending[1].cpu(), pending[2].cpu())
+            pending = (first, probs, index)
+            first += len(probs)
+        if pending is not None:
+            yield from records(pending[0], pending[1].cpu(), pending[2].cpu())
+
+
+def _int_in(lo, hi, what):
+    def parse(v):
+        n = int(v)
+        if not lo <= n <= hi:
+            raise argparse.ArgumentTypeError(f"{what} must lie in [{lo}, {hi}], not {n}")
+        return n
+    return parse
+
+
+def _crop_pct_arg(v):
+    from .data import eval_resize_side
+    try:
+        eval_resize_side(224, float(v))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return float(v)
+
+
+def predict_command(args, dev):
+    """``predict``: one JSON line per image to --output (or stdout), then the summary line ``{"images", "errors", "batches", "img_per_s"}``."""
+    import sys
+    import time
+    from . import data
+    export = load_compact(args.compact)
+    classes = read_classes(args.classes) if args.classes else None
+    files = data.list_images(args.images)
+    cm = CompactVisionTransformer(export, precision=args.precision, device=dev)
+    out = open(args.output, "w", encoding="utf-8") if args.output else sys.stdout
+    n = nerr = 0
+    t0 = time.perf_counter()
+    try:
+        for rec in predict(cm, files, topk=args.topk, batch_size=args.batch_size, preset=args.preset, interpolation=args.interpolation,
+                           crop_pct=args.crop_pct, num_labels=args.num_labels, classes=classes, num_workers=args.num_workers,
+                           fused_input=bool(args.fused_input)):
+            out.write(json.dumps(rec) + "\n")
+            n += 1
+            nerr += "error" in rec
+        dt = time.perf_counter() - t0
+        summary = dict(images=n, errors=nerr, batches=math.ceil(n / args.batch_size), img_per_s=n / dt if dt > 0 else 0.0)
+        out.write(json.dumps(summary) + "\n")
+    finally:
+        if out is not sys.stdout:
+            out.close()
+    return summary
 
 
 # ---- command line -------------------------------------------------------------------------------------------------------------
@@ -507,6 +669,26 @@ def _parser():
     f.add_argument("--compact", required=True, help="the compact file to fine-tune")
     f.add_argument("--output", required=True, help="where the best model (validation top-1) is written, a version-1 compact file")
     add_stage2_flags(f, skip=("checkpoint_dir", "eval_only"))
+    # classify image files with a compact file
+    from .data import INTERPOLATIONS
+    q = sub.add_parser("predict")
+    q.add_argument("--compact", required=True, help="the compact file (a dense checkpoint goes through `export` first)")
+    q.add_argument("--images", nargs="+", required=True, help="image files, or directories walked recursively for image files (sorted)")
+    q.add_argument("--output", default=None, help="JSON-lines file; default: stdout")
+    q.add_argument("--topk", type=_int_in(1, MAX_TOPK, "--topk"), default=5)
+    q.add_argument("--batch_size", type=_int_in(1, 65535, "--batch_size"), default=64)
+    q.add_argument("--num_workers", type=int, default=8, help="decode threads (at most 16)")
+    q.add_argument("--precision", default="bf16")
+    q.add_argument("--preset", choices=list(PRESETS), default="imagenet",
+                   help="imagenet: resize, centre crop, ImageNet mean / std; cifar: square resize, mean / std 0.5")
+    q.add_argument("--interpolation", choices=list(INTERPOLATIONS), default="bilinear")
+    q.add_argument("--crop_pct", type=_crop_pct_arg, default=None,
+                   help="imagenet preset: resize the short side to floor(img_size / crop_pct) before the centre crop; default: img_size * 256 // 224")
+    q.add_argument("--classes", default=None, help="class names: one per line, or a JSON list")
+    q.add_argument("--num_labels", type=_int_in(1, 1 << 20, "--num_labels"), default=None,
+                   help="the valid logits (the rest of the head is padding); default: the length of --classes, else the file's num_classes")
+    q.add_argument("--fused_input", type=int, default=FUSED_INPUT_DEFAULT,
+                   help="1: the resampler writes the patch rows (uvc_image_prep_patches); 0: images, then uvc_patchify")
     return p
 
 
@@ -566,6 +748,8 @@ def main(argv=None):
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
     if args.cmd == "finetune":
         return finetune(args, dev)
+    if args.cmd == "predict":
+        return predict_command(args, dev)
     if args.cmd == "export" or not args.compact:
         model = _dense_model(args, dev)
         export = export_compact(model, compact_plan(model, args.mlp_multiple))

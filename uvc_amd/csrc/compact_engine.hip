@@ -415,7 +415,8 @@ extern "C" int uvc_vit_compact_train_update_shadows(const uvc_vit_cfg* cfg, cons
 // ---- forward (eval, training) and backward -------------------------------------------------------------------------------------------
 extern "C" int uvc_vit_compact_forward(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* stream) {
   TRY(check_blocks(cfg, blocks, nblocks));
-  if (!io || !io->params || !io->workspace || io->batch <= 0 || !io->x || !io->logits || (cfg->ntok == 2 && !io->logits_dist))
+  if (!io || !io->params || !io->workspace || io->batch <= 0 || (!io->x && !io->patches_in) || !io->logits ||
+      (cfg->ntok == 2 && !io->logits_dist))   // x is read by uvc_patchify alone: patch rows handed in (patches_in) stand for it
     return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_forward: null io member");
   if (cfg->dtype == UVC_BF16 && !io->shadow) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_forward: bf16 mode needs the shadow buffer");
   Ctx c;

@@ -5,7 +5,8 @@
 //   k_prep_coeffs   one thread per (image, output column or row): PIL's precompute_coeffs + normalize_coeffs_8bpc in float64
 //   k_prep_pass1    the first pass into a uint8 intermediate: horizontal, one thread per (covered source row, output column), or, for
 //                   the tall sources Image.resize shrinks vertically first, vertical, one thread per (output row, covered source column)
-//   k_prep_pass2    one thread per (image, output row, output column): the other axis, flip, normalise, NCHW store
+//   k_prep_pass2    one thread per (image, output row, output column): the other axis, flip, normalise, and the store its policy names:
+//                   the NCHW batch, or (uvc_image_prep_patches) the patch rows uvc_patchify would make of it, four columns per thread
 // Built with -ffp-contract=off (uvc_amd/build.py): the float64 coefficient arithmetic must round like the C it mirrors.
 //
 // The launch's filter (args.filter) picks the weight function and its support in k_prep_coeffs and the tap count desc_ok expects;
@@ -16,6 +17,7 @@
 // (tests/test_image_bicubic_cpu.py sweeps them).
 #include "common.h"
 #include "uvc_data.h"
+#include "uvc_kernels.h"                 // UVC_F32 / UVC_BF16, the patch rows' element types
 
 #include <math.h>
 
@@ -246,8 +248,66 @@ __global__ void __launch_bounds__(256) k_prep_pass1(Args a) {
   }
 }
 
-template <class Args>
-__global__ void __launch_bounds__(256) k_prep_pass2(Args a) {
+// Store policies of k_prep_pass2.  A thread owns kPixels consecutive output pixels of one output row; the policy says where their three
+// channels go.  StoreImage is the [B, 3, S, S] batch (float32 or uint8, args.out_dtype).  StorePatches writes the rows uvc_patchify would
+// make of that batch, [B * (S/P)^2, 3 * P * P] of T: pixel (b, ch, y, x) at row b (S/P)^2 + (y/P)(S/P) + x/P, column ch P P + (y%P) P + x%P,
+// with uvc_patchify's cast.  A patch row is contiguous only along x, P elements at a time, so a thread owns V = 4 pixels of such a run
+// (P % 4 == 0: one 8-byte bf16 or 16-byte float32 store per channel, uvc_patchify's own width; a 16-pixel run is four neighbouring lanes)
+// or, for the other patch sizes, one pixel.
+struct StoreImage {
+  static constexpr int kPixels = 1;
+  static constexpr bool kReadsOutDtype = true;
+  template <class Args>
+  __device__ __forceinline__ void operator()(const Args& a, int b, int S, int64_t p, int, int, const uint8_t (*u)[3]) const {
+    const int64_t plane = (int64_t)S * S;
+    const int64_t base = (int64_t)b * 3 * plane + p;
+    if (a.out_dtype == UVC_IMAGE_OUT_U8) {
+      uint8_t* o = (uint8_t*)a.out + base;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) o[ch * plane] = u[0][ch];
+    } else {
+      float* o = (float*)a.out + base;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) o[ch * plane] = __fdiv_rn(__fdiv_rn((float)u[0][ch], 255.0f) - a.mean[ch], a.std[ch]);
+    }
+  }
+};
+
+template <typename T, int V>
+struct StorePatches {
+  static_assert(V == 1 || V == 4, "pixels per thread");
+  static constexpr int kPixels = V;
+  static constexpr bool kReadsOutDtype = false;
+  int P;                               // S % P == 0 and P % V == 0 (uvc_image_prep_patches)
+  template <class Args>
+  __device__ __forceinline__ void operator()(const Args& a, int b, int S, int64_t, int r, int c, const uint8_t (*u)[3]) const {
+    const int G = S / P, py = r / P, px = c / P;
+    const int PP = P * P;
+    const int64_t row = ((int64_t)b * G + py) * G + px;
+    T* o = (T*)a.out + row * (3 * (int64_t)PP) + (r - py * P) * P + (c - px * P);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      float v[V];
+#pragma unroll
+      for (int i = 0; i < V; ++i) v[i] = __fdiv_rn(__fdiv_rn((float)u[i][ch], 255.0f) - a.mean[ch], a.std[ch]);
+      T* q = o + ch * PP;
+      if constexpr (V == 1) {
+        ElemIO<T>::store(q, v[0]);
+      } else if constexpr (sizeof(T) == 4) {
+        *reinterpret_cast<f32x4*>(q) = f32x4{v[0], v[1], v[2], v[3]};
+      } else {
+        u32x2 w;
+        w[0] = pack_bf16x2(v[0], v[1]);
+        w[1] = pack_bf16x2(v[2], v[3]);
+        *reinterpret_cast<u32x2*>(q) = w;
+      }
+    }
+  }
+};
+
+template <class Args, class Store>
+__global__ void __launch_bounds__(256) k_prep_pass2(Args a, Store store) {
+  constexpr int V = Store::kPixels;
   const int b = blockIdx.y;
   const auto d = a.desc[b];
   if (!desc_ok(d, a)) return;
@@ -260,30 +320,25 @@ __global__ void __launch_bounds__(256) k_prep_pass2(Args a) {
   const int32_t* vk = (const int32_t*)(ws + L.vk);
   const uint8_t* inter = ws + L.inter;
   const int64_t plane = (int64_t)S * S;
-  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < plane; p += (int64_t)gridDim.x * blockDim.x) {
-    const int r = (int)(p / S), c = (int)(p - (int64_t)r * S);
-    const int cc = d.flip ? S - 1 - c : c;
-    uint8_t u[3];
-    if (d.order == 0)                  // vertical down intermediate column cc
-      mac3(inter + (int64_t)vb[2 * r] * S * 3 + (int64_t)cc * 3, (int64_t)S * 3, vk + (int64_t)r * d.kv, vb[2 * r + 1], u);
-    else                               // horizontal along intermediate row r
-      mac3(inter + ((int64_t)r * d.span + hb[2 * cc]) * 3, 3, hk + (int64_t)cc * d.kh, hb[2 * cc + 1], u);
-    const int64_t base = (int64_t)b * 3 * plane + p;
-    if (a.out_dtype == UVC_IMAGE_OUT_U8) {
-      uint8_t* o = (uint8_t*)a.out + base;
+  for (int64_t p = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * V; p < plane; p += (int64_t)gridDim.x * blockDim.x * V) {
+    const int r = (int)(p / S), c = (int)(p - (int64_t)r * S);   // S % V == 0: the V pixels share the row
+    uint8_t u[V][3];
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) o[ch * plane] = u[ch];
-    } else {
-      float* o = (float*)a.out + base;
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) o[ch * plane] = __fdiv_rn(__fdiv_rn((float)u[ch], 255.0f) - a.mean[ch], a.std[ch]);
+    for (int i = 0; i < V; ++i) {
+      const int cc = d.flip ? S - 1 - (c + i) : c + i;
+      if (d.order == 0)                // vertical down intermediate column cc
+        mac3(inter + (int64_t)vb[2 * r] * S * 3 + (int64_t)cc * 3, (int64_t)S * 3, vk + (int64_t)r * d.kv, vb[2 * r + 1], u[i]);
+      else                             // horizontal along intermediate row r
+        mac3(inter + ((int64_t)r * d.span + hb[2 * cc]) * 3, 3, hk + (int64_t)cc * d.kh, hb[2 * cc + 1], u[i]);
     }
+    store(a, b, S, p, r, c, u);             // p = r S + c
   }
 }
 
-// workgroups per image and pass: about one pixel per thread for the S x S output (the first pass strides over its span)
-inline int pass_blocks(int S) {
-  const int64_t g = ((int64_t)S * S + 255) / 256;
+// workgroups per image and pass: about one pixel per thread for the S x S output (the first pass strides over its span), or one
+// thread per `pixels` of them
+inline int pass_blocks(int S, int pixels = 1) {
+  const int64_t g = ((int64_t)S * S / pixels + 255) / 256;
   return (int)(g < 1 ? 1 : (g > 1024 ? 1024 : g));
 }
 
@@ -328,18 +383,18 @@ int prep_workspace(Desc* desc, int32_t B, int32_t S, int64_t src_bytes, int32_t 
   return UVC_OK;
 }
 
-template <class Args>
-int prep_launch(const Args* a, void* stream, const char* null_msg, const char* arg_msg, const char* align_msg) {
+template <class Args, class Store>
+int prep_launch(const Args* a, Store store, void* stream, const char* null_msg, const char* arg_msg, const char* align_msg) {
   if (!a || !a->src || !a->desc || !a->workspace || !a->out) return uvc_set_error_msg(UVC_ERR_ARG, null_msg);
-  if (a->B < 1 || a->B > 65535 || a->S < 1 || a->S > kMaxS || (a->out_dtype != UVC_IMAGE_OUT_F32 && a->out_dtype != UVC_IMAGE_OUT_U8) ||
-      !filter_ok(a->filter))
+  if (a->B < 1 || a->B > 65535 || a->S < 1 || a->S > kMaxS ||
+      (Store::kReadsOutDtype && a->out_dtype != UVC_IMAGE_OUT_F32 && a->out_dtype != UVC_IMAGE_OUT_U8) || !filter_ok(a->filter))
     return uvc_set_error_msg(UVC_ERR_ARG, arg_msg);
   if (((uintptr_t)a->workspace & 15) || a->workspace_bytes < 0 || a->src_bytes < 0) return uvc_set_error_msg(UVC_ERR_ARG, align_msg);
   hipStream_t st = (hipStream_t)stream;
   const Args args = *a;
   k_prep_coeffs<Args><<<dim3((2 * args.S + 255) / 256, args.B), 256, 0, st>>>(args);
   k_prep_pass1<Args><<<dim3(pass_blocks(args.S), args.B), 256, 0, st>>>(args);
-  k_prep_pass2<Args><<<dim3(pass_blocks(args.S), args.B), 256, 0, st>>>(args);
+  k_prep_pass2<Args, Store><<<dim3(pass_blocks(args.S, Store::kPixels), args.B), 256, 0, st>>>(args, store);
   UVC_CHECK_LAUNCH();
   return UVC_OK;
 }
@@ -366,6 +421,14 @@ int crops_workspace(uvc_image_crop_desc* desc, int32_t B, int32_t S, int64_t sto
   return prep_workspace(desc, B, S, store_bytes, filter, bytes, msg);
 }
 
+template <typename T>
+int patches_launch(const uvc_image_prep_args* a, int32_t P, void* stream) {
+  static const char *null_msg = "uvc_image_prep_patches: null pointer", *arg_msg = "uvc_image_prep_patches: bad B, S or filter",
+                    *align_msg = "uvc_image_prep_patches: workspace must be 16-byte aligned";
+  if (P % 4 == 0) return prep_launch(a, StorePatches<T, 4>{P}, stream, null_msg, arg_msg, align_msg);
+  return prep_launch(a, StorePatches<T, 1>{P}, stream, null_msg, arg_msg, align_msg);
+}
+
 }  // namespace
 
 extern "C" int uvc_image_prep_workspace(uvc_image_desc* desc, int32_t B, int32_t S, int64_t src_bytes, int64_t* bytes) {
@@ -377,8 +440,15 @@ extern "C" int uvc_image_prep_workspace_filter(uvc_image_desc* desc, int32_t B, 
 }
 
 extern "C" int uvc_image_prep(const uvc_image_prep_args* a, void* stream) {
-  return prep_launch(a, stream, "uvc_image_prep: null pointer", "uvc_image_prep: bad B, S, out_dtype or filter",
+  return prep_launch(a, StoreImage{}, stream, "uvc_image_prep: null pointer", "uvc_image_prep: bad B, S, out_dtype or filter",
                      "uvc_image_prep: workspace must be 16-byte aligned");
+}
+
+extern "C" int uvc_image_prep_patches(const uvc_image_prep_args* a, int32_t P, int32_t dtype, void* stream) {
+  if (dtype != UVC_F32 && dtype != UVC_BF16) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep_patches: dtype must be UVC_F32 or UVC_BF16");
+  if (!a || P <= 0 || a->S % P) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep_patches: the patch size must be positive and divide S");
+  if ((uintptr_t)a->out & 15) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_image_prep_patches: out must be 16-byte aligned");
+  return dtype == UVC_F32 ? patches_launch<float>(a, P, stream) : patches_launch<bf16_t>(a, P, stream);
 }
 
 extern "C" int uvc_image_prep_crops_workspace(uvc_image_crop_desc* desc, int32_t B, int32_t S, int64_t store_bytes, int64_t* bytes) {
@@ -391,6 +461,6 @@ extern "C" int uvc_image_prep_crops_workspace_filter(uvc_image_crop_desc* desc, 
 }
 
 extern "C" int uvc_image_prep_crops(const uvc_image_prep_crops_args* a, void* stream) {
-  return prep_launch(a, stream, "uvc_image_prep_crops: null pointer", "uvc_image_prep_crops: bad B, S, out_dtype or filter",
+  return prep_launch(a, StoreImage{}, stream, "uvc_image_prep_crops: null pointer", "uvc_image_prep_crops: bad B, S, out_dtype or filter",
                      "uvc_image_prep_crops: workspace must be 16-byte aligned");
 }

@@ -99,6 +99,55 @@ __global__ __launch_bounds__(256) void k_loss_final(const float* rows, int B, fl
   if (threadIdx.x == 0) loss[0] = s;
 }
 
+// ---------------------------------------------------------------------------- softmax + top-k of the logits (uvc_logits_topk)
+// "a before b" in the output order: larger value first, equal values by ascending index
+__device__ __forceinline__ bool topk_before(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
+
+// one block per batch row: max, sum of exp, then k selection rounds.  A round picks the first column in the output order that comes
+// after the previous round's pick, so nothing is marked and nothing is written between rounds; the order is that of the logits, which
+// is the order of their exact probabilities.  No atomics: every reduction is a fixed tree (wave butterfly, then the four waves in order).
+__global__ __launch_bounds__(256) void k_logits_topk(const float* __restrict__ logits, int ld, int n, int k, float* __restrict__ probs,
+                                                     int32_t* __restrict__ index) {
+  __shared__ float sh[4];
+  __shared__ float shv[4];
+  __shared__ int shi[4];
+  const float* o = logits + (size_t)blockIdx.x * ld;
+  float mx = -INFINITY;
+  for (int c = threadIdx.x; c < n; c += 256) mx = fmaxf(mx, o[c]);
+  mx = block_reduce(mx, sh, true);
+  float se = 0.f;
+  for (int c = threadIdx.x; c < n; c += 256) se += expf(o[c] - mx);
+  se = block_reduce(se, sh, false);
+  float pv = INFINITY;                 // the previous pick; (+inf, -1) comes before every column
+  int pi = -1;
+  for (int j = 0; j < k; ++j) {
+    float bv = -INFINITY;              // (-inf, INT_MAX): nothing found
+    int bi = 0x7fffffff;
+    for (int c = threadIdx.x; c < n; c += 256) {
+      const float v = o[c];
+      if (topk_before(pv, pi, v, c) && topk_before(v, c, bv, bi)) { bv = v; bi = c; }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+      const float ov = __shfl_xor(bv, s, 64);
+      const int oi = __shfl_xor(bi, s, 64);
+      if (topk_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { shv[threadIdx.x >> 6] = bv; shi[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    bv = shv[0]; bi = shi[0];
+    for (int w = 1; w < 4; ++w)
+      if (topk_before(shv[w], shi[w], bv, bi)) { bv = shv[w]; bi = shi[w]; }
+    const bool found = bi < n;         // k <= n columns exist; a NaN logit compares with nothing and is never picked
+    if (threadIdx.x == 0) {
+      probs[(size_t)blockIdx.x * k + j] = found ? __fdiv_rn(expf(bv - mx), se) : __builtin_nanf("");
+      index[(size_t)blockIdx.x * k + j] = found ? bi : -1;
+    }
+    pv = bv; pi = bi;
+  }
+}
+
 // ---------------------------------------------------------------------------- grad norm + AdamW
 constexpr int NORM_BLOCKS = 1024;
 
@@ -199,6 +248,15 @@ extern "C" int uvc_distill_loss(const uvc_loss_args* p, void* stream) {
   k_loss_rows<<<p->B, 256, 0, st>>>(*p);
   UVC_CHECK_LAUNCH();
   k_loss_final<<<1, 256, 0, st>>>(p->row_scratch, p->B, p->loss);
+  UVC_CHECK_LAUNCH();
+  return UVC_OK;
+}
+
+extern "C" int uvc_logits_topk(const float* logits, int32_t B, int32_t ld, int32_t n_valid, int32_t k, float* probs, int32_t* index, void* stream) {
+  if (!logits || !probs || !index || B <= 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_logits_topk: null pointer or B <= 0");
+  if (n_valid < 1 || n_valid > ld) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_logits_topk: need 1 <= n_valid <= ld");
+  if (k < 1 || k > 16 || k > n_valid) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_logits_topk: need 1 <= k <= min(n_valid, 16)");
+  k_logits_topk<<<B, 256, 0, (hipStream_t)stream>>>(logits, ld, n_valid, k, probs, index);
   UVC_CHECK_LAUNCH();
   return UVC_OK;
 }

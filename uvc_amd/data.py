@@ -9,6 +9,7 @@ were trained and evaluated with; ``crop_pct`` sets the eval resize by timm's rul
     ImageFolder(root)            torchvision.datasets.ImageFolder indexing (sorted classes, os.walk(followlinks=True), IMG_EXTENSIONS)
     read_cifar(root, name, train) the local python-pickle CIFAR-10 / CIFAR-100 layout, nothing is downloaded -> ArrayDataset
     ArrayDataset(images, labels) uint8 [N, H, W, 3] in memory
+    FileListDataset(paths)       image files in the order given, loaded as the folder dataset loads them, dummy targets (compact predict)
     DeviceLoader(...)            (x float32 [B, 3, S, S] cuda, target int64 cuda) batches, DistributedSampler order
     (uvc_amd/packed.py: PackedDataset, a dataset decoded once into one file, and ResidentLoader, the same batches from pixels that stay on the GPU)
     build_loaders(args, ...)     the reference's train / test loaders for --dataset cifar10 | cifar100 | imagenet
@@ -64,10 +65,7 @@ class ImageFolder:
 
     def load(self, i):
         """uint8 [H, W, 3] pixels of sample i."""
-        from PIL import Image
-        with open(self.samples[i][0], "rb") as f:
-            img = Image.open(f)
-            return np.asarray(img.convert("RGB"))
+        return _open_rgb(self.samples[i][0])
 
 
 class ArrayDataset:
@@ -87,6 +85,53 @@ class ArrayDataset:
 
     def load(self, i):
         return self.images[i]
+
+
+def _open_rgb(path):
+    """uint8 [H, W, 3] pixels of an image file: ``Image.open(f).convert("RGB")``, as torchvision's folder loader."""
+    from PIL import Image
+    with open(path, "rb") as f:
+        img = Image.open(f)
+        return np.asarray(img.convert("RGB"))
+
+
+class FileListDataset:
+    """Image files in the order given, without labels (targets are zeros): what ``python -m uvc_amd.compact predict`` classifies.
+    ``load(i)`` is ImageFolder's (RGB conversion included).  ``tolerant``: a file that cannot be read or decoded does not end the
+    epoch; its message goes to ``errors[i]`` and one black pixel stands in for it, so the batches keep their order and size."""
+
+    def __init__(self, paths, tolerant=False):
+        self.paths = [os.fspath(p) for p in paths]
+        self.targets = np.zeros(len(self.paths), dtype=np.int64)
+        self.tolerant, self.errors = bool(tolerant), {}
+
+    def __len__(self):
+        return len(self.paths)
+
+    def load(self, i):
+        if not self.tolerant:
+            return _open_rgb(self.paths[i])
+        try:
+            return _open_rgb(self.paths[i])
+        except Exception as e:                          # noqa: BLE001 (PIL raises OSError, SyntaxError, ValueError, ... on damaged files)
+            self.errors[i] = f"{type(e).__name__}: {e}"
+            return np.zeros((1, 1, 3), dtype=np.uint8)
+
+
+def list_images(paths):
+    """The image files ``paths`` name, in order: a file as it is (whatever its extension), a directory walked recursively for
+    IMG_EXTENSIONS (case-insensitive) with directories and names sorted, as ImageFolder walks a class folder."""
+    out = []
+    for p in paths:
+        p = os.fspath(p)
+        if os.path.isdir(p):
+            for dirpath, _, fnames in sorted(os.walk(p, followlinks=True)):
+                out.extend(os.path.join(dirpath, f) for f in sorted(fnames) if f.lower().endswith(IMG_EXTENSIONS))
+        elif os.path.exists(p):
+            out.append(p)
+        else:
+            raise FileNotFoundError(f"{p}: no such file or directory")
+    return out
 
 
 def read_cifar(root, name, train):
@@ -245,6 +290,10 @@ def _grow_pinned(t, nbytes):
 class DeviceLoader:
     """Batches of (x float32 [B, 3, S, S] on the GPU, target int64 on the GPU).
 
+    output="image" (default): x as above.  output="patches": x is the batch's patch rows instead, [B * (S / patch_size)^2,
+    3 * patch_size^2] in ``dtype`` (torch.bfloat16 or torch.float32) -- bit for bit ops.patchify of the image batch, written by the
+    resampler's last pass (uvc_image_prep_patches) without the float32 images in between; what a ViT forward takes as ``patches=``.
+
     train=True : RandomResizedCrop(S, scale, ratio) [+ RandomHorizontalFlip] + Normalize, DistributedSampler order (rank, world,
                  reshuffled by set_epoch), drop_last=False: the last batch is short.
     train=False: every sample in order; eval="center": Resize(eval_resize_side(S, crop_pct)) + CenterCrop(S) (ImageNet: 256 / 224
@@ -256,10 +305,21 @@ class DeviceLoader:
 
     def __init__(self, dataset, batch_size, img_size, train=True, mean=IMAGENET_MEAN, std=IMAGENET_STD, scale=(0.08, 1.0),
                  ratio=(3.0 / 4.0, 4.0 / 3.0), flip=True, eval="center", seed=0, rank=0, world=1, num_workers=4, device=None, ahead=2,
-                 interpolation="bilinear", crop_pct=None):
+                 interpolation="bilinear", crop_pct=None, output="image", patch_size=None, dtype=None):
         from . import ops
         if eval not in ("center", "square"):
             raise ValueError(eval)
+        if output not in ("image", "patches"):
+            raise ValueError(f"output must be 'image' or 'patches', not {output!r}")
+        self.output, self.patch_size, self.dtype = output, None, torch.float32
+        if output == "patches":
+            if patch_size is None or int(patch_size) <= 0 or int(img_size) % int(patch_size):
+                raise ValueError(f"output='patches' needs a patch_size that divides img_size {img_size}, not {patch_size!r}")
+            if dtype not in (torch.bfloat16, torch.float32):
+                raise ValueError(f"output='patches' needs dtype torch.bfloat16 or torch.float32, not {dtype!r}")
+            self.patch_size, self.dtype = int(patch_size), dtype
+        elif patch_size is not None or dtype is not None:
+            raise ValueError("patch_size and dtype belong to output='patches'")
         self.interpolation, self.crop_pct = interpolation, crop_pct
         self.filter = ops.image_filter(interpolation)
         self.eval_side = eval_resize_side(int(img_size), crop_pct)
@@ -401,8 +461,18 @@ class DeviceLoader:
         """With the consumer's stream current, after the upload: the three launches into x.  Returns the batch's target."""
         from . import ops
         target, src, desc = up
-        ops.image_prep(src[:max(slot.src_bytes, 1)], desc, ws, x, self.mean, self.std, self.filter)
+        if self.output == "patches":
+            ops.image_prep_patches(src[:max(slot.src_bytes, 1)], desc, ws, x, self.patch_size, self.S, self.mean, self.std, self.filter)
+        else:
+            ops.image_prep(src[:max(slot.src_bytes, 1)], desc, ws, x, self.mean, self.std, self.filter)
         return target
+
+    def _new_batch(self, B):
+        """The uninitialised output of one batch of B images."""
+        if self.output == "patches":
+            P = self.patch_size
+            return torch.empty(B * (self.S // P) ** 2, 3 * P * P, dtype=self.dtype, device=self.device)
+        return torch.empty(B, 3, self.S, self.S, dtype=torch.float32, device=self.device)
 
     def __iter__(self):
         idx = self.indices()
@@ -433,7 +503,7 @@ class DeviceLoader:
                     uploaded.record(self._copy_stream)
                 main.wait_event(uploaded)
                 ws = torch.empty(max(slot.ws_bytes, 16), dtype=torch.uint8, device=self.device)
-                x = torch.empty(B, 3, self.S, self.S, dtype=torch.float32, device=self.device)
+                x = self._new_batch(B)
                 with torch.cuda.stream(main):
                     target = self._launch(slot, up, ws, x)
                 for buf in up:

@@ -539,6 +539,51 @@ def image_prep(src, desc_dev, workspace, out, mean=(0.0, 0.0, 0.0), std=(1.0, 1.
     return out
 
 
+def image_prep_patches(src, desc_dev, workspace, out, P, S, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), filter=0):
+    """out[B * (S/P)^2, 3 * P * P] (float32 or bfloat16) = the patch rows ``patchify`` makes of ``image_prep``'s float32 batch, bit for
+    bit, written by the resampler's last pass without the batch in between (uvc_image_prep_patches) -- three launches.  ``desc_dev`` and
+    ``workspace`` are image_prep's (the descriptors completed by image_prep_workspace for the same filter)."""
+    _chk(src, desc_dev, workspace, out)
+    if src.dtype != torch.uint8 or desc_dev.dtype != torch.uint8 or workspace.dtype != torch.uint8:
+        raise L.UvcHipError("image_prep_patches: src, desc and workspace are byte tensors")
+    P, S = int(P), int(S)
+    if out.dtype not in (torch.float32, torch.bfloat16):
+        raise L.UvcHipError("image_prep_patches: out must be float32 or bfloat16")
+    B = desc_dev.numel() // C.sizeof(L.uvc_image_desc)
+    if desc_dev.numel() != B * C.sizeof(L.uvc_image_desc) or out.numel() != B * 3 * S * S:
+        raise L.UvcHipError("image_prep_patches: out must hold [B * (S/P)^2, 3 * P * P] elements for the B descriptors")
+    if P > 0 and S % P == 0 and tuple(out.shape) != (B * (S // P) ** 2, 3 * P * P):     # (a P that does not divide S is the library's refusal)
+        raise L.UvcHipError("image_prep_patches: out must be [B * (S/P)^2, 3 * P * P]")
+    a = L.uvc_image_prep_args()
+    a.src, a.src_bytes, a.desc = L.ptr(src), src.numel(), L.ptr(desc_dev)
+    a.workspace, a.workspace_bytes, a.out = L.ptr(workspace), workspace.numel(), L.ptr(out)
+    a.mean[:], a.std[:] = [float(v) for v in mean], [float(v) for v in std]
+    a.B, a.S, a.filter = B, S, int(filter)
+    L.check(L.lib().uvc_image_prep_patches(C.byref(a), P, UVC_F32 if out.dtype == torch.float32 else UVC_BF16, L.cur_stream()),
+            "uvc_image_prep_patches")
+    return out
+
+
+def image_prep_patches_workspace(desc, S: int, src_bytes: int, filter=None) -> int:
+    """The workspace query of image_prep_patches: image_prep_workspace's (the patch-row store needs nothing more)."""
+    return image_prep_workspace(desc, S, src_bytes, filter)
+
+
+def logits_topk(logits, k, n_valid=None):
+    """(probs float32 [B, k], index int32 [B, k]) of float32 ``logits`` [B, ld]: softmax over columns [0, n_valid) (default: all), the k
+    largest in descending order, equal values by ascending index (uvc_logits_topk)."""
+    _chk(logits)
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise L.UvcHipError("logits_topk: logits must be float32 [B, ld]")
+    B, ld = logits.shape
+    n_valid = ld if n_valid is None else int(n_valid)
+    k = int(k)
+    probs = torch.empty(B, max(k, 0), dtype=torch.float32, device=logits.device)
+    index = torch.empty(B, max(k, 0), dtype=torch.int32, device=logits.device)
+    L.check(L.lib().uvc_logits_topk(L.ptr(logits), B, ld, n_valid, k, L.ptr(probs), L.ptr(index), L.cur_stream()), "uvc_logits_topk")
+    return probs, index
+
+
 def image_crop_desc_dtype():
     """numpy dtype with the layout of uvc_image_crop_desc: a crop window inside an image of a resident store."""
     import numpy as np

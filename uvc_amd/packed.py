@@ -269,6 +269,8 @@ class ResidentLoader(DeviceLoader):
     def __init__(self, dataset, batch_size, img_size, *args, **kw):
         from . import ops
         super().__init__(dataset, batch_size, img_size, *args, **kw)
+        if self.output != "image":
+            raise NotImplementedError("ResidentLoader yields image batches only (output='patches' is DeviceLoader's)")
         if self._pool is not None:                               # nothing is decoded or sliced here: no worker threads
             self._pool.shutdown()
             self._pool = None
