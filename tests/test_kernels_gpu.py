@@ -218,7 +218,8 @@ def test_attention_fwd_bwd(dtype, B, N, H):
 
 
 @pytest.mark.parametrize("B,N,H,grid,bias", [(2, 197, 3, 0, True), (7, 197, 3, 3, True), (5, 198, 3, 2, False), (3, 193, 3, 0, True), (2, 208, 3, 1, True),
-                                             (3, 197, 6, 0, True), (5, 197, 6, 4, False), (2, 198, 6, 3, True)])
+                                             (3, 197, 6, 0, True), (5, 197, 6, 4, False), (2, 198, 6, 3, True),
+                                             (2, 200, 3, 0, True), (3, 207, 3, 2, True), (2, 207, 6, 0, False)])     # 207: the upper end of the N / 16 == 12 branch
 def test_qkv_attention_forward_fused_equals_the_two_kernels(B, N, H, grid, bias):
     """uvc_qkv_attention_fwd (the qkv Linear + attention forward as one persistent kernel, r5) against uvc_gemm_nt (bias epilogue) + uvc_attention_fwd on the
     same inputs: o, lse and the stored qkv BIT for bit (same accumulation chain, same rounding points), with and without storing qkv, several images per

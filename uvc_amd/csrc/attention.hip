@@ -532,9 +532,11 @@ __global__ __launch_bounds__(512) void k_attn_bwd_dq(AttnArgs a) {
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          // padded keys need no mask here: their K rows are zero in LDS, so their (finite) ds only ever multiplies zeros in
-          // dq += ds . K (masking cost two compares / selects per score on every tile)
-          const float p = __builtin_amdgcn_exp2f(c[e] * c2 - lse2);
+          // padded keys need no mask here: their K rows are zero in LDS, so their ds only ever multiplies zeros in dq += ds . K
+          // (masking cost two compares / selects per score on every tile) -- as long as that ds is FINITE: their p is exp(-lse),
+          // +inf in float32 for a row whose scaled scores all lie below -88.7, and inf . 0 in the MFMA made the whole dq row NaN.
+          // The exponent of a real key is never positive (lse >= s), so the clamp is exact for them and bounds p of a padded key by 1.
+          const float p = __builtin_amdgcn_exp2f(fminf(c[e] * c2 - lse2, 0.f));
           ds[u][e] = p * ((dp[e] - dl) * a.scale);
         }
       }

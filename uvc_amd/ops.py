@@ -96,8 +96,10 @@ def _attn_args(qkv, o, lse, B, N, H, dtype, dout=None, dqkv=None, delta=None):
     return a
 
 
-def attention_fwd(qkv, o, lse, B, N, H, dtype, head_keep=None):
+def attention_fwd(qkv, o, lse, B, N, H, dtype, head_keep=None, v_dim=0):
+    """v_dim 16 / 32 / 48: the compact layout (include/uvc_kernels.h: uvc_attn_args.v_dim), qkv rows [q H*64 | k H*64 | v H*v_dim], o [B, N, H*v_dim]."""
     a = _attn_args(qkv, o, lse, B, N, H, dtype)
+    a.v_dim = int(v_dim)
     if head_keep is not None:
         _chk(head_keep)
         a.head_keep = L.ptr(head_keep)
