@@ -137,6 +137,22 @@ int uvc_attention_bwd(const uvc_attn_args* args, void* stream);
  * kernels uvc_attention_bwd(variant = 1) launches.  head_keep set, or N > 256 (whatever v_dim): UVC_ERR_UNSUPPORTED. */
 int uvc_attention_bwd_vdim(const uvc_attn_args* args, void* stream);
 
+/* One step of attention rollout (Abnar & Zuidema 2020) seen from the readout token(s): a row vector over the tokens pushed back through one
+ * attention block, r_out = keep * r_in + (mix / H) * sum_h P_h^T r_in, with P recomputed from q, k and the forward's lse -- no [N, N] matrix
+ * exists anywhere.  1 <= N <= 1026 (UVC_ERR_UNSUPPORTED beyond), head_dim 64, v_dim 16 / 32 / 48 / 64 (it only sets the row stride), UVC_F32 or
+ * UVC_BF16 operands; r and the sums are float32.  No atomics: every r_out element has one writer, the result is bit-identical on a repeat and
+ * independent of the batch an image sits in.  Null pointers, overlapping r_in / r_out, a bad dtype or v_dim, an empty problem: UVC_ERR_ARG. */
+typedef struct uvc_attn_rollout_args {
+  const void* qkv;      /* T [B, N, H*(128 + v_dim)], rows [q H*64 | k H*64 | v H*v_dim] (the compact layout; v is not read) */
+  const float* lse;     /* [B, H, N], as uvc_attention_fwd wrote it (natural log) */
+  const float* r_in;    /* [B, N] */
+  float* r_out;         /* [B, N], must not overlap r_in */
+  int32_t B, N, H, head_dim, v_dim, dtype;
+  float scale, keep, mix;
+} uvc_attn_rollout_args;
+/* r_out[b,j] = keep * r_in[b,j] + (mix / H) * sum_h sum_i r_in[b,i] * exp(scale * q[b,h,i].k[b,h,j] - lse[b,h,i]) */
+int uvc_attention_rollout_step(const uvc_attn_rollout_args* a, void* stream);
+
 /* The qkv Linear and the attention forward of a block as ONE kernel (UVC/models/model_distilled.py:175-185: `self.qkv(x)` ... `attn @ v`):
  * h [B*N, D] (the LayerNorm-1 rows) and the qkv weight [3D, D] in, o [B,N,H*64] and lse out; qkv [B,N,3,H,64] is written only when the
  * pointer is given (the backward needs it; a no-grad forward does not).  Same bits as uvc_gemm_nt (UVC_EPI_BIAS) + uvc_attention_fwd.

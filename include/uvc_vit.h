@@ -179,6 +179,16 @@ int uvc_vit_compact_update_shadows(const uvc_vit_cfg* cfg, const uvc_compact_blo
  * Reads io->params, shadow (bf16), workspace, x, logits, logits_dist, patch_mask (optional device [B, P]), patches_in (optional), batch;
  * the other members are ignored.  cfg.dtype UVC_F32 or UVC_BF16 (cfg.resid_f32 = 0). */
 int uvc_vit_compact_forward(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* stream);
+/* Attention rollout maps (Abnar & Zuidema 2020) of the readout token(s): uvc_vit_compact_forward with qkv and lse of every attention block kept
+ * (workspace of uvc_vit_compact_rollout_workspace_bytes; io as for the forward, and logits / logits_dist are its bits), then a row vector pushed
+ * back through the attention blocks, last block first, by uvc_attention_rollout_step (uvc_kernels.h).  rollout: device float32 [B, N] over
+ * the model's tokens (class, distillation, patches), every row sums to 1.  The start vector is uniform over the readout tokens (1 on token
+ * 0; 1/2 and 1/2 on tokens 0 and 1 with the distillation token, as the eval logits average the two heads).  method 0: rollout,
+ * r <- r/2 + (1/2H) sum_h P_h^T r per block; method 1: "last", r <- (1/H) sum_h P_h^T r of the last attention block alone -- the head-mean
+ * attention of the readout tokens.  A block without heads is the identity.  N <= 1026, UVC_F32 or UVC_BF16; deterministic. */
+int64_t uvc_vit_compact_rollout_workspace_bytes(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int32_t batch);
+int uvc_vit_compact_rollout(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, float* rollout,
+                            int32_t method, void* stream);
 
 /* ---- fine-tuning a compact model at its kept widths (uvc_amd/compact_train.py) ----
  * One flat float32 parameter buffer serves eval and training, and a gradient buffer congruent with it: `off` is uvc_vit_compact_layout's.

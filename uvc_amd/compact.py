@@ -17,11 +17,14 @@ zero ``b1`` and zero fc2 columns (GELU(0) = 0 meets a zero column).
     python -m uvc_amd.compact eval --compact model.compact.pt [--synthetic 0 --dataset ... --data_dir ...]
     python -m uvc_amd.compact finetune --compact model.compact.pt --output tuned.compact.pt [Stage 2's flags]
     python -m uvc_amd.compact predict --compact model.compact.pt --images PATH [PATH ...] [--output preds.jsonl]
+    python -m uvc_amd.compact explain --compact model.compact.pt --images PATH [PATH ...] [--output maps.jsonl] [--overlay_dir DIR]
 
 ``reference_forward`` is the written spec of the format (plain PyTorch, CPU or GPU, any dtype); ``CompactVisionTransformer``
 runs it through ``uvc_vit_compact_forward`` (include/uvc_vit.h).  ``predict`` classifies image files with it (file -> eval transform -> patch rows -> compact forward -> softmax + top-k, all of it
 behind the decode on the device).  ``reference_logits`` is the same network with the two heads kept
 apart: the function ``compact_train.CompactTrainer`` fine-tunes (a fine-tuned file is an ordinary version-1 compact file).
+``explain`` adds to ``predict``'s records what the model looked at: the attention rollout of the readout token(s) over the patches
+(``uvc_vit_compact_rollout``; ``reference_rollout`` is its written spec).
 """
 from __future__ import annotations
 
@@ -184,6 +187,38 @@ def reference_logits(export: dict, x: torch.Tensor):
     """``(logits, logits_dist)`` of a compact model in plain PyTorch -- the two heads kept apart, as a training loss takes them
     (``logits_dist is logits`` without the distillation token).  Differentiable: state_dict tensors that already have x's dtype and
     device enter the graph as they are, so leaves with ``requires_grad`` receive the compact model's gradients."""
+    return _reference_walk(export, x)[:2]
+
+
+METHODS = ("rollout", "last")
+
+
+def reference_rollout(export: dict, x: torch.Tensor, method: str = "rollout") -> torch.Tensor:
+    """Attention rollout (Abnar & Zuidema 2020) of a compact model's readout token(s) in plain PyTorch: float64 ``[B, N]`` over the
+    tokens (class, distillation, patches), every row a probability vector.  The network and its block loop are ``reference_logits``'
+    (in x's dtype); per attention block A_l is the mean of the kept heads' materialised softmax, and the class-token row of
+    ``(A_L + I) / 2 ... (A_1 + I) / 2`` is the row vector ``r <- r / 2 + r A_l / 2`` pushed back from the last block to the first, in
+    float64.  It starts uniform over the readout tokens (token 0; tokens 0 and 1 with the distillation token, whose two heads the eval
+    logits average).  A block without heads has no attention: the identity.  ``method="last"``: ``r A_L`` of the last attention
+    block alone, the head-mean attention of the readout tokens."""
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, not {method!r}")
+    with torch.no_grad():
+        atts = _reference_walk(export, x, keep_attention=True)[2]
+    ntok = 2 if export["cfg"]["enable_dist"] else 1
+    r = torch.zeros(x.shape[0], _seq(export["cfg"]), dtype=torch.float64, device=x.device)
+    r[:, :ntok] = 1.0 / ntok
+    for a in reversed(atts):
+        ra = torch.einsum("bi,bij->bj", r, a.double())
+        if method == "last":
+            return ra
+        r = 0.5 * r + 0.5 * ra
+    return r
+
+
+def _reference_walk(export: dict, x: torch.Tensor, keep_attention: bool = False):
+    """The block loop behind ``reference_logits`` and ``reference_rollout``: ``(logits, logits_dist, atts)``; with ``keep_attention``
+    ``atts`` lists the head-mean softmax ``[B, N, N]`` of every block that has heads, in block order (else it is empty)."""
     check_export(export)
     cfg = export["cfg"]
     P = {k: v.to(device=x.device, dtype=x.dtype) for k, v in export["state_dict"].items()}
@@ -200,6 +235,7 @@ def reference_logits(export: dict, x: torch.Tensor):
     toks = [P["cls_token"].expand(B, -1, -1)] + ([P["dist_token"].expand(B, -1, -1)] if cfg["enable_dist"] else [])
     h = torch.cat(toks + [t], dim=1) + P["pos_embed"]
     N = h.shape[1]
+    atts = []
     for k, b in enumerate(export["blocks"]):
         p = f"blocks.{k}."
         nh, dv = len(b["heads"]), b["v_dim"]
@@ -210,6 +246,8 @@ def reference_logits(export: dict, x: torch.Tensor):
             kk = qkv[..., nh * 64:2 * nh * 64].reshape(B, N, nh, 64).transpose(1, 2)
             v = qkv[..., 2 * nh * 64:].reshape(B, N, nh, dv).transpose(1, 2)
             att = ((q @ kk.transpose(-2, -1)) * HEAD_DIM ** -0.5).softmax(dim=-1)
+            if keep_attention:
+                atts.append(att.mean(dim=1))
             o = (att @ v).transpose(1, 2).reshape(B, N, nh * dv)
             h = h + F.linear(o, P[p + "attn.proj.weight"], P[p + "attn.proj.bias"])
         else:                                                             # no kept head: the branch is proj.bias
@@ -223,7 +261,7 @@ def reference_logits(export: dict, x: torch.Tensor):
     h = F.layer_norm(h, (D,), P["norm.weight"], P["norm.bias"], eps)
     o = F.linear(h[:, 0], P["head.weight"], P["head.bias"])
     od = F.linear(h[:, 1], P["head_dist.weight"], P["head_dist.bias"]) if cfg["enable_dist"] else o
-    return o, od
+    return o, od, atts
 
 
 # ---- MAC bookkeeping (oracle/vit.py:mac_table with per-block widths) ------------------------------------------------------------
@@ -315,7 +353,7 @@ _SLOTS = ["norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "att
 
 
 def _bind():
-    """The library with the argument types of the ten compact entry points (include/uvc_vit.h, uvc_vit_compact_*) set."""
+    """The library with the argument types of the twelve compact entry points (include/uvc_vit.h, uvc_vit_compact_*) set."""
     from . import _lib as L
     from .model_distilled import uvc_vit_cfg, uvc_vit_io, uvc_vit_offsets, uvc_vit_shadow_offsets
     lib = L.lib()
@@ -324,9 +362,11 @@ def _bind():
         run = [C.POINTER(uvc_vit_io), C.c_void_p]
         tails = {"layout": [C.POINTER(uvc_vit_offsets), C.POINTER(uvc_vit_shadow_offsets)], "workspace_bytes": [C.c_int32],
                  "update_shadows": [C.c_void_p, C.c_void_p, C.c_void_p], "forward": run, "train_forward": run, "backward": run,
-                 "frozen_ranges": [C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]}
+                 "frozen_ranges": [C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)],
+                 "rollout": [C.POINTER(uvc_vit_io), C.c_void_p, C.c_int32, C.c_void_p]}
         for n in ("layout", "workspace_bytes", "update_shadows"):
             tails["train_" + n] = tails[n]
+        tails["rollout_workspace_bytes"] = tails["workspace_bytes"]
         for n, tail in tails.items():
             f = getattr(lib, "uvc_vit_compact_" + n)
             f.argtypes, f.restype = head + tail, C.c_int64 if n.endswith("workspace_bytes") else C.c_int
@@ -421,15 +461,18 @@ class _CompactModule(nn.Module):
         return patches.shape[0] // npatch
 
     def _workspace(self, B, training):
-        """One workspace per mode, for the last batch size seen."""
-        key = (B, bool(training))
+        """One workspace per mode (eval, training, or "rollout": the eval forward that keeps qkv and lse per block), for the last
+        batch size seen."""
+        mode = training if training == "rollout" else bool(training)
+        key = (B, mode)
         if key not in self._ws:
             from . import _lib as L
-            entry = "uvc_vit_compact_train_workspace_bytes" if training else "uvc_vit_compact_workspace_bytes"
+            entry = {False: "uvc_vit_compact_workspace_bytes", True: "uvc_vit_compact_train_workspace_bytes",
+                     "rollout": "uvc_vit_compact_rollout_workspace_bytes"}[mode]
             n = self._lib_call(entry, B)
             if n < 0:
                 L.check(-1, entry)
-            self._ws = {k: v for k, v in self._ws.items() if k[1] != bool(training)}
+            self._ws = {k: v for k, v in self._ws.items() if k[1] != mode}
             self._ws[key] = torch.empty(n, dtype=torch.uint8, device=self._flat.device)
         return self._ws[key]
 
@@ -448,12 +491,13 @@ class _CompactModule(nn.Module):
             ops.patch_gate_sigmoid(self._flat[o:o + P], mask, B, P, bool(c["patch_hard"]))
         io = uvc_vit_io()
         io.params, io.shadow, io.workspace, io.workspace_bytes = L.ptr(self._flat), L.ptr(self._shadow), L.ptr(ws), ws.numel()
-        io.x, io.patch_mask, io.batch, io.training = L.ptr(x), L.ptr(mask), B, int(training)
+        io.x, io.patch_mask, io.batch, io.training = L.ptr(x), L.ptr(mask), B, int(training is True)
         return io, mask
 
-    def _forward(self, x, training=False, patches=None):
+    def _forward(self, x, training=False, patches=None, rollout=None):
         """``(logits, logits_dist or None, what a backward needs of the pass)`` through the eval or the training forward.  ``patches``
-        (eval only, in place of ``x``): the batch's patch rows, which the forward then does not make itself."""
+        (eval only, in place of ``x``): the batch's patch rows, which the forward then does not make itself.  ``rollout`` (eval only;
+        0 = rollout, 1 = last): the pass goes through ``uvc_vit_compact_rollout`` and its maps, float32 [B, N], come back as ``"maps"``."""
         from . import _lib as L
         dev = self._flat.device
         if patches is not None:
@@ -463,19 +507,25 @@ class _CompactModule(nn.Module):
         else:
             x = self._prep(x)
             B = x.shape[0]
+        if rollout is not None and training:
+            raise ValueError("rollout maps come from the eval forward")
         self._refresh_shadows()
-        io, mask = self._io(x, B, training)
+        io, mask = self._io(x, B, "rollout" if rollout is not None else bool(training))
         io.patches_in = L.ptr(patches)                  # (None: the forward rearranges x itself)
         nc = self._export["cfg"]["num_classes"]
         logits = torch.empty(B, nc, device=dev)
         logits_dist = torch.empty(B, nc, device=dev) if self.num_tokens == 2 else None
         io.logits, io.logits_dist = L.ptr(logits), L.ptr(logits_dist)
+        if rollout is not None:
+            maps = torch.empty(B, _seq(self._export["cfg"]), device=dev)
+            L.check(self._lib_call("uvc_vit_compact_rollout", C.byref(io), L.ptr(maps), int(rollout), L.cur_stream()), "uvc_vit_compact_rollout")
+            return logits, logits_dist, dict(x=x, B=B, mask=mask, maps=maps)
         entry = "uvc_vit_compact_train_forward" if training else "uvc_vit_compact_forward"
         L.check(self._lib_call(entry, C.byref(io), L.cur_stream()), entry)
         return logits, logits_dist, dict(x=x, B=B, mask=mask)
 
     @torch.no_grad()
-    def _eval_logits(self, x, patches=None):
+    def _eval_logits(self, x=None, patches=None):
         """The eval logits: ``(x + x_dist) / 2`` with the distillation token."""
         o, od, _ = self._forward(x, patches=patches)
         return o if od is None else (o + od) / 2
@@ -501,11 +551,22 @@ class CompactVisionTransformer(_CompactModule):
         logits = self._eval_logits(x, patches)
         return logits, self.macs(logits.shape[0])
 
+    @torch.no_grad()
+    def rollout(self, x=None, *, patches=None, method="rollout"):
+        """``(eval logits, maps)``: the logits are ``forward``'s bit for bit; ``maps`` float32 [B, N] is the attention rollout of the
+        readout token(s) over the model's tokens (``reference_rollout`` is the spec; ``method`` "rollout" or "last"), every row sums
+        to 1.  Inputs as ``forward`` takes them."""
+        if method not in METHODS:
+            raise ValueError(f"method must be one of {METHODS}, not {method!r}")
+        o, od, kept = self._forward(x, patches=patches, rollout=METHODS.index(method))
+        return (o if od is None else (o + od) / 2), kept["maps"]
+
 
 # ---- classify image files -------------------------------------------------------------------------------------------------------
 MAX_TOPK = 16                                       # uvc_logits_topk's limit
 FUSED_INPUT_DEFAULT = 1                             # decided by tools/predict_time.py's rounds (README "Classify images")
 PRESETS = ("imagenet", "cifar")
+OVERLAY_ALPHA = 160                                 # opacity (of 255) of the red layer where the patch map has its maximum
 
 
 def read_classes(path) -> List[str]:
@@ -532,18 +593,9 @@ def topk_reference(logits, k, n_valid=None):
     return np.take_along_axis(p, index, axis=1), index.astype(np.int32)
 
 
-def predict(model, files, *, topk=5, batch_size=64, preset="imagenet", interpolation="bilinear", crop_pct=None, num_labels=None, classes=None,
-            num_workers=8, fused_input=bool(FUSED_INPUT_DEFAULT)):
-    """Classify image files with a ``CompactVisionTransformer``: yields one record per file, in input order,
-    ``{"file", "top": [{"index", "label", "prob"}, ...]}`` with the ``topk`` most probable labels first, or ``{"file", "error"}`` for a file
-    that cannot be read (the run goes on).
-
-    preset "imagenet": Resize(eval_resize_side(S, crop_pct)) + CenterCrop(S) with ImageNet's mean / std, ``build_loaders``' test transform;
-    "cifar": Resize((S, S)) with 0.5 / 0.5.  ``interpolation`` / ``crop_pct`` as the loaders take them.  The softmax runs over the first
-    ``num_labels`` logits (default: ``len(classes)``, else the model's num_classes), so the padding logits of a 16 / 104-wide CIFAR head
-    are never reported; ``classes`` names them (``label`` is None without).  ``fused_input``: the resampler writes the patch rows the
-    forward reads (uvc_image_prep_patches); False: it writes the float32 images and the forward rearranges them (uvc_image_prep +
-    uvc_patchify) -- the same records bit for bit.  ``files``: paths, or a dataset with ``load(i)`` / ``targets`` (records then name indices)."""
+def _classify(model, files, method, overlay_dir, topk, batch_size, preset, interpolation, crop_pct, num_labels, classes, num_workers, fused_input):
+    """The generator behind ``predict`` (``method`` None) and ``explain``: the checked arguments, the tolerant dataset over ``files``,
+    the preset's eval loader, the forward (with the rollout maps when a method is given), top-k, one record per file."""
     from . import data, ops
     if preset not in PRESETS:
         raise ValueError(f"preset must be one of {PRESETS}, not {preset!r}")
@@ -568,27 +620,97 @@ def predict(model, files, *, topk=5, batch_size=64, preset="imagenet", interpola
         kw.update(output="patches", patch_size=c["patch_size"], dtype=ops.tdtype(model._cfg.dtype))
     loader = data.DeviceLoader(ds, int(batch_size), c["img_size"], train=False, num_workers=num_workers, device=dev, interpolation=interpolation,
                                crop_pct=crop_pct, **kw)
+    g = c["img_size"] // c["patch_size"]
+    ntok = 2 if c["enable_dist"] else 1
+    if overlay_dir is not None:
+        import os
+        os.makedirs(overlay_dir, exist_ok=True)
 
-    def records(first, probs, index):
+    def records(first, probs, index, maps):
         for b, (pr, ix) in enumerate(zip(probs.tolist(), index.tolist())):
             i = first + b
             if i in errors:
                 yield dict(file=names[i], error=errors[i])
-            else:
-                yield dict(file=names[i], top=[dict(index=j, label=None if classes is None else classes[j], prob=q) for j, q in zip(ix, pr)])
+                continue
+            rec = dict(file=names[i], top=[dict(index=j, label=None if classes is None else classes[j], prob=q) for j, q in zip(ix, pr)])
+            if maps is not None:
+                row = maps[b].tolist()
+                rec.update(grid=[g, g], tokens=row[:ntok], map=row[ntok:])
+                if overlay_dir is not None:
+                    write_overlay(overlay_dir, i, names[i], ds.load(i), maps[b, ntok:].reshape(g, g).numpy(), c["img_size"], preset, interpolation, crop_pct)
+            yield rec
 
     # the records of a batch are read back after the next batch's launches, so the device does not idle behind the host
     first, pending = 0, None
+    host = lambda t: None if t is None else t.cpu()
     with torch.cuda.device(dev):
         for x, _ in loader:
-            logits = model._eval_logits(None, x) if fused_input else model._eval_logits(x)
+            inp = dict(patches=x) if fused_input else dict(x=x)
+            logits, maps = (model._eval_logits(**inp), None) if method is None else model.rollout(method=method, **inp)
             probs, index = ops.logits_topk(logits, topk, num_labels)
             if pending is not None:
-                yield from records(pending[0], pending[1].cpu(), pending[2].cpu())
-            pending = (first, probs, index)
+                yield from records(pending[0], pending[1].cpu(), pending[2].cpu(), host(pending[3]))
+            pending = (first, probs, index, maps)
             first += len(probs)
         if pending is not None:
-            yield from records(pending[0], pending[1].cpu(), pending[2].cpu())
+            yield from records(pending[0], pending[1].cpu(), pending[2].cpu(), host(pending[3]))
+
+
+def write_overlay(overlay_dir, index, name, pixels, patch_map, img_size, preset="imagenet", interpolation="bilinear", crop_pct=None):
+    """``<overlay_dir>/<index>_<basename>.png``, img_size x img_size: the model's own view of the image (the preset's resize and centre
+    crop, or square resize, done with PIL) with the patch map -- divided by its maximum, upsampled bilinearly -- blended in in red.
+    ``pixels``: uint8 [H, W, 3]; ``patch_map``: [g, g] non-negative.  Returns the path."""
+    import os
+    import numpy as np
+    from PIL import Image
+    from . import data
+    S = int(img_size)
+    im = Image.fromarray(np.ascontiguousarray(pixels))
+    resample = data._pil_filter(interpolation)
+    if preset == "cifar":
+        im = im.resize((S, S), resample)
+    else:
+        rh, rw = data.resize_short_side(pixels.shape[0], pixels.shape[1], data.eval_resize_side(S, crop_pct))
+        im = im.resize((rw, rh), resample)
+        y0, x0 = data.center_crop_offset(rh, rw, S)
+        im = im.crop((x0, y0, x0 + S, y0 + S))
+    m = np.asarray(patch_map, dtype=np.float64)
+    top = float(m.max())
+    m = m / top if top > 0 else np.zeros_like(m)
+    alpha = Image.fromarray(np.round(m * 255).astype(np.uint8), "L").resize((S, S), Image.BILINEAR)
+    alpha = alpha.point(lambda v: v * OVERLAY_ALPHA // 255)
+    out = Image.composite(Image.new("RGB", (S, S), (255, 0, 0)), im.convert("RGB"), alpha)
+    path = os.path.join(overlay_dir, f"{index}_{os.path.basename(str(name))}.png")
+    out.save(path)
+    return path
+
+
+def predict(model, files, *, topk=5, batch_size=64, preset="imagenet", interpolation="bilinear", crop_pct=None, num_labels=None, classes=None,
+            num_workers=8, fused_input=bool(FUSED_INPUT_DEFAULT)):
+    """Classify image files with a ``CompactVisionTransformer``: yields one record per file, in input order,
+    ``{"file", "top": [{"index", "label", "prob"}, ...]}`` with the ``topk`` most probable labels first, or ``{"file", "error"}`` for a file
+    that cannot be read (the run goes on).
+
+    preset "imagenet": Resize(eval_resize_side(S, crop_pct)) + CenterCrop(S) with ImageNet's mean / std, ``build_loaders``' test transform;
+    "cifar": Resize((S, S)) with 0.5 / 0.5.  ``interpolation`` / ``crop_pct`` as the loaders take them.  The softmax runs over the first
+    ``num_labels`` logits (default: ``len(classes)``, else the model's num_classes), so the padding logits of a 16 / 104-wide CIFAR head
+    are never reported; ``classes`` names them (``label`` is None without).  ``fused_input``: the resampler writes the patch rows the
+    forward reads (uvc_image_prep_patches); False: it writes the float32 images and the forward rearranges them (uvc_image_prep +
+    uvc_patchify) -- the same records bit for bit.  ``files``: paths, or a dataset with ``load(i)`` / ``targets`` (records then name indices)."""
+    yield from _classify(model, files, None, None, topk, batch_size, preset, interpolation, crop_pct, num_labels, classes, num_workers, fused_input)
+
+
+def explain(model, files, *, method="rollout", overlay_dir=None, topk=5, batch_size=64, preset="imagenet", interpolation="bilinear", crop_pct=None,
+            num_labels=None, classes=None, num_workers=8, fused_input=bool(FUSED_INPUT_DEFAULT)):
+    """``predict``'s records plus what the model looked at: ``"grid": [g, g]`` (patches per side), ``"tokens"``: the map's mass on the
+    readout token(s) ``[r_cls(, r_dist)]``, ``"map"``: g * g floats, row-major, the mass on every patch -- ``CompactVisionTransformer.rollout``
+    with ``method`` "rollout" or "last"; tokens and map sum to 1.  A file that cannot be read stays ``{"file", "error"}``.
+    ``overlay_dir``: one PNG per readable image (``write_overlay``), named ``<running index>_<basename>.png``.  The other keywords are
+    ``predict``'s."""
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, not {method!r}")
+    yield from _classify(model, files, method, overlay_dir, topk, batch_size, preset, interpolation, crop_pct, num_labels, classes, num_workers,
+                         fused_input)
 
 
 def _int_in(lo, hi, what):
@@ -610,7 +732,8 @@ def _crop_pct_arg(v):
 
 
 def predict_command(args, dev):
-    """``predict``: one JSON line per image to --output (or stdout), then the summary line ``{"images", "errors", "batches", "img_per_s"}``."""
+    """``predict`` and ``explain``: one JSON line per image to --output (or stdout), then the summary line
+    ``{"images", "errors", "batches", "img_per_s"}``."""
     import sys
     import time
     from . import data
@@ -622,9 +745,10 @@ def predict_command(args, dev):
     n = nerr = 0
     t0 = time.perf_counter()
     try:
-        for rec in predict(cm, files, topk=args.topk, batch_size=args.batch_size, preset=args.preset, interpolation=args.interpolation,
-                           crop_pct=args.crop_pct, num_labels=args.num_labels, classes=classes, num_workers=args.num_workers,
-                           fused_input=bool(args.fused_input)):
+        kw = dict(topk=args.topk, batch_size=args.batch_size, preset=args.preset, interpolation=args.interpolation, crop_pct=args.crop_pct,
+                  num_labels=args.num_labels, classes=classes, num_workers=args.num_workers, fused_input=bool(args.fused_input))
+        recs = explain(cm, files, method=args.method, overlay_dir=args.overlay_dir, **kw) if args.cmd == "explain" else predict(cm, files, **kw)
+        for rec in recs:
             out.write(json.dumps(rec) + "\n")
             n += 1
             nerr += "error" in rec
@@ -669,9 +793,19 @@ def _parser():
     f.add_argument("--compact", required=True, help="the compact file to fine-tune")
     f.add_argument("--output", required=True, help="where the best model (validation top-1) is written, a version-1 compact file")
     add_stage2_flags(f, skip=("checkpoint_dir", "eval_only"))
-    # classify image files with a compact file
+    # classify image files with a compact file; `explain` adds the attention rollout maps to the records
+    for name in ("predict", "explain"):
+        _add_predict_flags(sub.add_parser(name))
+    x = sub.choices["explain"]
+    x.add_argument("--method", choices=list(METHODS), default="rollout",
+                   help="rollout: the readout tokens' attention rolled back through every block; last: their head-mean attention in the last block")
+    x.add_argument("--overlay_dir", default=None, help="write <index>_<basename>.png per readable image: the model's view with the map in red")
+    return p
+
+
+def _add_predict_flags(q):
+    """``predict``'s flags; ``explain`` takes the same ones with the same defaults."""
     from .data import INTERPOLATIONS
-    q = sub.add_parser("predict")
     q.add_argument("--compact", required=True, help="the compact file (a dense checkpoint goes through `export` first)")
     q.add_argument("--images", nargs="+", required=True, help="image files, or directories walked recursively for image files (sorted)")
     q.add_argument("--output", default=None, help="JSON-lines file; default: stdout")
@@ -689,7 +823,6 @@ def _parser():
                    help="the valid logits (the rest of the head is padding); default: the length of --classes, else the file's num_classes")
     q.add_argument("--fused_input", type=int, default=FUSED_INPUT_DEFAULT,
                    help="1: the resampler writes the patch rows (uvc_image_prep_patches); 0: images, then uvc_patchify")
-    return p
 
 
 def _dense_model(args, dev):
@@ -748,7 +881,7 @@ def main(argv=None):
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
     if args.cmd == "finetune":
         return finetune(args, dev)
-    if args.cmd == "predict":
+    if args.cmd in ("predict", "explain"):
         return predict_command(args, dev)
     if args.cmd == "export" or not args.compact:
         model = _dense_model(args, dev)

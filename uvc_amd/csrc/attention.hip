@@ -1489,6 +1489,104 @@ __global__ __launch_bounds__(512) void k_attn_bwd_dkv_long(AttnArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Attention rollout, one step (uvc_attention_rollout_step): r_out = keep * r_in + (mix / H) * sum_h P_h^T r_in, the row vector of the readout
+// token(s) pushed back through one block.  P_h^T r is the dV product of k_attn_bwd_dkv_long with dO replaced by one scalar per query: P is
+// recomputed from q, k and lse as there, V and dO are not read and the second MFMA becomes a multiply-add per score.  One workgroup of 8 waves per
+// (image, block of LQ = 128 keys) walks ALL heads, so the head sum stays in a register and every output element has one writer: no atomics, the
+// same bits on a repeat and in any batch.  Per head each wave holds its 16 keys' K fragments (those of the next head are fetched under the last Q
+// tile of the current one); the Q tiles of LK = 64 rows stream through the double buffer with lse * log2(e) (+inf on padded queries: p = 0) and r
+// (0 there).  A lane (key li, group g) sums p * r over the queries 4g .. 4g+3 of every tile; the four groups of a key are added once at the end.
+// Padded keys (zero K fragments) may hold anything, inf and NaN included: their lanes share no sum with a real key's and are not written.
+struct RolloutArgs {
+  const void* qkv; const float* lse; const float* r_in; float* r_out;
+  int B, N, H, v_dim;
+  float scale, keep, mix;
+};
+
+template <typename T>
+__global__ __launch_bounds__(512) void k_attn_rollout_step(RolloutArgs a) {
+  typedef Mma<T> MM;
+  typedef Geom<T> G;
+  typedef LongTile<T> LT;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int BUF = LT::BYTES + 2 * LK * (int)sizeof(float);       // Q, lse, r
+  const int nkb = (a.N + LQ - 1) / LQ;
+  const int kblk = blockIdx.x % nkb, b = blockIdx.x / nkb;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
+  const size_t ldq = (size_t)a.H * (2 * HD + a.v_dim);
+  const T* qb = reinterpret_cast<const T*>(a.qkv) + (size_t)b * a.N * ldq;      // q of head 0; head h: + h * HD, its k: + (H + h) * HD
+  const float* lse = a.lse + (size_t)b * a.H * a.N;
+  const float* rin = a.r_in + (size_t)b * a.N;
+  const int key = kblk * LQ + w * 16 + li;
+  const float c2 = a.scale * 1.44269504088896340736f;
+  // threads 0 .. LK-1 carry lse * log2(e) of head h, LK .. 2 LK-1 the r of the same queries
+  auto ld_row = [&](int h, int r0) -> float {
+    const int i = r0 + ((int)threadIdx.x & (LK - 1));
+    if (threadIdx.x < LK) return i < a.N ? lse[(size_t)h * a.N + i] * 1.44269504088896340736f : INFINITY;
+    return i < a.N ? rin[i] : 0.f;
+  };
+  auto ld_k = [&](typename MM::Frag (&f)[G::KS], int h) {
+#pragma unroll
+    for (int ks = 0; ks < G::KS; ++ks) f[ks] = row_frag_global<T>(qb + (a.H + h) * HD, ldq, key, a.N, ks * 4 + g);
+  };
+  typename MM::Frag kf[G::KS], kn[G::KS];
+  ld_k(kn, 0);
+  u32x4 pq[LT::NCL];
+  float pr = 0.f;
+  LT::load(pq, qb, ldq, 0, a.N);
+  if (threadIdx.x < 2 * LK) pr = ld_row(0, 0);
+  LT::store(smem, pq);
+  if (threadIdx.x < 2 * LK) reinterpret_cast<float*>(smem + LT::BYTES)[threadIdx.x] = pr;
+  __syncthreads();
+  const int nqt = (a.N + LK - 1) / LK;
+  float acc = 0.f;
+  int it = 0;
+  for (int h = 0; h < a.H; ++h) {
+#pragma unroll
+    for (int ks = 0; ks < G::KS; ++ks) kf[ks] = kn[ks];
+    for (int j = 0; j < nqt; ++j, ++it) {
+      const char* sQ = smem + (it & 1) * BUF;
+      const float* sLse = reinterpret_cast<const float*>(sQ + LT::BYTES);
+      const float* sR = sLse + LK;
+      const bool last = j + 1 == nqt;
+      const int h1 = last ? h + 1 : h, j1 = last ? 0 : j + 1;          // the tile behind this one
+      if (h1 < a.H) {
+        LT::load(pq, qb + h1 * HD, ldq, j1 * LK, a.N);
+        if (threadIdx.x < 2 * LK) pr = ld_row(h1, j1 * LK);
+        if (last) ld_k(kn, h1);
+      }
+#pragma unroll
+      for (int t = 0; t < LK / 16; ++t) {
+        f32x4 c = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < G::KS; ++ks) c = MM::mma(row_frag_lds<T>(sQ, t * 16 + li, ks * 4 + g), kf[ks], c);
+        const f32x4 l4 = *reinterpret_cast<const f32x4*>(sLse + t * 16 + g * 4);
+        const f32x4 r4 = *reinterpret_cast<const f32x4*>(sR + t * 16 + g * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc += __builtin_amdgcn_exp2f(c[e] * c2 - l4[e]) * r4[e];
+      }
+      if (h1 < a.H) {
+        char* nQ = smem + ((it + 1) & 1) * BUF;                        // read in tile it - 1: every wave has passed the barrier behind it
+        LT::store(nQ, pq);
+        if (threadIdx.x < 2 * LK) reinterpret_cast<float*>(nQ + LT::BYTES)[threadIdx.x] = pr;
+      }
+      __syncthreads();
+    }
+  }
+  acc = sum_rows4(acc);
+  if (key < a.N && g == 0) a.r_out[(size_t)b * a.N + key] = a.keep * rin[key] + (a.mix / (float)a.H) * acc;
+}
+
+template <typename T> int launch_rollout(const RolloutArgs& a, hipStream_t st) {
+  const int64_t grid = (int64_t)a.B * ((a.N + LQ - 1) / LQ);
+  if (grid > 0x7fffffff) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_attention_rollout_step: too many workgroups");
+  constexpr int SH = 2 * (LongTile<T>::BYTES + 2 * LK * (int)sizeof(float));
+  k_attn_rollout_step<T><<<(int)grid, 512, SH, st>>>(a);
+  UVC_CHECK_LAUNCH();
+  return UVC_OK;
+}
+
 template <typename T, int DV = HD> int launch_long(const AttnArgs& a, int which, hipStream_t st) {
   const int nblk = (a.N + LQ - 1) / LQ;
   const int64_t grid = (int64_t)a.B * a.H * nblk;
@@ -1690,4 +1788,20 @@ extern "C" int uvc_attention_bwd_vdim(const uvc_attn_args* p, void* stream) {
   if ((int64_t)p->B * p->H > 0x7fffffff) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_attention_bwd_vdim: too many workgroups");
   const AttnArgs a = conv(p);
   return p->dtype == UVC_F32 ? dispatch_bwd_vdim<float>(a, (hipStream_t)stream) : dispatch_bwd_vdim<bf16_t>(a, (hipStream_t)stream);
+}
+
+extern "C" int uvc_attention_rollout_step(const uvc_attn_rollout_args* p, void* stream) {
+  if (!p || !p->qkv || !p->lse || !p->r_in || !p->r_out) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_attention_rollout_step: null pointer");
+  if (p->head_dim != HD) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_attention_rollout_step: head_dim must be 64");
+  if (p->B <= 0 || p->N <= 0 || p->H <= 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_attention_rollout_step: empty problem");
+  if (p->dtype != UVC_F32 && p->dtype != UVC_BF16) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_attention_rollout_step: bad dtype");
+  if (p->v_dim != 16 && p->v_dim != 32 && p->v_dim != 48 && p->v_dim != 64) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_attention_rollout_step: v_dim must be 16, 32, 48 or 64");
+  if (p->N > LONG_MAX_N) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_attention_rollout_step: sequence length > 1026 not supported");
+  const int64_t n = (int64_t)p->B * p->N;
+  if (p->r_out < p->r_in + n && p->r_in < p->r_out + n) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_attention_rollout_step: r_out overlaps r_in");
+  if (((uintptr_t)p->qkv & 15) != 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_attention_rollout_step: qkv must be 16-byte aligned");
+  RolloutArgs a;
+  a.qkv = p->qkv; a.lse = p->lse; a.r_in = p->r_in; a.r_out = p->r_out;
+  a.B = p->B; a.N = p->N; a.H = p->H; a.v_dim = p->v_dim; a.scale = p->scale; a.keep = p->keep; a.mix = p->mix;
+  return p->dtype == UVC_F32 ? launch_rollout<float>(a, (hipStream_t)stream) : launch_rollout<bf16_t>(a, (hipStream_t)stream);
 }

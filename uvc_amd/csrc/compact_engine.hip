@@ -1,11 +1,12 @@
 // Compact-model sequencers (include/uvc_vit.h, uvc_vit_compact_*): a pruned DeiT exported at its kept widths (uvc_amd/compact.py) --
 // per block LayerNorm1, qkv GEMM, attention with a value head dim of its own (uvc_attn_args.v_dim), proj GEMM (+ bias + residual),
-// LayerNorm2, fc1 (+ bias, GELU), fc2 (+ bias + residual).  Host code only; every arithmetic step is one of the kernels behind
+// LayerNorm2, fc1 (+ bias, GELU), fc2 (+ bias + residual).  Host code (but for the start vector of the rollout); every arithmetic step is one of the kernels behind
 // uvc_kernels.h, the embedding, token assembly, final norm and heads as uvc_vit_forward runs them.
 // ONE forward body serves evaluation (uvc_vit_compact_forward) and fine-tuning (uvc_vit_compact_train_forward): the same kernels in the
 // same order on one stream.  The modes differ in where a block's buffers live (carve: one shared set in eval, a set per block that
 // the backward reads in training) and in the fc1 epilogue (training also keeps GELU').  uvc_vit_compact_backward walks the blocks in
-// reverse: plain GEMMs and the attention backward at a value width.
+// reverse: plain GEMMs and the attention backward at a value width.  uvc_vit_compact_rollout is the eval forward with qkv and lse kept
+// per attention block, then one uvc_attention_rollout_step per such block, last block first.
 #include "engine_host.h"
 
 namespace {
@@ -63,7 +64,9 @@ int check_train(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nbl
 // ---- workspace -------------------------------------------------------------------------------------------------------------------
 // Block k's buffers.  Training: its own, kept for the backward; x1 / xo (residual-stream rows [M, D]) only where the branch has a GEMM
 // (a bias-only branch adds in place).  Eval: every block points at one shared set sized by the widest block (h1 = h2, one mean / rstd
-// pair, no gp), and x1 / xo alternate between two residual-row buffers.
+// pair, no gp), and x1 / xo alternate between two residual-row buffers.  Rollout (CARVE_ROLLOUT): the eval set, but every block with heads
+// owns its qkv and lse (the reverse sweep reads them), and two [B, N] float vectors behind everything else.
+enum { CARVE_EVAL = 0, CARVE_TRAIN = 1, CARVE_ROLLOUT = 2 };
 struct BlockBufs {
   void* h1; void* qkv; void* o; float* lse; float* mean1; float* rstd1; void* x1;
   void* h2; float* mean2; float* rstd2; void* gp; void* u; void* xo;
@@ -74,6 +77,7 @@ struct Work {
   // backward: the dL/dx stream ping-pongs between g[0] and g[1] (T: bf16, or float32 in the exact mode)
   void* g[2]; void* dA; void* dH; void* dO; void* dqkv; float* delta; float* ln_partial; int64_t ln_region; float* cs_partial;
   void* tn_ws; int64_t tn_ws_bytes; void* dhc; void* dpe;
+  float* roll[2];      // rollout: the row vector ping-pongs between them
 };
 
 int64_t train_tn_ws(const CDims& d, const uvc_compact_block* blocks, int nblocks) {
@@ -87,7 +91,8 @@ int64_t train_tn_ws(const CDims& d, const uvc_compact_block* blocks, int nblocks
   return best;
 }
 
-int64_t carve(const CDims& d, const uvc_compact_block* blocks, int nblocks, int training, char* base, Work& w) {
+int64_t carve(const CDims& d, const uvc_compact_block* blocks, int nblocks, int mode, char* base, Work& w) {
+  const bool training = mode == CARVE_TRAIN;
   Carver c{base, 0};
   const int64_t M = d.M, MD = M * d.D;
   memset(&w, 0, sizeof(w));
@@ -100,8 +105,9 @@ int64_t carve(const CDims& d, const uvc_compact_block* blocks, int nblocks, int 
   if (!training) {
     r[1] = c.take(MD * d.rsz);
     shared.h1 = shared.h2 = c.take(MD * d.tsz);
-    shared.qkv = c.take(M * d.maxQ * d.tsz); shared.o = c.take(M * d.maxO * d.tsz);
-    shared.lse = (float*)c.take((int64_t)d.B * d.maxH * d.N * 4);
+    if (mode == CARVE_EVAL) shared.qkv = c.take(M * d.maxQ * d.tsz);
+    shared.o = c.take(M * d.maxO * d.tsz);
+    if (mode == CARVE_EVAL) shared.lse = (float*)c.take((int64_t)d.B * d.maxH * d.N * 4);
     shared.u = c.take(M * d.maxF * d.tsz);
     shared.mean1 = shared.mean2 = (float*)c.take(M * 4); shared.rstd1 = shared.rstd2 = (float*)c.take(M * 4);
   }
@@ -112,6 +118,10 @@ int64_t carve(const CDims& d, const uvc_compact_block* blocks, int nblocks, int 
       b = shared;
       if (blocks[k].heads > 0) b.x1 = r[cur ^= 1];
       if (F > 0) b.xo = r[cur ^= 1];
+      if (mode == CARVE_ROLLOUT && blocks[k].heads > 0) {
+        b.qkv = c.take(M * nq * d.tsz);
+        b.lse = (float*)c.take((int64_t)d.B * blocks[k].heads * d.N * 4);
+      }
       continue;
     }
     if (blocks[k].heads > 0) {
@@ -129,6 +139,7 @@ int64_t carve(const CDims& d, const uvc_compact_block* blocks, int nblocks, int 
   w.hc = c.take((int64_t)d.B * d.ntok * d.D * d.tsz);
   w.meanf = (float*)c.take((int64_t)d.B * d.ntok * 4); w.rstdf = (float*)c.take((int64_t)d.B * d.ntok * 4);
   w.ones = (float*)c.take(M * 4);
+  if (mode == CARVE_ROLLOUT) { w.roll[0] = (float*)c.take(M * 4); w.roll[1] = (float*)c.take(M * 4); }
   if (!training) return c.off;
   w.g[0] = c.take(MD * d.tsz); w.g[1] = c.take(MD * d.tsz);
   w.dA = c.take(M * (d.maxF > 0 ? d.maxF : 1) * d.tsz);
@@ -162,9 +173,9 @@ Chain chain_of(const Work& w, const uvc_compact_block* blocks, int nblocks) {
 struct Ctx { CDims d; const uvc_vit_io* io; void* st; Work w; uvc_ln_reduce_item ln_items[64]; int n_ln; };
 
 // fills the context and carves io->workspace; false when the workspace is too small for the mode
-bool bind(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nblocks, const uvc_vit_io* io, void* stream, int training) {
+bool bind(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nblocks, const uvc_vit_io* io, void* stream, int mode) {
   c.d = cdims_of(*cfg, blocks, nblocks, io->batch); c.io = io; c.st = stream; c.n_ln = 0;
-  const int64_t need = carve(c.d, blocks, nblocks, training, (char*)io->workspace, c.w);
+  const int64_t need = carve(c.d, blocks, nblocks, mode, (char*)io->workspace, c.w);
   if (io->patches_in) c.w.patches = const_cast<void*>(io->patches_in);
   return io->workspace_bytes >= need;
 }
@@ -249,7 +260,7 @@ int update_shadows(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int 
   return sb.flush();
 }
 
-// the forward of both modes; `training` keeps GELU' of fc1 beside its output (and c.w holds a buffer set per block)
+// the forward of every mode; `training` keeps GELU' of fc1 beside its output (and c.w holds a buffer set per block)
 int forward(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nblocks, int training) {
   const CDims& d = c.d;
   const Work& w = c.w;
@@ -413,15 +424,61 @@ extern "C" int uvc_vit_compact_train_update_shadows(const uvc_vit_cfg* cfg, cons
 }
 
 // ---- forward (eval, training) and backward -------------------------------------------------------------------------------------------
-extern "C" int uvc_vit_compact_forward(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* stream) {
+// r[b, i] = 1 / ntok on the readout tokens (i < ntok), 0 elsewhere: the one device code of this file, too small for an entry point of its own
+static __global__ void k_rollout_start(float* r, int64_t n, int N, int ntok) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) r[i] = (int)(i % N) < ntok ? 1.0f / (float)ntok : 0.f;
+}
+
+static int setup_eval(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nblocks, const uvc_vit_io* io, void* stream, int mode) {
   TRY(check_blocks(cfg, blocks, nblocks));
   if (!io || !io->params || !io->workspace || io->batch <= 0 || (!io->x && !io->patches_in) || !io->logits ||
       (cfg->ntok == 2 && !io->logits_dist))   // x is read by uvc_patchify alone: patch rows handed in (patches_in) stand for it
     return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_forward: null io member");
   if (cfg->dtype == UVC_BF16 && !io->shadow) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_forward: bf16 mode needs the shadow buffer");
+  if (!bind(c, cfg, blocks, nblocks, io, stream, mode)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_forward: workspace too small");
+  return UVC_OK;
+}
+
+extern "C" int uvc_vit_compact_forward(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* stream) {
   Ctx c;
-  if (!bind(c, cfg, blocks, nblocks, io, stream, 0)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_forward: workspace too small");
+  TRY(setup_eval(c, cfg, blocks, nblocks, io, stream, CARVE_EVAL));
   return forward(c, cfg, blocks, nblocks, 0);
+}
+
+extern "C" int64_t uvc_vit_compact_rollout_workspace_bytes(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int32_t batch) {
+  if (check_blocks(cfg, blocks, nblocks)) return -1;
+  if (batch <= 0) { uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_rollout_workspace_bytes: batch <= 0"); return -1; }
+  Work w;
+  return carve(cdims_of(*cfg, blocks, nblocks, batch), blocks, nblocks, CARVE_ROLLOUT, nullptr, w);
+}
+
+extern "C" int uvc_vit_compact_rollout(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, float* rollout,
+                                       int32_t method, void* stream) {
+  if (!rollout) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_rollout: null rollout");
+  if (method != 0 && method != 1) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_rollout: method must be 0 (rollout) or 1 (last)");
+  Ctx c;
+  TRY(setup_eval(c, cfg, blocks, nblocks, io, stream, CARVE_ROLLOUT));
+  TRY(forward(c, cfg, blocks, nblocks, 0));
+  const CDims& d = c.d;
+  // the start vector: uniform over the readout tokens (the eval logits are (x + x_dist) / 2 with the distillation token)
+  float* r = c.w.roll[0];
+  float* other = c.w.roll[1];
+  k_rollout_start<<<(unsigned)((d.M + 255) / 256), 256, 0, (hipStream_t)stream>>>(r, d.M, d.N, d.ntok);
+  UVC_CHECK_LAUNCH();
+  for (int k = nblocks - 1; k >= 0; --k) {
+    if (blocks[k].heads == 0) continue;                       // the branch is a bias: the identity for the row vector
+    uvc_attn_rollout_args a;
+    memset(&a, 0, sizeof(a));
+    a.qkv = c.w.blk[k].qkv; a.lse = c.w.blk[k].lse; a.r_in = r; a.r_out = other;
+    a.B = d.B; a.N = d.N; a.H = blocks[k].heads; a.head_dim = 64; a.v_dim = blocks[k].v_dim; a.dtype = d.dtype; a.scale = 0.125f;
+    a.keep = method == 0 ? 0.5f : 0.f; a.mix = method == 0 ? 0.5f : 1.0f;
+    TRY(uvc_attention_rollout_step(&a, stream));
+    float* t = r; r = other; other = t;
+    if (method == 1) break;
+  }
+  const hipError_t e = hipMemcpyAsync(rollout, r, (size_t)d.M * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  return e == hipSuccess ? UVC_OK : uvc_set_error(e, __FILE__, __LINE__);
 }
 
 extern "C" int uvc_vit_compact_train_forward(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* stream) {

@@ -123,6 +123,17 @@ def attention_bwd_vdim(qkv, o, lse, dout, dqkv, delta, B, N, H, v_dim, dtype):
     L.check(L.lib().uvc_attention_bwd_vdim(C.byref(a), L.cur_stream()), "uvc_attention_bwd_vdim")
 
 
+def attention_rollout_step(qkv, lse, r_in, r_out, B, N, H, v_dim, dtype, keep=0.5, mix=0.5):
+    """One attention-rollout step (include/uvc_kernels.h: uvc_attention_rollout_step): r_out = keep * r_in + (mix / H) * sum_h P_h^T r_in over
+    qkv rows [q H*64 | k H*64 | v H*v_dim] and the forward's lse [B, H, N]; r_in / r_out float32 [B, N], distinct buffers."""
+    _chk(qkv, lse, r_in, r_out)
+    a = L.uvc_attn_rollout_args()
+    a.qkv, a.lse, a.r_in, a.r_out = (L.ptr(t) for t in (qkv, lse, r_in, r_out))
+    a.B, a.N, a.H, a.head_dim, a.v_dim, a.dtype = B, N, H, 64, int(v_dim), dtype
+    a.scale, a.keep, a.mix = 64 ** -0.5, float(keep), float(mix)
+    L.check(L.lib().uvc_attention_rollout_step(C.byref(a), L.cur_stream()), "uvc_attention_rollout_step")
+
+
 def qkv_attention_supported(B, N, H, D, dtype):
     return bool(L.lib().uvc_qkv_attention_supported(B, N, H, D, dtype))
 
