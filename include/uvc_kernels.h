@@ -80,6 +80,10 @@ int uvc_gemm_nt_ln_supported(int32_t M, int32_t N, int32_t K, int32_t dtype, int
 /* 1 where UVC_EPI_BIAS_GELU_GRAD_Q8 (N = hidden width, K = embed_dim) AND its partner UVC_EPI_MUL_AUX_Q8 (N and K swapped roles: [M, K'] x [N', K'] with
  * K' = embed_dim) exist: bf16, embed_dim 192, hidden % 256 == 0, M >= 4096.  Callers fall back to UVC_EPI_BIAS_GELU_GRAD / UVC_EPI_MUL_AUX elsewhere. */
 int uvc_gemm_nt_q8_supported(int32_t M, int32_t hidden, int32_t embed_dim, int32_t dtype);
+/* 1 where uvc_gemm_nt (force_generic = 0, no ln_out) runs the row-panel kernel (16 rows x 64 columns per workgroup, the wave's fragments of 512 elements
+ * of K requested at once): bf16 compute, 1 <= M <= 1024, 8 <= K <= 1024, K % 8 == 0, N % 8 == 0, lda / ldb / ldc multiples of 8 (ldr and ldaux too),
+ * epilogue one of UVC_EPI_NONE, _BIAS, _BIAS_RESID, _BIAS_RESID_GATE, _BIAS_GELU_GRAD, _MUL_AUX; A and C bf16 or float32.  Same bits as every other route. */
+int uvc_gemm_nt_rows_supported(int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t ldc, int32_t dtype, int32_t epilogue);
 
 /* C[N1,N2] = beta*C + alpha * A[M,N1]^T . B[M,N2]  (weight gradients; float32 C).
  * Deterministic: M is cut into slices reduced in a fixed order through `workspace`. */

@@ -188,6 +188,7 @@ _SIGNATURES = {
     "uvc_gemm_nt": [C.POINTER(uvc_gemm_nt_args), VP],
     "uvc_gemm_nt_ln_supported": [I32, I32, I32, I32, I32],
     "uvc_gemm_nt_q8_supported": [I32, I32, I32, I32],
+    "uvc_gemm_nt_rows_supported": [I32, I32, I32, I32, I32, I32, I32, I32],
     "uvc_gemm_tn": [C.POINTER(uvc_gemm_tn_args), VP],
     "uvc_gemm_tn_workspace_bytes": [I32, I32, I32, C.POINTER(I64), C.POINTER(I32)],
     "uvc_attention_fwd": [C.POINTER(uvc_attn_args), VP],

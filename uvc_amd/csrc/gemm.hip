@@ -391,6 +391,74 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(NtArgs g) {
 }
 
 // ================================================================================================
+//                          NT, row panels (bf16, M <= 1024, K <= 1024)
+// ================================================================================================
+// The step's turnaround (the last block's class-token rows, the head, their backward) and the teacher's tail are GEMMs on a few hundred rows:
+// 128 x 128 tiles put M = 512 on 8 of the 256 CUs, and their k loop is one 64-element tile in flight between two barriers -- 12 to 16 serial
+// memory round trips for 0.1 GFLOP.  Here a workgroup owns 16 rows x 64 columns (M = 512, N = 192: 96 workgroups; the head's N = 1000: 512), wave w
+// the 16 columns 16w..16w+15, and a wave requests its A and W fragments of 16 k-steps (512 elements of K: 128 VGPRs) before the first MFMA: one
+// memory latency per half instead of one per tile.  No LDS in the k loop (the four waves read the same 16 A rows: 24 KB at K = 768, from L2).
+// The accumulator is k_gemm_nt's: one k-ordered chain of 2 * ceil(K / 64) MFMA steps, zero-padded past K, leaving through the same staged
+// epilogue -- the same bits (tests/test_row_gemm_gpu.py).
+constexpr int RP_BM = 16, RP_BN = 64, RP_KS = 16;      // rows, columns of a workgroup; k-steps (of 32) requested at a time
+constexpr int RP_MAX_M = 1024, RP_MAX_K = 1024;
+
+// NS k-steps of a wave's chain from step s0: every fragment requested first (straight-line code, no branch: one batch of loads, answered in order),
+// then the MFMAs.  A lane whose row is past M / N, or whose chunk is past K, reads a valid address and multiplies zeros.
+template <typename TA, int NS>
+__device__ __forceinline__ f32x4 rp_steps(const TA* __restrict__ Ap, const bf16_t* __restrict__ Bp, int s0, int K, int gq, bool mv, bool nv, f32x4 acc) {
+  typedef Mma<bf16_t> MM;
+  u32x4 fa[NS], fb[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const int kc = (s0 + s) * 32 + gq * 8, kl = kc < K ? kc : K - 8;
+    fa[s] = ChunkLoad<TA, bf16_t>::ld(Ap + kl);
+    fb[s] = ChunkLoad<bf16_t, bf16_t>::ld(Bp + kl);
+  }
+  const u32x4 z = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const bool in = (s0 + s) * 32 + gq * 8 < K;
+    acc = MM::mma(__builtin_bit_cast(MM::Frag, (nv && in) ? fb[s] : z), __builtin_bit_cast(MM::Frag, (mv && in) ? fa[s] : z), acc);
+  }
+  return acc;
+}
+
+template <typename TA, typename TC, int EPI>
+__global__ __launch_bounds__(256) void k_gemm_nt_rows(NtArgs g) {
+  typedef bf16_t T;
+  typedef Mma<T> MM;
+  __shared__ __attribute__((aligned(16))) float stg[RP_BM * EP_LD];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, li = lane & 15, gq = lane >> 4;
+  const int ntn = (g.N + RP_BN - 1) / RP_BN;
+  const int m0 = ((int)blockIdx.x / ntn) * RP_BM, n0 = ((int)blockIdx.x % ntn) * RP_BN;
+  const int m = m0 + li, n = n0 + w * 16 + li;
+  const bool mv = m < g.M, nv = n < g.N;
+  // (rows past M / N: row 0's addresses, the values replaced by zeros -- every load unconditional, so that they leave as one batch)
+  const TA* __restrict__ Ap = reinterpret_cast<const TA*>(g.A) + (size_t)(mv ? m : 0) * g.lda;
+  const T* __restrict__ Bp = reinterpret_cast<const T*>(g.B) + (size_t)(nv ? n : 0) * g.ldb;
+  float alpha = g.alpha;
+  if (g.alpha_ptr) alpha *= *g.alpha_ptr;
+  float d0 = 0.f, d1 = 1.f;
+  if (EPI == UVC_EPI_BIAS_RESID_GATE) { d0 = g.dptr[0]; d1 = g.dptr[1]; }
+  float bias_v[OutVec<TC>::VN];
+  nt_load_bias<TC, EPI>(g, lane, n0, bias_v);
+
+  // k_gemm_nt's chain is 2 * ceil(K / 64) steps of 32; the steps run here in batches of 16 or 8, and a step past the chain's end multiplies two zero
+  // fragments like any step past K: it adds +0 to an accumulator that started at +0 and so is never -0 -- the same bits
+  const int nsteps = 2 * ((g.K + 63) / 64);
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+  int s0 = 0;
+  for (; nsteps - s0 > RP_KS / 2; s0 += RP_KS) acc = rp_steps<TA, RP_KS>(Ap, Bp, s0, g.K, gq, mv, nv, acc);
+  if (s0 < nsteps) acc = rp_steps<TA, RP_KS / 2>(Ap, Bp, s0, g.K, gq, mv, nv, acc);
+  // lane (li, gq) holds row li, columns 4 gq .. 4 gq + 3 of the wave's 16: the 16 x 64 tile is staged once and leaves as whole row segments,
+  // eight rows per wave (waves 0 and 1)
+  *reinterpret_cast<f32x4*>(stg + li * EP_LD + w * 16 + gq * 4) = acc;
+  __syncthreads();
+  if (w < 2) nt_epilogue_rows<T, TC, EPI, 8>(g, stg + w * 8 * EP_LD, lane, m0 + w * 8, n0, alpha, d0, d1, bias_v);
+}
+
+// ================================================================================================
 //                     NT, weights-stationary / activation-streaming (bf16, K <= 192)
 // ================================================================================================
 // The DeiT GEMMs are skinny: M = B*197 rows (1e5) against K, N of a few hundred, i.e. HBM-bound
@@ -1079,6 +1147,23 @@ static int launch_nt_epi(const NtArgs& a, int epi, hipStream_t st) {
   return UVC_OK;
 }
 
+static bool nt_rows_epilogue(int epi) {
+  return epi == UVC_EPI_NONE || epi == UVC_EPI_BIAS || epi == UVC_EPI_BIAS_RESID || epi == UVC_EPI_BIAS_RESID_GATE || epi == UVC_EPI_BIAS_GELU_GRAD ||
+         epi == UVC_EPI_MUL_AUX;
+}
+template <typename TA, typename TC>
+static int launch_nt_rows(const NtArgs& a, int epi, hipStream_t st) {
+  const int grid = ceil_div(a.M, RP_BM) * ceil_div(a.N, RP_BN);
+#define RP_CASE(E) case E: k_gemm_nt_rows<TA, TC, E><<<grid, 256, 0, st>>>(a); break;
+  switch (epi) {
+    RP_CASE(UVC_EPI_NONE) RP_CASE(UVC_EPI_BIAS) RP_CASE(UVC_EPI_BIAS_RESID) RP_CASE(UVC_EPI_BIAS_RESID_GATE) RP_CASE(UVC_EPI_BIAS_GELU_GRAD) RP_CASE(UVC_EPI_MUL_AUX)
+    default: return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: epilogue not taken by the row-panel kernel");
+  }
+#undef RP_CASE
+  UVC_CHECK_LAUNCH();
+  return UVC_OK;
+}
+
 // the 256 x 256-tile kernel of the wide models (defined behind the LDS-DMA helpers below)
 int launch_nt256_f32(const NtArgs& a, int epi, hipStream_t st);
 int launch_nt256_bf16(const NtArgs& a, int epi, hipStream_t st);
@@ -1102,6 +1187,11 @@ extern "C" int uvc_gemm_nt_ln_supported(int32_t M, int32_t N, int32_t K, int32_t
 
 extern "C" int uvc_gemm_nt_q8_supported(int32_t M, int32_t hidden, int32_t embed_dim, int32_t dtype) {
   return dtype == UVC_BF16 && embed_dim == 192 && hidden > 0 && hidden % 256 == 0 && M >= 4096;
+}
+
+extern "C" int uvc_gemm_nt_rows_supported(int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t ldc, int32_t dtype, int32_t epilogue) {
+  return dtype == UVC_BF16 && M >= 1 && M <= RP_MAX_M && K >= 8 && K <= RP_MAX_K && K % 8 == 0 && N >= 8 && N % 8 == 0 && lda >= K && ldb >= K && ldc >= N &&
+         lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && nt_rows_epilogue(epilogue);
 }
 
 extern "C" int uvc_gemm_nt(const uvc_gemm_nt_args* p, void* stream) {
@@ -1161,6 +1251,11 @@ extern "C" int uvc_gemm_nt(const uvc_gemm_nt_args* p, void* stream) {
     if (!p->force_generic && !p->a_is_f32 && e == UVC_EPI_BIAS_RESID && p->K == 192 && p->N == 192 && a.ldb == 192 &&
         p->M >= 4096 && p->M % 16 == 0 && p->alpha == 1.0f && !p->alpha_ptr && wsn16_dma_ok(a))
       return p->c_is_f32 ? launch_wsn16_dma<UVC_EPI_BIAS_RESID, 6, false, 7, false>(a, st) : launch_wsn16_dma<UVC_EPI_BIAS_RESID, 6, false, 7, true>(a, st);
+  }
+  // few rows (the token-row tail, the heads, their backward, small batches): row panels, whatever the widths -- same chain, same epilogue, same bits
+  if (!p->force_generic && a.ldr % 8 == 0 && a.ldaux % 8 == 0 && uvc_gemm_nt_rows_supported(a.M, a.N, a.K, a.lda, a.ldb, a.ldc, p->dtype, e)) {
+    if (p->a_is_f32) return p->c_is_f32 ? launch_nt_rows<float, float>(a, e, st) : launch_nt_rows<float, bf16_t>(a, e, st);
+    return p->c_is_f32 ? launch_nt_rows<bf16_t, float>(a, e, st) : launch_nt_rows<bf16_t, bf16_t>(a, e, st);
   }
   const bool ws = !generic && ws_ok(a, p->c_is_f32 ? 4 : 8);
   if (q8 && !ws) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_gemm_nt: the one-byte GELU' epilogues exist in the K = 192 streaming kernel only");

@@ -666,7 +666,11 @@ extern "C" int uvc_vit_backward(const uvc_vit_cfg* cfg, const uvc_vit_io* io, vo
     TRY(nt(c, gB, gf, sh(c, so.blk_wt[l][1]), tail ? t.dOc : w.dH, 0, rows, d.D, d.D, UVC_EPI_NONE));                          // dO
     // (dW_proj on the main stream in every / every second / every third block, to even the two streams out: 11.47 / 11.48 / 11.42 against 11.38 ms, profiles/r5z)
     TRY(tn(c, gB, gf, tail ? t.oc : b.o, G + q[4], G + q[5], rows, d.D, d.D));
-    // (the last block's dW_proj flushed to the idle side stream here, under the attention backward: 11.10 against 11.08 ms -- nothing, profiles/r5zz_ab_early_last_flush.txt)
+    // The call's last block: the side stream has nothing else left, so its dW_proj goes there now, under the attention backward, and its dW_qkv below, beside
+    // dqkv + LayerNorm1' (one more event record each); only the patch embedding's gradient is then left behind the main stream's end: the side stream's
+    // exposed tail 149 -> 87 us, the step 10.62 -> 10.59 ms (profiles/r7a_ab_parts.txt; the first flush alone had measured nothing, r5zz_ab_early_last_flush.txt).
+    // With both flushes the block's two MLP weight gradients still belong on the main stream (dW1 only: +0.01 ms, neither: +0.10 ms).
+    if (l == last_l) TRY(flush_tn(c));
     if (tail) {
       TRY(attn_tok(c, b, true, l));         // writes all of dqkv: dq is zero off the token rows, dk / dv are dense
       // the full-row stream of dL/dx1 that the LayerNorm1 backward adds: zero but for the token rows
@@ -678,6 +682,7 @@ extern "C" int uvc_vit_backward(const uvc_vit_cfg* cfg, const uvc_vit_io* io, vo
     const bool fuse1 = lnb_fused_ok(c, 3 * d.D);
     if (!fuse1) TRY(nt(c, w.dqkv, 0, sh(c, so.blk_wt[l][0]), w.dH, 0, d.M, d.D, 3 * d.D, UVC_EPI_NONE));
     TRY(tn(c, w.dqkv, 0, b.h1, G + q[2], d.qkv_bias ? G + q[3] : nullptr, d.M, 3 * d.D, d.D));
+    if (l == last_l) TRY(flush_tn(c));
     // gA (this block's) <- dL/dx_l = LN1'(dH) + gB + d0 * (dL/d output) ; dots: <new gA, x_l>, <old gA, x_l>
     // (a `tail` block's full-row output gradient is zero off its token rows, which is what its compact stream gAc holds: the d0 term reads the full-row
     //  stream the final norm's backward left in gAs[L])

@@ -220,6 +220,11 @@ def gemm_nt_q8_supported(M, hidden, embed_dim, dtype) -> bool:
     return bool(L.lib().uvc_gemm_nt_q8_supported(M, hidden, embed_dim, dtype))
 
 
+def gemm_nt_rows_supported(M, N, K, dtype, epilogue, lda=None, ldb=None, ldc=None) -> bool:
+    """Where gemm_nt (force_generic off, no ln_out) runs the row-panel kernel of few rows (M <= 1024, K <= 1024, bf16 compute)."""
+    return bool(L.lib().uvc_gemm_nt_rows_supported(M, N, K, K if lda is None else lda, K if ldb is None else ldb, N if ldc is None else ldc, dtype, epilogue))
+
+
 def gemm_lnbwd_supported(M, D, K, dtype) -> bool:
     return bool(L.lib().uvc_gemm_lnbwd_supported(M, D, K, dtype))
 
