@@ -43,6 +43,23 @@ enum {
 #define UVC_Q8_LO (-0.13f)
 #define UVC_Q8_STEP (1.26f / 255.0f)
 
+/* uvc_gemm_nt_args.force_generic.  Every choice computes the same bits (one k-ordered accumulation chain, the same epilogue arithmetic).  Only
+ * UVC_NT_BY_SHAPE is a product setting; the others exist for tests and tuning tools (uvc_vit_cfg.force_generic passes 1, 2 and 3 to a whole pass). */
+enum {
+  UVC_NT_BY_SHAPE = 0,         /* the kernel is picked by shape (uvc_gemm_nt_route tells which)                                                        */
+  UVC_NT_GENERIC = 1,          /* tests: the generic LDS-tiled 128 x 128 kernel, the reference every other kernel must match bit for bit; ln_out and the
+                                  one-byte GELU' epilogues are UVC_ERR_UNSUPPORTED                                                                     */
+  UVC_NT_NO_DMA = 2,           /* tests: no LDS-DMA kernel -- the N = 192 residual epilogues on the register-staged k_gemm_wsn16 (ln_out still takes the
+                                  ring), no 256 x 256 and no 8-phase kernel; the K = N = 192 ring and the row panels are skipped as for any value but 0  */
+  UVC_NT_WIDE_ANY_SIZE = 3,    /* tests: the wide-tile kernels wherever the shape admits them, whatever the row / tile count, split as the production
+                                  batch of DeiT-Small / Base splits them: 8-phase where N % 256 == 0 and N < 1792 (bf16 C), else 256 x 256              */
+  UVC_NT_256_ANY_SIZE = 4,     /* tests / tools: the 256 x 256 kernel wherever the shape admits it, whatever the row / tile count                        */
+  UVC_NT_WS384_SIX_WAVES = 5,  /* tools (A/B): the K = 384 streaming kernel in its six-wave form where eight waves are the default                        */
+  UVC_NT_8PHASE = 0x100        /* tests / tools: UVC_NT_8PHASE | ri = the 8-phase kernel at 32 * ri rows per tile (ri of 8, 6, 5, 4; 0 = the height picked
+                                  by shape; float32 C: 8), at any size; UVC_ERR_UNSUPPORTED where the shape is not taken.  The K = 384 and N = 192
+                                  streaming kernels still come first                                                                                    */
+};
+
 /* C[M,N] = epilogue( A[M,K] . B[N,K]^T ); A, B row-major with K contiguous. */
 typedef struct uvc_gemm_nt_args {
   const void* A;       /* [M,K]  T, or float32 when a_is_f32 (converted to T while staging) */
@@ -58,11 +75,7 @@ typedef struct uvc_gemm_nt_args {
   float alpha;
   int32_t M, N, K, lda, ldb, ldc, ldr, ldaux;
   int32_t dtype, a_is_f32, c_is_f32, epilogue;
-  int32_t force_generic;  /* tests/tuning: 0 = pick the kernel by shape; 1 = the generic LDS-tiled kernel; 2 = the streaming kernels in their
-                             register-staged forms (no LDS-DMA ring; the 256 x 256-tile kernel IS an LDS-DMA kernel and is skipped too);
-                             3 = the wide-tile kernels (256 x 256) wherever the shape admits them, whatever the row / tile count -- what
-                             the production batch of DeiT-Small / Base selects, at a size the host oracle finishes in seconds.  Every
-                             choice computes the same bits (one k-ordered accumulation chain, the same epilogue arithmetic) */
+  int32_t force_generic;  /* tests / tuning: one of the UVC_NT_* values above; 0 in the product */
   int32_t r_is_f32;       /* element type of R / R2, stated by the caller and checked: they have C's type (c_is_f32, or float32 mode), so
                              this must equal it whenever R is given.  Rounds 1-2 took float32 R beside a bf16 C; a caller still built to
                              that contract gets UVC_ERR_ARG instead of its rows read as bf16 */
@@ -85,6 +98,14 @@ int uvc_gemm_nt_q8_supported(int32_t M, int32_t hidden, int32_t embed_dim, int32
  * epilogue one of UVC_EPI_NONE, _BIAS, _BIAS_RESID, _BIAS_RESID_GATE, _BIAS_GELU_GRAD, _MUL_AUX; A and C bf16 or float32.  Same bits as every other route. */
 int uvc_gemm_nt_rows_supported(int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t ldc, int32_t dtype, int32_t epilogue);
 
+/* uvc_gemm_tn_args.variant.  Only UVC_TN_BY_SHAPE is a product setting. */
+enum {
+  UVC_TN_BY_SHAPE = 0,   /* kernel picked by shape: the two-group schedule (k_gemm_tn8p) for every 192- / 256-wide tile but the 96 x 192 one             */
+  UVC_TN_BY_SHAPE_1 = 1, /* the same as 0 (once the two-group schedule's opt-in; kept because tests and tools pass it)                                   */
+  UVC_TN_RING = 2,       /* tests / tools: the LDS-DMA ring kernel (k_gemm_tn_dma) for the 192 x 192, 192 x 256 and 256 x 192 tiles: the same bits        */
+  UVC_TN_128X256 = 3     /* tools (A/B): 128 x 256 tiles where the shape takes 256 x 256 (half the splits: another summation order)                       */
+};
+
 /* C[N1,N2] = beta*C + alpha * A[M,N1]^T . B[M,N2]  (weight gradients; float32 C).
  * Deterministic: M is cut into slices reduced in a fixed order through `workspace`. */
 typedef struct uvc_gemm_tn_args {
@@ -98,12 +119,44 @@ typedef struct uvc_gemm_tn_args {
   float alpha, beta;
   int32_t M, N1, N2, lda, ldb, ldc;
   int32_t dtype, a_is_f32;
-  int32_t variant;     /* tuning / A-B: 0 (and 1) = kernel picked by shape -- since r6 the two-group schedule (k_gemm_tn8p) for every 192- / 256-wide tile but
-                          the 96 x 192 one; 2 = the LDS-DMA ring kernel (k_gemm_tn_dma) for the 192 x 192, 192 x 256 and 256 x 192 tiles.  All of them write
-                          the same bits.  3 = 128 x 256 tiles where the shape takes 256 x 256 (half the splits: another summation order) */
+  int32_t variant;     /* tests / tuning: one of the UVC_TN_* values above; 0 in the product */
 } uvc_gemm_tn_args;
 int uvc_gemm_tn(const uvc_gemm_tn_args* args, void* stream);
 int uvc_gemm_tn_workspace_bytes(int32_t M, int32_t N1, int32_t N2, int64_t* bytes, int32_t* splits);
+
+/* Which kernel uvc_gemm_nt / uvc_gemm_tn run for a problem, without running it (for tests: no HIP call, pointer members are read as integers only --
+ * null, alignment, aliasing).  uvc_gemm_nt_route / uvc_gemm_tn_route make every check of their entry point and return its status; the entry points
+ * call them and launch what they return. */
+enum {
+  UVC_ROUTE_NT = 0,        /* k_gemm_nt<TA, T, TC, EPI>: the generic 128 x 128 kernel                                  */
+  UVC_ROUTE_NT_ROWS,       /* k_gemm_nt_rows<TA, TC, EPI>: row panels, M <= 1024 (uvc_gemm_nt_rows_supported)          */
+  UVC_ROUTE_WS,            /* k_gemm_ws<TA, TC, EPI, kt, nw, nj>: K = 192 / 128 streaming                              */
+  UVC_ROUTE_WS384,         /* k_gemm_ws<bf16, TC, EPI, 12, nw, 2>: K = 384 streaming                                   */
+  UVC_ROUTE_WSN,           /* k_gemm_wsn<TC, EPI, kt>: N = 192 column-sliced, 32-row tiles                             */
+  UVC_ROUTE_WSN16,         /* k_gemm_wsn16<TC, EPI, kt>: the same on 16-row tiles, register-staged                     */
+  UVC_ROUTE_WSN16_DMA,     /* k_gemm_wsn16_dma<EPI, kt, ln, nst, !c_f32>: N = 192 residual epilogues on the LDS-DMA ring */
+  UVC_ROUTE_ROW384,        /* k_gemm_row384_lnbwd<true, 1>: N = 384 with ln_out                                        */
+  UVC_ROUTE_NT256,         /* k_gemm_nt256<TC, EPI>: 256 x 256 tiles                                                   */
+  UVC_ROUTE_NT8P,          /* k_gemm_nt8p<TC, EPI, ri>: (32 ri) x 256 tiles, 8-phase schedule                          */
+  UVC_ROUTE_TN,            /* k_gemm_tn<TA, T>: 128 x 64 tiles (cfg 0)                                                 */
+  UVC_ROUTE_TN_BIG,        /* k_gemm_tn_big<float, b1, b2, ..>: float32 A                                              */
+  UVC_ROUTE_TN_DMA,        /* k_gemm_tn_dma<b1, b2, ..>: LDS-DMA ring                                                  */
+  UVC_ROUTE_TN8P,          /* k_gemm_tn8p<b1 / 32, b2 / 64>: two-group schedule                                        */
+  UVC_ROUTE_COUNT
+};
+typedef struct uvc_gemm_route {
+  int32_t family;                /* UVC_ROUTE_* */
+  int32_t a_f32, t_f32, c_f32;   /* TA, T (the compute type: dtype == UVC_F32), TC are float (1) or bf16 (0) */
+  int32_t epilogue;              /* EPI (NT) */
+  int32_t kt, nw, nj;            /* k_gemm_ws / wsn / wsn16 / wsn16_dma: K / 32; k_gemm_ws: waves, 16-column blocks per wave */
+  int32_t ln, nst;               /* k_gemm_wsn16_dma: LayerNorm output, ring stages */
+  int32_t ri;                    /* k_gemm_nt8p: rows per tile / 32 */
+  int32_t cfg, b1, b2, splits, rows_per_split;   /* TN: tile configuration 0-6, tile, M slices and their length */
+} uvc_gemm_route;
+int uvc_gemm_nt_route(const uvc_gemm_nt_args* args, uvc_gemm_route* route);
+int uvc_gemm_tn_route(const uvc_gemm_tn_args* args, uvc_gemm_route* route);
+/* the kernel template's name of a UVC_ROUTE_* family, e.g. "k_gemm_wsn16_dma" (NULL outside the enum) */
+const char* uvc_gemm_route_kernel(int32_t family);
 
 /* Fused softmax(q k^T * scale) v for one DeiT sequence per (batch, head)
  * (UVC/models/model_distilled.py:175-185).  qkv is the packed Linear(dim, 3*dim) output

@@ -131,11 +131,10 @@ typedef struct uvc_vit_io {
   int32_t fuse_next_ln;                /* 1: a kernel that produces a block's output rows (uvc_mlp_fused_fwd; fc2 + residual + gate mix) also writes
                                           norm1 of the NEXT block that runs (model_distilled.py:241) from the rows it holds, and that block skips its
                                           stand-alone LayerNorm pass.  0: every LayerNorm is its own pass. */
-  int32_t force_generic;               /* tests / A-B runs: passed to every uvc_gemm_nt of the pass (uvc_gemm_nt_args.force_generic: 1 = the generic
-                                          LDS-tiled kernel everywhere, 2 = register-staged streaming kernels instead of the LDS-DMA rings);
-                                          1 also runs every dgrad + LayerNorm backward as the unfused pair, 2 runs uvc_gemm_nt_lnbwd's
-                                          register-staged variant; 3 = the production batch's wide-tile kernels at any row count.  0 = kernels
-                                          picked by shape */
+  int32_t force_generic;               /* tests / A-B runs: passed to every uvc_gemm_nt of the pass; the values are described once, at the UVC_NT_*
+                                          enum of uvc_kernels.h (UVC_NT_GENERIC, UVC_NT_NO_DMA, UVC_NT_WIDE_ANY_SIZE).  UVC_NT_GENERIC also runs every
+                                          dgrad + LayerNorm backward as the unfused pair, UVC_NT_NO_DMA runs uvc_gemm_nt_lnbwd's register-staged
+                                          variant.  0 = kernels picked by shape */
   int32_t head_keep_bwd;               /* 1: uvc_vit_backward skips dq / dk / dv of the heads head_keep marks 0 (written as zeros).  Exact when the
                                           64 attn.proj input columns of such a head are zero IN THE WEIGHTS the forward and the dgrad used (Stage-2:
                                           post_train.py:343-346 multiplies weight by mask before every step): dL/d(attention output) of the head is then

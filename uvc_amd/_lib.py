@@ -54,6 +54,11 @@ class uvc_gemm_tn_args(C.Structure):
                [(n, C.c_int32) for n in ("M", "N1", "N2", "lda", "ldb", "ldc", "dtype", "a_is_f32", "variant")]
 
 
+class uvc_gemm_route(C.Structure):             # what uvc_gemm_nt_route / uvc_gemm_tn_route answer (include/uvc_kernels.h)
+    _fields_ = [(n, C.c_int32) for n in ("family", "a_f32", "t_f32", "c_f32", "epilogue", "kt", "nw", "nj", "ln", "nst", "ri",
+                                         "cfg", "b1", "b2", "splits", "rows_per_split")]
+
+
 class uvc_attn_args(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("qkv", "o", "lse", "dout", "dqkv", "delta")] + \
                [(n, C.c_int32) for n in ("B", "N", "H", "head_dim", "dtype")] + [("scale", C.c_float), ("head_keep", C.c_void_p),
@@ -169,6 +174,7 @@ UVC_F32, UVC_BF16 = 0, 1
 UVC_IMAGE_OUT_F32, UVC_IMAGE_OUT_U8 = 0, 1
 UVC_IMAGE_FILTER_BILINEAR, UVC_IMAGE_FILTER_BICUBIC = 0, 1
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_RESID_GATE, EPI_DGELU, EPI_BIAS_GELU_OUT, EPI_BIAS_GELU_GRAD, EPI_MUL_AUX = range(9)
+ROUTE_FAMILIES = ("NT", "NT_ROWS", "WS", "WS384", "WSN", "WSN16", "WSN16_DMA", "ROW384", "NT256", "NT8P", "TN", "TN_BIG", "TN_DMA", "TN8P")   # UVC_ROUTE_*
 EPI_BIAS_GELU_GRAD_Q8, EPI_MUL_AUX_Q8 = 9, 10      # GELU'(a) as one byte per activation (include/uvc_kernels.h)
 Q8_LO, Q8_STEP = -0.13, 1.26 / 255.0               # UVC_Q8_LO, UVC_Q8_STEP
 
@@ -191,6 +197,8 @@ _SIGNATURES = {
     "uvc_gemm_nt_rows_supported": [I32, I32, I32, I32, I32, I32, I32, I32],
     "uvc_gemm_tn": [C.POINTER(uvc_gemm_tn_args), VP],
     "uvc_gemm_tn_workspace_bytes": [I32, I32, I32, C.POINTER(I64), C.POINTER(I32)],
+    "uvc_gemm_nt_route": [C.POINTER(uvc_gemm_nt_args), C.POINTER(uvc_gemm_route)],
+    "uvc_gemm_tn_route": [C.POINTER(uvc_gemm_tn_args), C.POINTER(uvc_gemm_route)],
     "uvc_attention_fwd": [C.POINTER(uvc_attn_args), VP],
     "uvc_attention_bwd": [C.POINTER(uvc_attn_args), VP],
     "uvc_attention_bwd_vdim": [C.POINTER(uvc_attn_args), VP],
@@ -281,7 +289,7 @@ def side_stream(device, priority_class=None):
 
 
 def exported_symbols():
-    return list(_SIGNATURES) + ["uvc_last_error"] + VIT_SYMBOLS
+    return list(_SIGNATURES) + ["uvc_last_error", "uvc_gemm_route_kernel"] + VIT_SYMBOLS
 
 
 def lib():
@@ -293,6 +301,7 @@ def lib():
                               "(there is no CPU fallback for the product path)")
         _lib = C.CDLL(LIB_PATH)
         _lib.uvc_last_error.restype = C.c_char_p
+        _lib.uvc_gemm_route_kernel.argtypes, _lib.uvc_gemm_route_kernel.restype = [I32], C.c_char_p
         for name, args in _SIGNATURES.items():
             fn = getattr(_lib, name)
             fn.argtypes = args

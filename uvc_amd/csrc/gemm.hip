@@ -722,107 +722,6 @@ __global__ __launch_bounds__(64 * WS_NW, (KT > 6 && WS_NW > 6) ? 1 : (NJ == 4 ||
   }
 }
 
-// eligibility of the streaming kernel: bf16 compute, K in {128, 192}, N a multiple of 64, vector-aligned leading dims
-static bool ws_ok(const NtArgs& a, int vn) {
-  return (a.K == 192 || a.K == 128) && a.N % 64 == 0 && a.ldb == a.K && a.lda % 8 == 0 && a.ldc % vn == 0 && a.ldr % vn == 0 &&
-         a.ldaux % vn == 0 && a.M >= 4096;
-}
-template <typename TA, typename TC, int KT, int WS_NW>
-static int launch_ws_epi(const NtArgs& a, int epi, hipStream_t st) {
-  const int ngroups = ceil_div(a.N, 64 * WS_NW);
-  const int ntiles = ceil_div(a.M, WS_BM);
-  // (r6: more, shorter workgroups -- 4 / 8 per CU in total, so that the dispatcher hands tiles to whichever CU is free beside the weight-gradient stream -- measured:
-  //  1024 / 2048 in total: +0.10 / +0.15 ms in the step, profiles/r6o_ab_ws_slots_not_kept.txt; -DUVC_WS_WG_TOTAL builds)
-#ifndef UVC_WS_WG_TOTAL
-#define UVC_WS_WG_TOTAL 512
-#endif
-  int nslots = (UVC_WS_WG_TOTAL / ngroups) & ~7;           // ~2 workgroups per CU in total, slots a multiple of the 8 XCDs (r5: these main-stream kernels on 224 / 192 CUs: +1 % step time, profiles/r5u)
-  if (nslots < 8) nslots = 8;
-  if (nslots > ((ntiles + 7) & ~7)) nslots = (ntiles + 7) & ~7;
-  const int grid = nslots * ngroups;
-  if (epi == UVC_EPI_BIAS_GELU_GRAD_Q8) {                  // (bf16 operands and outputs, K = 192, four waves x 64 columns: uvc_gemm_nt checked)
-    if constexpr (sizeof(TA) == 2 && sizeof(TC) == 2 && KT == 6 && WS_NW == 4) {
-      k_gemm_ws<TA, TC, UVC_EPI_BIAS_GELU_GRAD_Q8, KT, WS_NW><<<grid, 64 * WS_NW, 0, st>>>(a, ngroups, nslots);
-      UVC_CHECK_LAUNCH();
-      return UVC_OK;
-    } else return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_gemm_nt: UVC_EPI_BIAS_GELU_GRAD_Q8 outside uvc_gemm_nt_q8_supported");
-  }
-#define WS_CASE(E) case E: k_gemm_ws<TA, TC, E, KT, WS_NW><<<grid, 64 * WS_NW, 0, st>>>(a, ngroups, nslots); break;
-  switch (epi) {
-    WS_CASE(UVC_EPI_NONE) WS_CASE(UVC_EPI_BIAS) WS_CASE(UVC_EPI_BIAS_GELU) WS_CASE(UVC_EPI_BIAS_RESID)
-    WS_CASE(UVC_EPI_BIAS_RESID_GATE) WS_CASE(UVC_EPI_DGELU) WS_CASE(UVC_EPI_BIAS_GELU_OUT) WS_CASE(UVC_EPI_BIAS_GELU_GRAD) WS_CASE(UVC_EPI_MUL_AUX)
-    default: return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: unknown epilogue");
-  }
-#undef WS_CASE
-  UVC_CHECK_LAUNCH();
-  return UVC_OK;
-}
-// K = 384, N a multiple of 192 (DeiT-Small / T2T-ViT: qkv, proj, fc1 and the dgrads with K = D)
-// Measured at M = 50 k rows against the generic tiled kernel: qkv 102 -> 72 us, fc1 (+GELU, GELU') 178 -> 148, proj 47 -> 43, fc2 dgrad x GELU'
-// 133 -> 128; the plain and the recomputing-dGELU epilogues were slower (26 -> 28, 149 -> 162) and stay on the generic kernel.
-static bool ws384_ok(const NtArgs& a, int epi, int vn, bool a_f32) {
-  if (epi == UVC_EPI_DGELU) return false;
-  if (epi == UVC_EPI_NONE && !(vn == 8 && a.N % 128 == 0 && a.N >= 512)) return false;      // (plain epilogue: the eight-wave form only -- T2T-ViT's bias-free qkv)
-  return !a_f32 && a.K == 384 && a.N % 192 == 0 && a.ldb == a.K && a.lda % 8 == 0 && a.ldc % vn == 0 && a.ldr % vn == 0 && a.ldaux % vn == 0 && a.M >= 4096;
-}
-// NW = 8 (r4): N a multiple of 128 from 512 up runs eight waves x 32 columns -- two waves on every SIMD (six left two SIMDs with one), six column groups
-// instead of eight per A tile at N = 1536; N = 1152 (qkv; T2T-ViT's MLP) is 4.5 groups, the last with four idle waves: still 6-15 % faster than six waves
-template <typename TC, int NW = 6>
-static int launch_ws384(const NtArgs& a, int epi, hipStream_t st) {
-  constexpr int KT = 12, NJ = 2;
-  const int ngroups = ceil_div(a.N, 32 * NW);               // (a last group with idle waves: N = 1152 on eight waves is 4.5 groups)
-  const int ntiles = ceil_div(a.M, WS_BM);
-  int nslots = (256 / ngroups) & ~7;                       // one workgroup per CU
-  if (nslots < 8) nslots = 8;
-  if (nslots > ((ntiles + 7) & ~7)) nslots = (ntiles + 7) & ~7;
-  const int grid = nslots * ngroups;
-  const int sh = 2 * WS_BM * (KT * 64 + 32) + NW * 16 * (16 * NJ + 4) * 4;
-#define WS_CASE(E) case E: { \
-    UVC_MAX_LDS(sh, k_gemm_ws<bf16_t, TC, E, KT, NW, NJ>); \
-    k_gemm_ws<bf16_t, TC, E, KT, NW, NJ><<<grid, 64 * NW, sh, st>>>(a, ngroups, nslots); } break;
-  switch (epi) {
-    WS_CASE(UVC_EPI_NONE) WS_CASE(UVC_EPI_BIAS) WS_CASE(UVC_EPI_BIAS_GELU) WS_CASE(UVC_EPI_BIAS_RESID)
-    WS_CASE(UVC_EPI_BIAS_RESID_GATE) WS_CASE(UVC_EPI_BIAS_GELU_OUT) WS_CASE(UVC_EPI_BIAS_GELU_GRAD) WS_CASE(UVC_EPI_MUL_AUX)
-    default: return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: unknown epilogue");
-  }
-#undef WS_CASE
-  UVC_CHECK_LAUNCH();
-  return UVC_OK;
-}
-
-template <typename TA, typename TC, int KT>
-static int launch_ws_narrow(const NtArgs& a, int epi, hipStream_t st) {      // 8 waves x 32 columns
-  const int ngroups = ceil_div(a.N, 256);
-  const int ntiles = ceil_div(a.M, WS_BM);
-  int nslots = (UVC_WS_WG_TOTAL / ngroups) & ~7;
-  if (nslots < 8) nslots = 8;
-  if (nslots > ((ntiles + 7) & ~7)) nslots = (ntiles + 7) & ~7;
-  const int grid = nslots * ngroups;
-#define WS_CASE(E) case E: k_gemm_ws<TA, TC, E, KT, 8, 2><<<grid, 512, 0, st>>>(a, ngroups, nslots); break;
-  switch (epi) {
-    WS_CASE(UVC_EPI_DGELU) WS_CASE(UVC_EPI_MUL_AUX) WS_CASE(UVC_EPI_MUL_AUX_Q8) WS_CASE(UVC_EPI_BIAS_GELU_GRAD_Q8)
-    default: return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: epilogue");
-  }
-#undef WS_CASE
-  UVC_CHECK_LAUNCH();
-  return UVC_OK;
-}
-template <typename TA, typename TC>
-static int launch_ws(const NtArgs& a, int epi, hipStream_t st) {
-  // dL/d(fc1 out) = (g W2) * gelu'(a): measured 95 -> 83 us (stored gelu') and 118 -> 105 us (recomputed) with 32 columns per wave;
-  // the forward's GELU epilogues are VALU-bound either way and stay on the 64-column tiling
-  if constexpr (sizeof(TC) == 2 && sizeof(TA) == 2) {
-    if (a.N % 256 == 0 && a.K == 192 && (epi == UVC_EPI_DGELU || epi == UVC_EPI_MUL_AUX || epi == UVC_EPI_MUL_AUX_Q8)) return launch_ws_narrow<TA, TC, 6>(a, epi, st);
-#ifdef UVC_FC1_NARROW        // A/B build: fc1 + GELU, GELU' (one-byte code) on eight waves x 32 columns (109 us against 84, the step 11.07 against 10.64 ms: not kept, profiles/r6j_ab_fc1_narrow_not_kept.txt)
-    if (a.N % 256 == 0 && a.K == 192 && epi == UVC_EPI_BIAS_GELU_GRAD_Q8) return launch_ws_narrow<TA, TC, 6>(a, epi, st);
-#endif
-  }
-  if (epi == UVC_EPI_MUL_AUX_Q8) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_gemm_nt: UVC_EPI_MUL_AUX_Q8 outside uvc_gemm_nt_q8_supported");
-  // 4 waves (256 columns) per workgroup when N divides: more waves per CU to overlap the GELU epilogues
-  if (a.N % 256 == 0) return a.K == 192 ? launch_ws_epi<TA, TC, 6, 4>(a, epi, st) : launch_ws_epi<TA, TC, 4, 4>(a, epi, st);
-  return a.K == 192 ? launch_ws_epi<TA, TC, 6, 3>(a, epi, st) : launch_ws_epi<TA, TC, 4, 3>(a, epi, st);
-}
-
 // ================================================================================================
 //        NT, weights-stationary, one 16-column slice of the FULL reduction per wave (bf16, N == 192)
 // ================================================================================================
@@ -1049,247 +948,6 @@ __global__ __launch_bounds__(768) void k_gemm_wsn16(NtArgs g) {
   }
 }
 
-static bool wsn_ok(const NtArgs& a, int epi, bool a_f32) {
-  return !a_f32 && a.N == 192 && (a.K == 768 || a.K == 576 || a.K == 512 || a.K == 256) && a.ldb == a.K && a.lda % 8 == 0 && a.ldc % 4 == 0 && a.ldr % 4 == 0 && a.M >= 4096 &&
-         (epi == UVC_EPI_NONE || epi == UVC_EPI_BIAS || epi == UVC_EPI_BIAS_RESID || epi == UVC_EPI_BIAS_RESID_GATE);
-}
-template <int EPI, int KT, bool LN, int NST, bool RLOW> __global__ void k_gemm_wsn16_dma(NtArgs g);
-template <int EPI, int KT, bool LN, int NST, bool RLOW>
-static int launch_wsn16_dma(const NtArgs& a, hipStream_t st) {
-  constexpr int NX_ = RLOW ? 7 : 13;                              // KB of a stage per residual operand (16 rows x (24 | 48) + 2 slots)
-  constexpr int NA_ = (16 * (KT * 4 + 2) + 63) / 64, NI_ = NA_ + NX_ + (EPI == UVC_EPI_BIAS_RESID_GATE ? NX_ : 0);
-  const int sh = NST * NI_ * 1024 + (LN ? 2 * 16 * 12 * 8 + 3 * 192 * 4 : 0);
-  UVC_MAX_LDS(sh, k_gemm_wsn16_dma<EPI, KT, LN, NST, RLOW>);
-  const int ntiles = ceil_div(a.M, 16);
-  k_gemm_wsn16_dma<EPI, KT, LN, NST, RLOW><<<ntiles < 256 ? ntiles : 256, 768, sh, st>>>(a);
-  UVC_CHECK_LAUNCH();
-  return UVC_OK;
-}
-// the shapes whose residual epilogue can also write LayerNorm(output rows): what k_gemm_wsn16_dma takes
-static bool wsn16_dma_ok(const NtArgs& a) {
-  return a.M >= 16 && a.lda == a.K && a.ldr == 192 && a.ldc % 4 == 0 && (((uintptr_t)a.R | (uintptr_t)a.R2 | (uintptr_t)a.A) & 15) == 0;
-}
-template <typename TC, int KT>
-static int launch_wsn16_kt(const NtArgs& a, int epi, hipStream_t st) {
-  if constexpr (KT == 24 || KT == 16 || KT == 8) {
-    constexpr bool RLOW = sizeof(TC) == 2;
-    // fc2 of DeiT-Tiny on the LDS-DMA ring (uvc_gemm_nt_args.force_generic = 2 keeps the register-staged kernel); with ln_out also the compacted Stage-2
-    // widths (K = 512 / 256: more stages of the smaller images fit)
-    const bool ok = (!a.no_dma || a.ln_out) && wsn16_dma_ok(a) && (a.ln_out || a.M % 16 == 0);
-    constexpr int NST_ = KT == 8 ? 4 : 3;
-    if (ok && a.ln_out) {
-      if (epi == UVC_EPI_BIAS_RESID) return launch_wsn16_dma<UVC_EPI_BIAS_RESID, KT, true, NST_, RLOW>(a, st);
-      if (epi == UVC_EPI_BIAS_RESID_GATE) return launch_wsn16_dma<UVC_EPI_BIAS_RESID_GATE, KT, true, NST_, RLOW>(a, st);
-    }
-    if constexpr (KT == 24) {
-      if (ok && epi == UVC_EPI_BIAS_RESID) return launch_wsn16_dma<UVC_EPI_BIAS_RESID, KT, false, 3, RLOW>(a, st);
-      if (ok && epi == UVC_EPI_BIAS_RESID_GATE) return launch_wsn16_dma<UVC_EPI_BIAS_RESID_GATE, KT, false, 3, RLOW>(a, st);
-    }
-  }
-  if (a.ln_out) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_gemm_nt: ln_out is not available for this problem (uvc_gemm_nt_ln_supported)");
-  const int ntiles = ceil_div(a.M, 16);
-  const int grid = ntiles < 256 ? ntiles : 256;
-  const size_t sh = (size_t)2 * 16 * (KT * 64 + 32);
-#define WN_CASE(E) case E: { \
-    UVC_MAX_LDS(sh, k_gemm_wsn16<TC, E, KT>); \
-    k_gemm_wsn16<TC, E, KT><<<grid, 768, sh, st>>>(a); } break;
-  switch (epi) {
-    WN_CASE(UVC_EPI_NONE) WN_CASE(UVC_EPI_BIAS) WN_CASE(UVC_EPI_BIAS_RESID) WN_CASE(UVC_EPI_BIAS_RESID_GATE)
-    default: return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: epilogue");
-  }
-#undef WN_CASE
-  UVC_CHECK_LAUNCH();
-  return UVC_OK;
-}
-template <typename TC, int KT>
-static int launch_wsn_kt(const NtArgs& a, int epi, hipStream_t st) {
-  // float32 outputs (fc2 with its residual / gate operands) run on 16-row tiles: with 32 rows the two sub-tiles' residual
-  // prefetch spilled 24-45 VGPRs next to the 96 of W and cost a third of the time (129 -> 88 us); bf16 outputs keep 32 rows
-  if (sizeof(TC) == 4 || epi == UVC_EPI_BIAS_RESID || epi == UVC_EPI_BIAS_RESID_GATE) {
-    return launch_wsn16_kt<TC, KT>(a, epi, st);
-  } else {
-  const int ntiles = ceil_div(a.M, WN_BM);
-  const int grid = ntiles < 256 ? ntiles : 256;                 // one persistent workgroup per CU
-  const size_t sh = (size_t)2 * WN_BM * (KT * 64 + 32);
-#define WN_CASE(E) case E: { \
-    UVC_MAX_LDS(sh, k_gemm_wsn<TC, E, KT>); \
-    k_gemm_wsn<TC, E, KT><<<grid, 768, sh, st>>>(a); } break;
-  switch (epi) {                       // bf16 outputs only (float32 outputs run k_gemm_wsn16; residual epilogues need float32 C)
-    WN_CASE(UVC_EPI_NONE) WN_CASE(UVC_EPI_BIAS)
-    default: return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: epilogue not supported by the column-sliced streaming kernel");
-  }
-#undef WN_CASE
-  UVC_CHECK_LAUNCH();
-  return UVC_OK;
-  }
-}
-template <typename TC>
-static int launch_wsn(const NtArgs& a, int epi, hipStream_t st) {
-  switch (a.K) {                                      // 512 / 256: compacted MLP widths of Stage-2
-    case 768: return launch_wsn_kt<TC, 24>(a, epi, st);
-    case 576: return launch_wsn_kt<TC, 18>(a, epi, st);
-    case 512: return launch_wsn_kt<TC, 16>(a, epi, st);
-    default: return launch_wsn_kt<TC, 8>(a, epi, st);
-  }
-}
-
-template <typename TA, typename T, typename TC>
-static int launch_nt_epi(const NtArgs& a, int epi, hipStream_t st) {
-  const int grid = ceil_div(ceil_div(a.M, NT_BM), 8) * 8 * ceil_div(a.N, NT_BN);   // M tiles padded to the 8 XCDs
-#define NT_CASE(E) case E: k_gemm_nt<TA, T, TC, E><<<grid, 256, 0, st>>>(a); break;
-  switch (epi) {
-    NT_CASE(UVC_EPI_NONE) NT_CASE(UVC_EPI_BIAS) NT_CASE(UVC_EPI_BIAS_GELU) NT_CASE(UVC_EPI_BIAS_RESID)
-    NT_CASE(UVC_EPI_BIAS_RESID_GATE) NT_CASE(UVC_EPI_DGELU) NT_CASE(UVC_EPI_BIAS_GELU_OUT) NT_CASE(UVC_EPI_BIAS_GELU_GRAD) NT_CASE(UVC_EPI_MUL_AUX)
-    default: return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: unknown epilogue");
-  }
-#undef NT_CASE
-  UVC_CHECK_LAUNCH();
-  return UVC_OK;
-}
-
-static bool nt_rows_epilogue(int epi) {
-  return epi == UVC_EPI_NONE || epi == UVC_EPI_BIAS || epi == UVC_EPI_BIAS_RESID || epi == UVC_EPI_BIAS_RESID_GATE || epi == UVC_EPI_BIAS_GELU_GRAD ||
-         epi == UVC_EPI_MUL_AUX;
-}
-template <typename TA, typename TC>
-static int launch_nt_rows(const NtArgs& a, int epi, hipStream_t st) {
-  const int grid = ceil_div(a.M, RP_BM) * ceil_div(a.N, RP_BN);
-#define RP_CASE(E) case E: k_gemm_nt_rows<TA, TC, E><<<grid, 256, 0, st>>>(a); break;
-  switch (epi) {
-    RP_CASE(UVC_EPI_NONE) RP_CASE(UVC_EPI_BIAS) RP_CASE(UVC_EPI_BIAS_RESID) RP_CASE(UVC_EPI_BIAS_RESID_GATE) RP_CASE(UVC_EPI_BIAS_GELU_GRAD) RP_CASE(UVC_EPI_MUL_AUX)
-    default: return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: epilogue not taken by the row-panel kernel");
-  }
-#undef RP_CASE
-  UVC_CHECK_LAUNCH();
-  return UVC_OK;
-}
-
-// the 256 x 256-tile kernel of the wide models (defined behind the LDS-DMA helpers below)
-int launch_nt256_f32(const NtArgs& a, int epi, hipStream_t st);
-int launch_nt256_bf16(const NtArgs& a, int epi, hipStream_t st);
-bool nt256_takes(const NtArgs& a, bool a_f32, bool any_size);
-int launch_nt8p_f32(const NtArgs& a, int epi, int ri, hipStream_t st);
-int launch_nt8p_bf16(const NtArgs& a, int epi, int ri, hipStream_t st);
-bool nt8p_takes(const NtArgs& a, bool a_f32);
-bool row384_fwd_ok(const NtArgs& a, int epi);
-int launch_row384_fwd(const NtArgs& a, int epi, hipStream_t st);
-// k_gemm_row384_lnbwd<.., 1> addresses A with 32-bit buffer offsets, the ragged last tile's 128 rows past M included: below 2 GB.  Shared by
-// uvc_gemm_nt_ln_supported and row384_fwd_ok, so the predicate never promises a problem the call refuses
-static bool row384_fwd_fits(int64_t M, int64_t K) { return (M + 128) * K * 2 < (1ll << 31); }
-
-extern "C" int uvc_gemm_nt_ln_supported(int32_t M, int32_t N, int32_t K, int32_t dtype, int32_t epilogue) {
-  // N = 384 (r4): k_gemm_row384_lnbwd<.., 1>, bf16 C / R only; its rows are bit-identical to the unfused pair, so the row threshold does not show in results
-  if (dtype == UVC_BF16 && N == 384)
-    return M >= 4096 && K % 64 == 0 && K >= 384 && (epilogue == UVC_EPI_BIAS_RESID || epilogue == UVC_EPI_BIAS_RESID_GATE) && row384_fwd_fits(M, K);
-  if (dtype != UVC_BF16 || N != 192 || M < 16) return 0;      // any row count from 16 up: whether norm is fused must not depend on the batch
-  return ((K == 768 || K == 512 || K == 256) && (epilogue == UVC_EPI_BIAS_RESID || epilogue == UVC_EPI_BIAS_RESID_GATE)) || (K == 192 && epilogue == UVC_EPI_BIAS_RESID);
-}
-
-extern "C" int uvc_gemm_nt_q8_supported(int32_t M, int32_t hidden, int32_t embed_dim, int32_t dtype) {
-  return dtype == UVC_BF16 && embed_dim == 192 && hidden > 0 && hidden % 256 == 0 && M >= 4096;
-}
-
-extern "C" int uvc_gemm_nt_rows_supported(int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t ldc, int32_t dtype, int32_t epilogue) {
-  return dtype == UVC_BF16 && M >= 1 && M <= RP_MAX_M && K >= 8 && K <= RP_MAX_K && K % 8 == 0 && N >= 8 && N % 8 == 0 && lda >= K && ldb >= K && ldc >= N &&
-         lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && nt_rows_epilogue(epilogue);
-}
-
-extern "C" int uvc_gemm_nt(const uvc_gemm_nt_args* p, void* stream) {
-  if (!p || !p->A || !p->B || !p->C) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: null pointer");
-  if (p->M <= 0 || p->N <= 0 || p->K <= 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: empty problem");
-  const int ch = (p->dtype == UVC_F32) ? 4 : 8;
-  if (p->K % ch || p->lda % ch || p->ldb % ch) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: K, lda, ldb must be multiples of a 16-byte chunk");
-  const int e = p->epilogue;
-  if ((e == UVC_EPI_BIAS || e == UVC_EPI_BIAS_GELU || e == UVC_EPI_BIAS_GELU_OUT || e == UVC_EPI_BIAS_RESID || e == UVC_EPI_BIAS_RESID_GATE ||
-       e == UVC_EPI_BIAS_GELU_GRAD) && !p->bias)
-    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: epilogue needs bias");
-  if ((e == UVC_EPI_BIAS_RESID || e == UVC_EPI_BIAS_RESID_GATE) && !p->R)
-    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: residual epilogue needs R");
-  if ((e == UVC_EPI_BIAS_RESID || e == UVC_EPI_BIAS_RESID_GATE) && (p->r_is_f32 != 0) != (p->c_is_f32 != 0 || p->dtype == UVC_F32))
-    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: R / R2 have C's element type (r_is_f32 must equal c_is_f32)");
-  if (e == UVC_EPI_BIAS_RESID_GATE && (!p->R2 || !p->gate)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: gate epilogue needs R2 and gate");
-  if ((e == UVC_EPI_BIAS_GELU || e == UVC_EPI_BIAS_GELU_GRAD) && !p->C2) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: GELU epilogue needs C2");
-  if ((e == UVC_EPI_DGELU || e == UVC_EPI_MUL_AUX || e == UVC_EPI_MUL_AUX_Q8) && !p->aux) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: dGELU epilogue needs aux");
-  const bool q8 = e == UVC_EPI_BIAS_GELU_GRAD_Q8 || e == UVC_EPI_MUL_AUX_Q8;
-  if (e == UVC_EPI_BIAS_GELU_GRAD_Q8 && (!p->bias || !p->C2)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: UVC_EPI_BIAS_GELU_GRAD_Q8 needs bias and C2");
-  // the one-byte GELU' code exists in the streaming kernel of DeiT-Tiny's width only (uvc_gemm_nt_q8_supported): N here is the hidden width, K the embed_dim
-  if (q8 && (p->force_generic == 1 || p->a_is_f32 || p->c_is_f32 || p->ln_out || !uvc_gemm_nt_q8_supported(p->M, p->N, p->K, p->dtype) ||
-             (p->ldaux ? p->ldaux : p->ldc) % 8 || p->ldc % 8 || p->ldb != p->K))
-    return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_gemm_nt: the one-byte GELU' epilogues need bf16 A / C, K = 192, N % 256 == 0, M >= 4096 (uvc_gemm_nt_q8_supported)");
-  NtArgs a;
-  a.A = p->A; a.B = p->B; a.C = p->C; a.C2 = p->C2; a.bias = p->bias; a.R = p->R; a.R2 = p->R2; a.aux = p->aux;
-  a.dptr = p->gate; a.M = p->M; a.N = p->N; a.K = p->K; a.lda = p->lda; a.ldb = p->ldb; a.ldc = p->ldc;
-  a.ldr = p->ldr ? p->ldr : p->ldc; a.ldaux = p->ldaux ? p->ldaux : p->ldc; a.alpha = p->alpha; a.alpha_ptr = p->alpha_ptr;
-  a.ln_gamma = p->ln_gamma; a.ln_beta = p->ln_beta; a.ln_out = p->ln_out; a.ln_mean = p->ln_mean; a.ln_rstd = p->ln_rstd; a.ln_eps = p->ln_eps;
-  a.no_dma = p->force_generic == 2;
-  const bool generic = p->force_generic == 1;
-  hipStream_t st = (hipStream_t)stream;
-  if (p->ln_out) {
-    if (!p->ln_gamma || !p->ln_beta || (p->ln_mean != nullptr) != (p->ln_rstd != nullptr))
-      return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: ln_out needs ln_gamma, ln_beta (and ln_mean, ln_rstd together)");
-    if (p->N == 384) {
-      if (!uvc_gemm_nt_ln_supported(p->M, p->N, p->K, p->dtype, e) || generic || p->a_is_f32 || p->c_is_f32 || p->alpha != 1.0f || p->alpha_ptr || !row384_fwd_ok(a, e))
-        return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_gemm_nt: ln_out is not available for this problem (uvc_gemm_nt_ln_supported; N = 384: bf16 C and R only)");
-      return launch_row384_fwd(a, e, st);
-    }
-    if (!uvc_gemm_nt_ln_supported(p->M, p->N, p->K, p->dtype, e) || generic || p->a_is_f32 || p->alpha != 1.0f || p->alpha_ptr ||
-        a.ldb != a.K || !wsn16_dma_ok(a) || ((uintptr_t)p->ln_out & 7) != 0)
-      return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_gemm_nt: ln_out is not available for this problem (uvc_gemm_nt_ln_supported)");
-    if (p->M % 16 != 0 && (p->C == (const void*)p->R || p->C == (const void*)p->R2))
-      return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: with ln_out and M % 16 != 0 the last row tile is computed twice: C must not alias R / R2");
-    // attn.proj + residual -> norm2 (K = 192): 20-KB stages, seven of them, six in flight
-    if (p->K == 192) return p->c_is_f32 ? launch_wsn16_dma<UVC_EPI_BIAS_RESID, 6, true, 7, false>(a, st) : launch_wsn16_dma<UVC_EPI_BIAS_RESID, 6, true, 7, true>(a, st);
-    return p->c_is_f32 ? launch_wsn<float>(a, e, st) : launch_wsn<bf16_t>(a, e, st);
-  }
-  if (p->dtype == UVC_F32) {
-    if (!p->a_is_f32 || !p->c_is_f32) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: float32 mode needs float32 A and C");
-    return launch_nt_epi<float, float, float>(a, e, st);
-  }
-  if (p->dtype != UVC_BF16) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: dtype must be UVC_F32 or UVC_BF16");
-  {
-    // attn.proj + residual (K = N = 192) without ln_out: the same seven-stage ring (same k-ordered chain and epilogue: same bits)
-    if (!p->force_generic && !p->a_is_f32 && e == UVC_EPI_BIAS_RESID && p->K == 192 && p->N == 192 && a.ldb == 192 &&
-        p->M >= 4096 && p->M % 16 == 0 && p->alpha == 1.0f && !p->alpha_ptr && wsn16_dma_ok(a))
-      return p->c_is_f32 ? launch_wsn16_dma<UVC_EPI_BIAS_RESID, 6, false, 7, false>(a, st) : launch_wsn16_dma<UVC_EPI_BIAS_RESID, 6, false, 7, true>(a, st);
-  }
-  // few rows (the token-row tail, the heads, their backward, small batches): row panels, whatever the widths -- same chain, same epilogue, same bits
-  if (!p->force_generic && a.ldr % 8 == 0 && a.ldaux % 8 == 0 && uvc_gemm_nt_rows_supported(a.M, a.N, a.K, a.lda, a.ldb, a.ldc, p->dtype, e)) {
-    if (p->a_is_f32) return p->c_is_f32 ? launch_nt_rows<float, float>(a, e, st) : launch_nt_rows<float, bf16_t>(a, e, st);
-    return p->c_is_f32 ? launch_nt_rows<bf16_t, float>(a, e, st) : launch_nt_rows<bf16_t, bf16_t>(a, e, st);
-  }
-  const bool ws = !generic && ws_ok(a, p->c_is_f32 ? 4 : 8);
-  if (q8 && !ws) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_gemm_nt: the one-byte GELU' epilogues exist in the K = 192 streaming kernel only");
-  if (!generic && ws384_ok(a, e, p->c_is_f32 ? 4 : 8, p->a_is_f32 != 0)) {
-    if (!p->c_is_f32 && a.N % 128 == 0 && a.N >= 512 && p->force_generic != 5) return launch_ws384<bf16_t, 8>(a, e, st);    // (force_generic == 5: six waves, A/B)
-    return p->c_is_f32 ? launch_ws384<float>(a, e, st) : launch_ws384<bf16_t>(a, e, st);
-  }
-  if (!generic && wsn_ok(a, e, p->a_is_f32 != 0))
-    return p->c_is_f32 ? launch_wsn<float>(a, e, st) : launch_wsn<bf16_t>(a, e, st);
-  // (force_generic == 2 asks for kernels WITHOUT an LDS-DMA ring: the 256 x 256 kernel is one; == 3 takes it at any size)
-  if ((p->force_generic >> 8) == 1) {                 // tuning: the 8-phase kernel with 32 * (force_generic & 255) rows per tile, at any size
-    if (!nt8p_takes(a, p->a_is_f32 != 0)) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_gemm_nt: shape not taken by the 8-phase kernel");
-    return p->c_is_f32 ? launch_nt8p_f32(a, e, p->force_generic & 255, st) : launch_nt8p_bf16(a, e, p->force_generic & 255, st);
-  }
-  // Wide GEMMs (K >= 256 against N >= 256).  Many tiles (>= 640 of 256 x 256: qkv, fc1, dfc2 of DeiT-Base): the lock-step 256 x 256 kernel -- at
-  // K = 768 the two kernels' k-loops cost the same (both wait for the L2 -> LDS latency of their requests: 64 KB in flight per CU) and its prologue
-  // is shorter (88 against 98 us for qkv; at K = 6144 the 8-phase kernel wins 542 : 607).  Fewer tiles with N a multiple of 256 (N = 768: proj,
-  // fc2, dfc1, dqkv, dproj -- 297 tiles of 256 x 256 are two rounds at 58 %): the 8-phase kernel at the tile height that fills its rounds
-  // (160 rows: 474 tiles): fc2 + residual + gate 153 -> 137 us, dfc1 129 -> 95, dqkv 98 -> 74, dproj 38 -> 32 against the 128 x 128 kernel.
-  // (force_generic == 3, "the production batch's kernels at any size": N < 1792 is what stays below 640 tiles at DeiT-Base's 25 216 rows)
-  const bool few_tiles_wide = !p->c_is_f32 && a.N % 256 == 0 && nt8p_takes(a, p->a_is_f32 != 0);
-  if (!generic && !a.no_dma && !(p->force_generic == 3 && few_tiles_wide && a.N < 1792) &&
-      nt256_takes(a, p->a_is_f32 != 0, p->force_generic == 3 || p->force_generic == 4))
-    return p->c_is_f32 ? launch_nt256_f32(a, e, st) : launch_nt256_bf16(a, e, st);
-  if (!generic && !a.no_dma && few_tiles_wide && (a.M >= 2048 || p->force_generic == 3))
-    return launch_nt8p_bf16(a, e, 0, st);
-  if (p->a_is_f32) {
-    if ((p->lda % 8) != 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: lda");
-    if (ws) return p->c_is_f32 ? launch_ws<float, float>(a, e, st) : launch_ws<float, bf16_t>(a, e, st);
-    return p->c_is_f32 ? launch_nt_epi<float, bf16_t, float>(a, e, st) : launch_nt_epi<float, bf16_t, bf16_t>(a, e, st);
-  }
-  if (ws) return p->c_is_f32 ? launch_ws<bf16_t, float>(a, e, st) : launch_ws<bf16_t, bf16_t>(a, e, st);
-  return p->c_is_f32 ? launch_nt_epi<bf16_t, bf16_t, float>(a, e, st) : launch_nt_epi<bf16_t, bf16_t, bf16_t>(a, e, st);
-}
 
 // ================================================================================================
 //      NT dgrad (K = 768 / 576 -> N = 192) with the LayerNorm backward as its epilogue (bf16 mode)
@@ -2613,56 +2271,6 @@ int launch_row384_lnbwd(const LnbArgs& a, int x_lowp, hipStream_t st) {
   UVC_CHECK_LAUNCH();
   return UVC_OK;
 }
-// uvc_gemm_nt with ln_out at N = 384 (bf16 operands, residual rows and outputs; K a multiple of 64, >= 128)
-bool row384_fwd_ok(const NtArgs& a, int epi) {
-  return a.N == R3_BN && a.K % 64 == 0 && a.K >= 128 && a.lda == a.K && a.ldb == a.K && a.ldc == R3_BN && a.ldr == R3_BN &&
-         (epi == UVC_EPI_BIAS_RESID || epi == UVC_EPI_BIAS_RESID_GATE) && (((uintptr_t)a.A | (uintptr_t)a.B | (uintptr_t)a.C | (uintptr_t)a.R | (uintptr_t)a.ln_out) & 15) == 0 &&
-         row384_fwd_fits(a.M, a.K);
-}
-int launch_row384_fwd(const NtArgs& a, int epi, hipStream_t st) {
-  LnbArgs b = {};
-  b.A = a.A; b.W = a.B; b.M = a.M; b.K = a.K;
-  R3Fwd f;
-  f.bias = a.bias; f.R = a.R; f.R2 = a.R2; f.dptr = a.dptr; f.C = a.C; f.ln_gamma = a.ln_gamma; f.ln_beta = a.ln_beta; f.ln_out = a.ln_out;
-  f.ln_mean = a.ln_mean; f.ln_rstd = a.ln_rstd; f.ln_eps = a.ln_eps; f.gate = epi == UVC_EPI_BIAS_RESID_GATE ? 1 : 0;
-  const int tiles_m = ceil_div(a.M, R3_BM);
-  // (r5, measured and not kept: tiles in whole rounds of the grid -- 512 frames of 98-99 rows instead of 394 of 128 at DeiT-Small batch 256, the frame rows past
-  //  the tile requested out of the descriptor's range -- DeiT-Small 15.70 -> 16.57 ms, T2T-ViT-14 12.50 -> 12.78: the 30 % more k-loops cost more than the
-  //  shorter row passes return, profiles/r5o; fewer workgroups than CUs for this launch: +- 0, profiles/r5k)
-  const int grid = tiles_m < 256 ? tiles_m : 256;
-  UVC_MAX_LDS(R3_LDS, k_gemm_row384_lnbwd<true, 1>);
-  k_gemm_row384_lnbwd<true, 1><<<grid, 512, R3_LDS, st>>>(b, tiles_m, f);
-  UVC_CHECK_LAUNCH();
-  return UVC_OK;
-}
-
-// the shapes k_gemm_nt256 takes: bf16 operands with 64-deep k tiles and 16-byte aligned rows, enough rows and columns to fill tiles
-// ... and enough tiles: one persistent workgroup per CU means ceil(tiles / 256) rounds, and with fewer than ~3 the last, partly
-// filled round costs more than the kernel gains (N = 768 at 25 k rows: 297 tiles = 2 rounds at 58 %; the 128 x 128 kernel with three
-// workgroups per CU is as fast or faster there, measured).  Operand sizes < 2 GB: 32-bit buffer offsets.
-static bool nt256_ok(const NtArgs& a, bool a_f32, bool any_size) {
-  const int tiles = ceil_div(a.M, G2_BM) * ceil_div(a.N, G2_BN);
-  return !a_f32 && (any_size || (tiles >= 640 && a.M >= 2048)) && a.K % 64 == 0 && a.K >= 256 && a.N >= 256 && a.lda % 8 == 0 && a.ldb % 8 == 0 &&
-         (((uintptr_t)a.A | (uintptr_t)a.B) & 15) == 0 && (size_t)a.M * a.lda * 2 < (1ull << 31) && (size_t)a.N * a.ldb * 2 < (1ull << 31);
-}
-template <typename TC>
-static int launch_nt256(const NtArgs& a, int epi, hipStream_t st) {
-  const int tm = ceil_div(a.M, G2_BM), tn = ceil_div(a.N, G2_BN);
-  const int nvirt = ceil_div(tm, 8) * 8 * tn;               // tile numbers incl. the holes of the XCD-major order (M tiles padded to the 8 XCDs)
-  const int grid = nvirt < 256 ? nvirt : 256;               // one persistent workgroup per CU
-#define G2_CASE(E) case E: UVC_MAX_LDS(G2_LDS, k_gemm_nt256<TC, E>); k_gemm_nt256<TC, E><<<grid, 512, G2_LDS, st>>>(a, tm, tn, nvirt); break;
-  switch (epi) {
-    G2_CASE(UVC_EPI_NONE) G2_CASE(UVC_EPI_BIAS) G2_CASE(UVC_EPI_BIAS_GELU) G2_CASE(UVC_EPI_BIAS_RESID)
-    G2_CASE(UVC_EPI_BIAS_RESID_GATE) G2_CASE(UVC_EPI_DGELU) G2_CASE(UVC_EPI_BIAS_GELU_OUT) G2_CASE(UVC_EPI_BIAS_GELU_GRAD) G2_CASE(UVC_EPI_MUL_AUX)
-    default: return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: unknown epilogue");
-  }
-#undef G2_CASE
-  UVC_CHECK_LAUNCH();
-  return UVC_OK;
-}
-int launch_nt256_f32(const NtArgs& a, int epi, hipStream_t st) { return launch_nt256<float>(a, epi, st); }
-int launch_nt256_bf16(const NtArgs& a, int epi, hipStream_t st) { return launch_nt256<bf16_t>(a, epi, st); }
-bool nt256_takes(const NtArgs& a, bool a_f32, bool any_size) { return nt256_ok(a, a_f32, any_size); }
 
 // ================================================================================================
 //        NT on (32 RI) x 256 tiles with two wave groups half a phase apart ("8-phase" schedule)
@@ -2865,54 +2473,430 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt8p(NtArgs g, int tiles_m, int
   wait_vm<0>();
 }
 
-static bool nt8p_ok(const NtArgs& a, bool a_f32) {
-  return !a_f32 && a.K % 64 == 0 && a.K >= 256 && a.N >= 256 && a.lda % 8 == 0 && a.ldb % 8 == 0 &&
-         (((uintptr_t)a.A | (uintptr_t)a.B) & 15) == 0 && (size_t)(a.M + 256) * a.lda * 2 < (1ull << 31) && (size_t)(a.N + 256) * a.ldb * 2 < (1ull << 31);
+// ================================================================================================
+//                      NT: routing, launchers and the entry point (host code)
+// ================================================================================================
+// nt_route() decides which kernel runs a problem and with which template arguments; uvc_gemm_nt() is nt_route() and one switch
+// over the family.  The launchers below compute grid and LDS bytes and decide nothing.  DESIGN.md ("GEMM routing") has the table
+// family -> kernel -> rule -> where measured; NOTEBOOK.md ("gemm.hip dispatcher comments") the history of each rule.
+namespace {
+
+NtArgs nt_args(const uvc_gemm_nt_args& p) {
+  NtArgs a;
+  a.A = p.A; a.B = p.B; a.C = p.C; a.C2 = p.C2; a.bias = p.bias; a.R = p.R; a.R2 = p.R2; a.aux = p.aux;
+  a.dptr = p.gate; a.M = p.M; a.N = p.N; a.K = p.K; a.lda = p.lda; a.ldb = p.ldb; a.ldc = p.ldc;
+  a.ldr = p.ldr ? p.ldr : p.ldc; a.ldaux = p.ldaux ? p.ldaux : p.ldc; a.alpha = p.alpha; a.alpha_ptr = p.alpha_ptr;
+  a.ln_gamma = p.ln_gamma; a.ln_beta = p.ln_beta; a.ln_out = p.ln_out; a.ln_mean = p.ln_mean; a.ln_rstd = p.ln_rstd; a.ln_eps = p.ln_eps;
+  a.no_dma = p.force_generic == UVC_NT_NO_DMA;
+  return a;
 }
-// rows per tile: the height (of 256 / 192 / 160 / 128) with the least work in the longest-running workgroup
-static int nt8p_pick_ri(int M, int N) {
+
+// ---- what each family takes
+bool epi_resid(int e) { return e == UVC_EPI_BIAS_RESID || e == UVC_EPI_BIAS_RESID_GATE; }
+// k_gemm_ws at K = 192 / 128: N a multiple of 64, vector-aligned leading dimensions
+bool ws_ok(const NtArgs& a, int vn) {
+  return (a.K == 192 || a.K == 128) && a.N % 64 == 0 && a.ldb == a.K && a.lda % 8 == 0 && a.ldc % vn == 0 && a.ldr % vn == 0 &&
+         a.ldaux % vn == 0 && a.M >= 4096;
+}
+// k_gemm_ws at K = 384, N a multiple of 192 (DeiT-Small / T2T-ViT).  The plain epilogue in the eight-wave form only, and the recomputing dGELU never: both
+// were slower than the generic kernel (26 -> 28 us, 149 -> 162 us at M = 50 k)
+bool ws384_ok(const NtArgs& a, int epi, int vn, bool a_f32) {
+  if (epi == UVC_EPI_DGELU) return false;
+  if (epi == UVC_EPI_NONE && !(vn == 8 && a.N % 128 == 0 && a.N >= 512)) return false;
+  return !a_f32 && a.K == 384 && a.N % 192 == 0 && a.ldb == a.K && a.lda % 8 == 0 && a.ldc % vn == 0 && a.ldr % vn == 0 && a.ldaux % vn == 0 && a.M >= 4096;
+}
+// k_gemm_wsn / k_gemm_wsn16: N = 192 against K = 768 / 576 (DeiT-Tiny) or 512 / 256 (compacted Stage-2 widths)
+bool wsn_ok(const NtArgs& a, int epi, bool a_f32) {
+  return !a_f32 && a.N == 192 && (a.K == 768 || a.K == 576 || a.K == 512 || a.K == 256) && a.ldb == a.K && a.lda % 8 == 0 && a.ldc % 4 == 0 && a.ldr % 4 == 0 && a.M >= 4096 &&
+         (epi == UVC_EPI_NONE || epi == UVC_EPI_BIAS || epi == UVC_EPI_BIAS_RESID || epi == UVC_EPI_BIAS_RESID_GATE);
+}
+// k_gemm_wsn16_dma: contiguous A and residual rows, 16-byte aligned
+bool wsn16_dma_ok(const NtArgs& a) {
+  return a.M >= 16 && a.lda == a.K && a.ldr == 192 && a.ldc % 4 == 0 && (((uintptr_t)a.R | (uintptr_t)a.R2 | (uintptr_t)a.A) & 15) == 0;
+}
+bool nt_rows_epilogue(int epi) {
+  return epi == UVC_EPI_NONE || epi == UVC_EPI_BIAS || epi == UVC_EPI_BIAS_RESID || epi == UVC_EPI_BIAS_RESID_GATE || epi == UVC_EPI_BIAS_GELU_GRAD ||
+         epi == UVC_EPI_MUL_AUX;
+}
+// k_gemm_row384_lnbwd<.., 1> addresses A with 32-bit buffer offsets, the ragged last tile's 128 rows past M included: below 2 GB.  Shared by
+// uvc_gemm_nt_ln_supported and row384_fwd_ok, so the predicate never promises a problem the call refuses
+bool row384_fwd_fits(int64_t M, int64_t K) { return (M + 128) * K * 2 < (1ll << 31); }
+// uvc_gemm_nt with ln_out at N = 384 (bf16 operands, residual rows and outputs; K a multiple of 64, >= 128)
+bool row384_fwd_ok(const NtArgs& a, int epi) {
+  return a.N == R3_BN && a.K % 64 == 0 && a.K >= 128 && a.lda == a.K && a.ldb == a.K && a.ldc == R3_BN && a.ldr == R3_BN &&
+         epi_resid(epi) && (((uintptr_t)a.A | (uintptr_t)a.B | (uintptr_t)a.C | (uintptr_t)a.R | (uintptr_t)a.ln_out) & 15) == 0 &&
+         row384_fwd_fits(a.M, a.K);
+}
+// the two wide-tile LDS-DMA kernels: bf16 operands, 64-deep k tiles, 16-byte aligned rows, operands below 2 GB (32-bit buffer offsets; k_gemm_nt8p
+// requests up to 256 rows past the edge)
+bool wide_ok(const NtArgs& a, bool a_f32, int past) {
+  return !a_f32 && a.K % 64 == 0 && a.K >= 256 && a.N >= 256 && a.lda % 8 == 0 && a.ldb % 8 == 0 && (((uintptr_t)a.A | (uintptr_t)a.B) & 15) == 0 &&
+         (size_t)(a.M + past) * a.lda * 2 < (1ull << 31) && (size_t)(a.N + past) * a.ldb * 2 < (1ull << 31);
+}
+// k_gemm_nt256 by shape: at least 640 tiles (under ~3 rounds of the 256 persistent workgroups the partly filled last round costs more than the kernel gains)
+bool nt256_ok(const NtArgs& a, bool a_f32, bool any_size) {
+  const int tiles = ceil_div(a.M, G2_BM) * ceil_div(a.N, G2_BN);
+  return (any_size || (tiles >= 640 && a.M >= 2048)) && wide_ok(a, a_f32, 0);
+}
+bool nt8p_ok(const NtArgs& a, bool a_f32) { return wide_ok(a, a_f32, 256); }
+// k_gemm_nt8p's rows per tile / 32: the height (of 256 / 192 / 160 / 128) with the least work in the longest-running workgroup.  Tile time ~ a + b * rows with
+// a / b = 8 row blocks (M = 25 216, N = 768: 189 / 150 / 137 / 169 us for ri 8 / 6 / 5 / 4)
+int nt8p_pick_ri(int M, int N) {
   const int tn = ceil_div(N, 256);
   int best = 8; long best_cost = -1;
   const int cand[4] = {8, 6, 5, 4};
   for (int ri : cand) {
-    const int tm = ceil_div(M, 32 * ri);
-    const long tiles = (long)tm * tn;
-    const long rounds = (tiles + 255) / 256;
-    const long cost = rounds * (ri + 8);           // tile time ~ a + b * rows with a / b = 8 row blocks (measured at M = 25 216, N = 768: 189 / 150 / 137 / 169 us for
-                                                   // ri 8 / 6 / 5 / 4 = 2 / 2 / 2 / 3 rounds; the requests of the B slots and the latency of a k-step do not shrink with the rows)
+    const long tiles = (long)ceil_div(M, 32 * ri) * tn;
+    const long cost = (tiles + 255) / 256 * (ri + 8);
     if (best_cost < 0 || cost < best_cost) { best = ri; best_cost = cost; }
   }
   return best;
 }
+
+const char* const NT_NO_LN = "uvc_gemm_nt: ln_out is not available for this problem (uvc_gemm_nt_ln_supported)";
+
+int nt_route_ring(uvc_gemm_route* r, int kt, bool ln, int nst) {
+  r->family = UVC_ROUTE_WSN16_DMA; r->kt = kt; r->ln = ln; r->nst = nst;
+  return UVC_OK;
+}
+// N = 192 column-sliced.  16 rows per tile for float32 C and the residual epilogues (with 32 the two sub-tiles' residual prefetch spilled 24-45 VGPRs:
+// 129 -> 88 us), 32 rows otherwise; the residual epilogues on the LDS-DMA ring at K = 768, and with ln_out at K = 512 / 256 too (UVC_NT_NO_DMA: never)
+int nt_route_wsn(const NtArgs& a, int e, bool c_f32, uvc_gemm_route* r) {
+  const int kt = a.K / 32;
+  const bool rows16 = c_f32 || epi_resid(e);
+  const bool dma = rows16 && kt != 18 && epi_resid(e) && (a.ln_out || kt == 24) && (!a.no_dma || a.ln_out) && wsn16_dma_ok(a) && (a.ln_out || a.M % 16 == 0);
+  if (dma) return nt_route_ring(r, kt, a.ln_out != nullptr, kt == 8 ? 4 : 3);
+  if (a.ln_out) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, NT_NO_LN);
+  r->family = rows16 ? UVC_ROUTE_WSN16 : UVC_ROUTE_WSN; r->kt = kt;
+  return UVC_OK;
+}
+
+// Every check of uvc_gemm_nt, then the family and template arguments of the kernel that runs the problem.  No HIP call; pointers are read as integers only.
+// Precedence in bf16 mode: ln_out forms; K = N = 192 ring; row panels; K = 384 streaming; N = 192 column-sliced; forced 8-phase; 256 x 256; 8-phase for
+// few wide tiles; K = 192 / 128 streaming; generic.
+int nt_route(const uvc_gemm_nt_args& p, uvc_gemm_route* r) {
+  *r = uvc_gemm_route{};
+  if (!p.A || !p.B || !p.C) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: null pointer");
+  if (p.M <= 0 || p.N <= 0 || p.K <= 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: empty problem");
+  const int ch = (p.dtype == UVC_F32) ? 4 : 8;
+  if (p.K % ch || p.lda % ch || p.ldb % ch) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: K, lda, ldb must be multiples of a 16-byte chunk");
+  const int e = p.epilogue, fg = p.force_generic;
+  if ((e == UVC_EPI_BIAS || e == UVC_EPI_BIAS_GELU || e == UVC_EPI_BIAS_GELU_OUT || e == UVC_EPI_BIAS_RESID || e == UVC_EPI_BIAS_RESID_GATE ||
+       e == UVC_EPI_BIAS_GELU_GRAD) && !p.bias)
+    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: epilogue needs bias");
+  if (epi_resid(e) && !p.R) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: residual epilogue needs R");
+  if (epi_resid(e) && (p.r_is_f32 != 0) != (p.c_is_f32 != 0 || p.dtype == UVC_F32))
+    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: R / R2 have C's element type (r_is_f32 must equal c_is_f32)");
+  if (e == UVC_EPI_BIAS_RESID_GATE && (!p.R2 || !p.gate)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: gate epilogue needs R2 and gate");
+  if ((e == UVC_EPI_BIAS_GELU || e == UVC_EPI_BIAS_GELU_GRAD) && !p.C2) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: GELU epilogue needs C2");
+  if ((e == UVC_EPI_DGELU || e == UVC_EPI_MUL_AUX || e == UVC_EPI_MUL_AUX_Q8) && !p.aux) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: dGELU epilogue needs aux");
+  const bool q8 = e == UVC_EPI_BIAS_GELU_GRAD_Q8 || e == UVC_EPI_MUL_AUX_Q8;
+  if (e == UVC_EPI_BIAS_GELU_GRAD_Q8 && (!p.bias || !p.C2)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: UVC_EPI_BIAS_GELU_GRAD_Q8 needs bias and C2");
+  // the one-byte GELU' code exists in the streaming kernel of DeiT-Tiny's width only (uvc_gemm_nt_q8_supported): N here is the hidden width, K the embed_dim
+  if (q8 && (fg == UVC_NT_GENERIC || p.a_is_f32 || p.c_is_f32 || p.ln_out || !uvc_gemm_nt_q8_supported(p.M, p.N, p.K, p.dtype) ||
+             (p.ldaux ? p.ldaux : p.ldc) % 8 || p.ldc % 8 || p.ldb != p.K))
+    return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_gemm_nt: the one-byte GELU' epilogues need bf16 A / C, K = 192, N % 256 == 0, M >= 4096 (uvc_gemm_nt_q8_supported)");
+  const NtArgs a = nt_args(p);
+  const bool generic = fg == UVC_NT_GENERIC, a_f32 = p.a_is_f32 != 0, c_f32 = p.c_is_f32 != 0;
+  r->a_f32 = a_f32; r->c_f32 = c_f32; r->t_f32 = p.dtype == UVC_F32; r->epilogue = e;
+  if (p.ln_out) {
+    if (!p.ln_gamma || !p.ln_beta || (p.ln_mean != nullptr) != (p.ln_rstd != nullptr))
+      return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: ln_out needs ln_gamma, ln_beta (and ln_mean, ln_rstd together)");
+    const bool ln_ok = uvc_gemm_nt_ln_supported(p.M, p.N, p.K, p.dtype, e) && !generic && !a_f32 && p.alpha == 1.0f && !p.alpha_ptr;
+    if (p.N == 384) {
+      if (!ln_ok || c_f32 || !row384_fwd_ok(a, e))
+        return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_gemm_nt: ln_out is not available for this problem (uvc_gemm_nt_ln_supported; N = 384: bf16 C and R only)");
+      r->family = UVC_ROUTE_ROW384;
+      return UVC_OK;
+    }
+    if (!ln_ok || a.ldb != a.K || !wsn16_dma_ok(a) || ((uintptr_t)p.ln_out & 7) != 0) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, NT_NO_LN);
+    if (p.M % 16 != 0 && (p.C == (const void*)p.R || p.C == (const void*)p.R2))
+      return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: with ln_out and M % 16 != 0 the last row tile is computed twice: C must not alias R / R2");
+    if (p.K == 192) return nt_route_ring(r, 6, true, 7);       // attn.proj + residual -> norm2: 20-KB stages, seven of them
+    return nt_route_wsn(a, e, c_f32, r);
+  }
+  if (p.dtype == UVC_F32) {
+    if (!a_f32 || !c_f32) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: float32 mode needs float32 A and C");
+  } else if (p.dtype != UVC_BF16) {
+    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: dtype must be UVC_F32 or UVC_BF16");
+  } else if (!fg && !a_f32 && e == UVC_EPI_BIAS_RESID && p.K == 192 && p.N == 192 && a.ldb == 192 && p.M >= 4096 && p.M % 16 == 0 && p.alpha == 1.0f &&
+             !p.alpha_ptr && wsn16_dma_ok(a)) {
+    return nt_route_ring(r, 6, false, 7);                      // attn.proj + residual without ln_out: the same seven-stage ring
+  } else if (!fg && a.ldr % 8 == 0 && a.ldaux % 8 == 0 && uvc_gemm_nt_rows_supported(a.M, a.N, a.K, a.lda, a.ldb, a.ldc, p.dtype, e)) {
+    r->family = UVC_ROUTE_NT_ROWS;                             // few rows, whatever the widths (profiles/r7a_ab_parent_new.txt)
+    return UVC_OK;
+  } else {
+    const int vn = c_f32 ? 4 : 8;
+    const bool ws = !generic && ws_ok(a, vn);
+    if (q8 && !ws) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_gemm_nt: the one-byte GELU' epilogues exist in the K = 192 streaming kernel only");
+    // eight waves x 32 columns where N is a multiple of 128 from 512 up: two waves on every SIMD, 6-15 % faster than six (UVC_NT_WS384_SIX_WAVES: the A/B)
+    if (!generic && ws384_ok(a, e, vn, a_f32)) {
+      r->family = UVC_ROUTE_WS384; r->kt = 12; r->nj = 2;
+      r->nw = (!c_f32 && a.N % 128 == 0 && a.N >= 512 && fg != UVC_NT_WS384_SIX_WAVES) ? 8 : 6;
+    } else if (!generic && wsn_ok(a, e, a_f32)) {
+      return nt_route_wsn(a, e, c_f32, r);
+    } else if ((fg >> 8) == 1) {                               // UVC_NT_8PHASE | ri
+      if (!nt8p_ok(a, a_f32)) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_gemm_nt: shape not taken by the 8-phase kernel");
+      r->family = UVC_ROUTE_NT8P; r->ri = fg & 255;
+    } else {
+      // Wide GEMMs.  >= 640 tiles of 256 x 256 (qkv, fc1, dfc2 of DeiT-Base): k_gemm_nt256, 88 against 98 us for qkv.  Fewer tiles with N % 256 == 0 (N = 768:
+      // 297 tiles are two rounds at 58 %): k_gemm_nt8p at the height that fills its rounds -- fc2 153 -> 137 us, dfc1 129 -> 95, dqkv 98 -> 74 against 128 x 128.
+      // UVC_NT_WIDE_ANY_SIZE keeps that split at any row count: N < 1792 is what stays below 640 tiles at DeiT-Base's 25 216 rows
+      const bool dma = !generic && !a.no_dma;
+      const bool few_tiles_wide = !c_f32 && a.N % 256 == 0 && nt8p_ok(a, a_f32);
+      if (dma && !(fg == UVC_NT_WIDE_ANY_SIZE && few_tiles_wide && a.N < 1792) && nt256_ok(a, a_f32, fg == UVC_NT_WIDE_ANY_SIZE || fg == UVC_NT_256_ANY_SIZE)) {
+        r->family = UVC_ROUTE_NT256;
+      } else if (dma && few_tiles_wide && (a.M >= 2048 || fg == UVC_NT_WIDE_ANY_SIZE)) {
+        r->family = UVC_ROUTE_NT8P;
+      } else {
+        if (a_f32 && p.lda % 8 != 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: lda");
+        if (ws) {
+          // bf16 A and C, N % 256 == 0, K = 192, the backward's multiplying epilogues: eight waves x 32 columns (95 -> 83 us, 118 -> 105); else four waves x 64
+          // columns where N divides (more waves per CU to overlap the GELU epilogues), three otherwise
+          const bool narrow = !a_f32 && !c_f32 && a.N % 256 == 0 && a.K == 192 && (e == UVC_EPI_DGELU || e == UVC_EPI_MUL_AUX || e == UVC_EPI_MUL_AUX_Q8);
+          r->family = UVC_ROUTE_WS; r->kt = a.K == 192 ? 6 : 4; r->nw = narrow ? 8 : a.N % 256 == 0 ? 4 : 3; r->nj = narrow ? 2 : 4;
+        }
+      }
+    }
+  }
+  if (r->family == UVC_ROUTE_NT8P) {                           // float32 C: the 256-row tile only
+    if (r->ri <= 0) r->ri = nt8p_pick_ri(a.M, a.N);
+    r->ri = c_f32 ? 8 : (r->ri == 8 || r->ri == 6 || r->ri == 5) ? r->ri : 4;
+  }
+  // (the row-panel, column-sliced and ring families have checked their epilogues above)
+  if (e < UVC_EPI_NONE || (e > UVC_EPI_MUL_AUX && !q8)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: unknown epilogue");
+  return UVC_OK;
+}
+
+// ---- launchers: grid, LDS bytes, launch.  NT_LAUNCH(epi, cases): the launch of the case that is `epi` (nt_route has checked that the family takes it)
+#define NT_LAUNCH(epi, ...) \
+  switch (epi) { __VA_ARGS__ default: return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: epilogue not built for the routed kernel"); } \
+  UVC_CHECK_LAUNCH(); \
+  return UVC_OK;
+#define NT_EPI9(X) X(UVC_EPI_NONE) X(UVC_EPI_BIAS) X(UVC_EPI_BIAS_GELU) X(UVC_EPI_BIAS_RESID) X(UVC_EPI_BIAS_RESID_GATE) X(UVC_EPI_DGELU) X(UVC_EPI_BIAS_GELU_OUT) \
+                   X(UVC_EPI_BIAS_GELU_GRAD) X(UVC_EPI_MUL_AUX)
+
+template <typename TA, typename T, typename TC>
+int launch_nt_epi(const NtArgs& a, int epi, hipStream_t st) {
+  const int grid = ceil_div(ceil_div(a.M, NT_BM), 8) * 8 * ceil_div(a.N, NT_BN);   // M tiles padded to the 8 XCDs
+#define NT_CASE(E) case E: k_gemm_nt<TA, T, TC, E><<<grid, 256, 0, st>>>(a); break;
+  NT_LAUNCH(epi, NT_EPI9(NT_CASE))
+#undef NT_CASE
+}
+
+template <typename TA, typename TC>
+int launch_nt_rows(const NtArgs& a, int epi, hipStream_t st) {
+  const int grid = ceil_div(a.M, RP_BM) * ceil_div(a.N, RP_BN);
+#define RP_CASE(E) case E: k_gemm_nt_rows<TA, TC, E><<<grid, 256, 0, st>>>(a); break;
+  NT_LAUNCH(epi, RP_CASE(UVC_EPI_NONE) RP_CASE(UVC_EPI_BIAS) RP_CASE(UVC_EPI_BIAS_RESID) RP_CASE(UVC_EPI_BIAS_RESID_GATE) RP_CASE(UVC_EPI_BIAS_GELU_GRAD) RP_CASE(UVC_EPI_MUL_AUX))
+#undef RP_CASE
+}
+
+// k_gemm_ws: `wgs` workgroups in all (512 at K = 192 / 128: ~2 per CU -- 1024 / 2048 cost +0.10 / +0.15 ms in the step, profiles/r6o_ab_ws_slots_not_kept.txt;
+// 256 at K = 384: one per CU), slots a multiple of the 8 XCDs
+int ws_slots(const NtArgs& a, int ngroups, int wgs) {
+  const int ntiles = ceil_div(a.M, WS_BM);
+  int nslots = (wgs / ngroups) & ~7;
+  if (nslots < 8) nslots = 8;
+  if (nslots > ((ntiles + 7) & ~7)) nslots = (ntiles + 7) & ~7;
+  return nslots;
+}
+template <typename TA, typename TC, int KT, int WS_NW>
+int launch_ws_epi(const NtArgs& a, int epi, hipStream_t st) {
+  const int ngroups = ceil_div(a.N, 64 * WS_NW), nslots = ws_slots(a, ngroups, 512);
+  const int grid = nslots * ngroups;
+  if (epi == UVC_EPI_BIAS_GELU_GRAD_Q8) {                  // (bf16 operands and outputs, K = 192, four waves x 64 columns: nt_route checked)
+    if constexpr (sizeof(TA) == 2 && sizeof(TC) == 2 && KT == 6 && WS_NW == 4) {
+      k_gemm_ws<TA, TC, UVC_EPI_BIAS_GELU_GRAD_Q8, KT, WS_NW><<<grid, 64 * WS_NW, 0, st>>>(a, ngroups, nslots);
+      UVC_CHECK_LAUNCH();
+      return UVC_OK;
+    } else return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_gemm_nt: UVC_EPI_BIAS_GELU_GRAD_Q8 outside uvc_gemm_nt_q8_supported");
+  }
+#define WS_CASE(E) case E: k_gemm_ws<TA, TC, E, KT, WS_NW><<<grid, 64 * WS_NW, 0, st>>>(a, ngroups, nslots); break;
+  NT_LAUNCH(epi, NT_EPI9(WS_CASE))
+#undef WS_CASE
+}
+template <typename TA, typename TC, int KT>
+int launch_ws_narrow(const NtArgs& a, int epi, hipStream_t st) {      // 8 waves x 32 columns
+  const int ngroups = ceil_div(a.N, 256), nslots = ws_slots(a, ngroups, 512);
+  const int grid = nslots * ngroups;
+#define WS_CASE(E) case E: k_gemm_ws<TA, TC, E, KT, 8, 2><<<grid, 512, 0, st>>>(a, ngroups, nslots); break;
+  NT_LAUNCH(epi, WS_CASE(UVC_EPI_DGELU) WS_CASE(UVC_EPI_MUL_AUX) WS_CASE(UVC_EPI_MUL_AUX_Q8) WS_CASE(UVC_EPI_BIAS_GELU_GRAD_Q8))
+#undef WS_CASE
+}
+template <typename TA, typename TC>
+int launch_ws(const uvc_gemm_route& r, const NtArgs& a, hipStream_t st) {
+  if constexpr (sizeof(TC) == 2 && sizeof(TA) == 2) {
+    if (r.nw == 8) return launch_ws_narrow<TA, TC, 6>(a, r.epilogue, st);
+  }
+  if (r.kt == 6) return r.nw == 4 ? launch_ws_epi<TA, TC, 6, 4>(a, r.epilogue, st) : launch_ws_epi<TA, TC, 6, 3>(a, r.epilogue, st);
+  return r.nw == 4 ? launch_ws_epi<TA, TC, 4, 4>(a, r.epilogue, st) : launch_ws_epi<TA, TC, 4, 3>(a, r.epilogue, st);
+}
+template <typename TC, int NW = 6>
+int launch_ws384(const NtArgs& a, int epi, hipStream_t st) {
+  constexpr int KT = 12, NJ = 2;
+  const int ngroups = ceil_div(a.N, 32 * NW), nslots = ws_slots(a, ngroups, 256);     // (a last group with idle waves: N = 1152 on eight waves is 4.5 groups)
+  const int grid = nslots * ngroups;
+  const int sh = 2 * WS_BM * (KT * 64 + 32) + NW * 16 * (16 * NJ + 4) * 4;
+#define WS_CASE(E) case E: { \
+    UVC_MAX_LDS(sh, k_gemm_ws<bf16_t, TC, E, KT, NW, NJ>); \
+    k_gemm_ws<bf16_t, TC, E, KT, NW, NJ><<<grid, 64 * NW, sh, st>>>(a, ngroups, nslots); } break;
+  NT_LAUNCH(epi, WS_CASE(UVC_EPI_NONE) WS_CASE(UVC_EPI_BIAS) WS_CASE(UVC_EPI_BIAS_GELU) WS_CASE(UVC_EPI_BIAS_RESID) WS_CASE(UVC_EPI_BIAS_RESID_GATE)
+                      WS_CASE(UVC_EPI_BIAS_GELU_OUT) WS_CASE(UVC_EPI_BIAS_GELU_GRAD) WS_CASE(UVC_EPI_MUL_AUX))
+#undef WS_CASE
+}
+
+// k_gemm_wsn (ROWS = 32: plain and bias epilogues) and k_gemm_wsn16 (ROWS = 16): one persistent workgroup per CU
+template <typename TC, int KT, int ROWS>
+int launch_wsn_rows(const NtArgs& a, int epi, hipStream_t st) {
+  const int ntiles = ceil_div(a.M, ROWS);
+  const int grid = ntiles < 256 ? ntiles : 256;
+  const size_t sh = (size_t)2 * ROWS * (KT * 64 + 32);
+#define WN_CASE(KERNEL, E) case E: { \
+    UVC_MAX_LDS(sh, KERNEL<TC, E, KT>); \
+    KERNEL<TC, E, KT><<<grid, 768, sh, st>>>(a); } break;
+  if constexpr (ROWS == 16) {
+    NT_LAUNCH(epi, WN_CASE(k_gemm_wsn16, UVC_EPI_NONE) WN_CASE(k_gemm_wsn16, UVC_EPI_BIAS) WN_CASE(k_gemm_wsn16, UVC_EPI_BIAS_RESID) WN_CASE(k_gemm_wsn16, UVC_EPI_BIAS_RESID_GATE))
+  } else {
+    static_assert(ROWS == WN_BM, "k_gemm_wsn's tile height");
+    NT_LAUNCH(epi, WN_CASE(k_gemm_wsn, UVC_EPI_NONE) WN_CASE(k_gemm_wsn, UVC_EPI_BIAS))
+  }
+#undef WN_CASE
+}
+template <typename TC>
+int launch_wsn(const uvc_gemm_route& r, const NtArgs& a, hipStream_t st) {
+#define WN_KT(KT) case KT: return r.family == UVC_ROUTE_WSN16 ? launch_wsn_rows<TC, KT, 16>(a, r.epilogue, st) : launch_wsn_rows<TC, KT, WN_BM>(a, r.epilogue, st);
+  switch (r.kt) {
+    WN_KT(24) WN_KT(18) WN_KT(16) WN_KT(8)
+    default: return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: K not built for the column-sliced kernel");
+  }
+#undef WN_KT
+}
+
+template <int EPI, int KT, bool LN, int NST, bool RLOW>
+int launch_wsn16_dma(const NtArgs& a, hipStream_t st) {
+  constexpr int NX_ = RLOW ? 7 : 13;                              // KB of a stage per residual operand (16 rows x (24 | 48) + 2 slots)
+  constexpr int NA_ = (16 * (KT * 4 + 2) + 63) / 64, NI_ = NA_ + NX_ + (EPI == UVC_EPI_BIAS_RESID_GATE ? NX_ : 0);
+  const int sh = NST * NI_ * 1024 + (LN ? 2 * 16 * 12 * 8 + 3 * 192 * 4 : 0);
+  UVC_MAX_LDS(sh, k_gemm_wsn16_dma<EPI, KT, LN, NST, RLOW>);
+  const int ntiles = ceil_div(a.M, 16);
+  k_gemm_wsn16_dma<EPI, KT, LN, NST, RLOW><<<ntiles < 256 ? ntiles : 256, 768, sh, st>>>(a);
+  UVC_CHECK_LAUNCH();
+  return UVC_OK;
+}
+// the instances built: K = 192 (RESID, seven stages, with and without LayerNorm), K = 768 (three stages, both), K = 512 / 256 (with LayerNorm only)
+template <bool RLOW>
+int launch_ring(const uvc_gemm_route& r, const NtArgs& a, hipStream_t st) {
+  const bool gate = r.epilogue == UVC_EPI_BIAS_RESID_GATE;
+#define RING(KT, LN, NST) \
+  if (r.kt == KT && r.ln == LN && r.nst == NST) \
+    return gate ? launch_wsn16_dma<UVC_EPI_BIAS_RESID_GATE, KT, LN, NST, RLOW>(a, st) : launch_wsn16_dma<UVC_EPI_BIAS_RESID, KT, LN, NST, RLOW>(a, st);
+  if (r.kt == 6 && r.nst == 7 && !gate)
+    return r.ln ? launch_wsn16_dma<UVC_EPI_BIAS_RESID, 6, true, 7, RLOW>(a, st) : launch_wsn16_dma<UVC_EPI_BIAS_RESID, 6, false, 7, RLOW>(a, st);
+  RING(24, true, 3) RING(24, false, 3) RING(16, true, 3) RING(8, true, 4)
+#undef RING
+  return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: ring kernel not built for this route");
+}
+
+int launch_row384_fwd(const NtArgs& a, int epi, hipStream_t st) {
+  LnbArgs b = {};
+  b.A = a.A; b.W = a.B; b.M = a.M; b.K = a.K;
+  R3Fwd f;
+  f.bias = a.bias; f.R = a.R; f.R2 = a.R2; f.dptr = a.dptr; f.C = a.C; f.ln_gamma = a.ln_gamma; f.ln_beta = a.ln_beta; f.ln_out = a.ln_out;
+  f.ln_mean = a.ln_mean; f.ln_rstd = a.ln_rstd; f.ln_eps = a.ln_eps; f.gate = epi == UVC_EPI_BIAS_RESID_GATE ? 1 : 0;
+  const int tiles_m = ceil_div(a.M, R3_BM);
+  // (tiles in whole rounds of the grid, and fewer workgroups than CUs: measured and not kept, profiles/r5o, profiles/r5k)
+  const int grid = tiles_m < 256 ? tiles_m : 256;
+  UVC_MAX_LDS(R3_LDS, k_gemm_row384_lnbwd<true, 1>);
+  k_gemm_row384_lnbwd<true, 1><<<grid, 512, R3_LDS, st>>>(b, tiles_m, f);
+  UVC_CHECK_LAUNCH();
+  return UVC_OK;
+}
+
+template <typename TC>
+int launch_nt256(const NtArgs& a, int epi, hipStream_t st) {
+  const int tm = ceil_div(a.M, G2_BM), tn = ceil_div(a.N, G2_BN);
+  const int nvirt = ceil_div(tm, 8) * 8 * tn;               // tile numbers incl. the holes of the XCD-major order (M tiles padded to the 8 XCDs)
+  const int grid = nvirt < 256 ? nvirt : 256;               // one persistent workgroup per CU
+#define G2_CASE(E) case E: UVC_MAX_LDS(G2_LDS, k_gemm_nt256<TC, E>); k_gemm_nt256<TC, E><<<grid, 512, G2_LDS, st>>>(a, tm, tn, nvirt); break;
+  NT_LAUNCH(epi, NT_EPI9(G2_CASE))
+#undef G2_CASE
+}
+
 template <typename TC, int RI>
-static int launch_nt8p_ri(const NtArgs& a, int epi, hipStream_t st) {
+int launch_nt8p_ri(const NtArgs& a, int epi, hipStream_t st) {
   const int tm = ceil_div(a.M, 32 * RI), tn = ceil_div(a.N, 256);
   const int nvirt = ceil_div(tm, 8) * 8 * tn;
   const int grid = nvirt < 256 ? nvirt : 256;
 #define P8_CASE(E) case E: UVC_MAX_LDS(P8_LDS, k_gemm_nt8p<TC, E, RI>); k_gemm_nt8p<TC, E, RI><<<grid, 512, P8_LDS, st>>>(a, tm, tn, nvirt); break;
-  switch (epi) {
-    P8_CASE(UVC_EPI_NONE) P8_CASE(UVC_EPI_BIAS) P8_CASE(UVC_EPI_BIAS_GELU) P8_CASE(UVC_EPI_BIAS_RESID)
-    P8_CASE(UVC_EPI_BIAS_RESID_GATE) P8_CASE(UVC_EPI_DGELU) P8_CASE(UVC_EPI_BIAS_GELU_OUT) P8_CASE(UVC_EPI_BIAS_GELU_GRAD) P8_CASE(UVC_EPI_MUL_AUX)
-    default: return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: unknown epilogue");
-  }
+  NT_LAUNCH(epi, NT_EPI9(P8_CASE))
 #undef P8_CASE
-  UVC_CHECK_LAUNCH();
-  return UVC_OK;
 }
 template <typename TC>
-static int launch_nt8p(const NtArgs& a, int epi, int ri, hipStream_t st) {
-  if (ri <= 0) ri = nt8p_pick_ri(a.M, a.N);
-  if constexpr (sizeof(TC) == 4) return launch_nt8p_ri<TC, 8>(a, epi, st);     // float32 C (resid_f32 A/B mode, patch embedding): the 256-row tile only
-  else switch (ri) {
-    case 8: return launch_nt8p_ri<TC, 8>(a, epi, st);
-    case 6: return launch_nt8p_ri<TC, 6>(a, epi, st);
-    case 5: return launch_nt8p_ri<TC, 5>(a, epi, st);
-    default: return launch_nt8p_ri<TC, 4>(a, epi, st);
+int launch_nt8p(const uvc_gemm_route& r, const NtArgs& a, hipStream_t st) {
+  if constexpr (sizeof(TC) == 4) return launch_nt8p_ri<TC, 8>(a, r.epilogue, st);
+  else switch (r.ri) {
+    case 8: return launch_nt8p_ri<TC, 8>(a, r.epilogue, st);
+    case 6: return launch_nt8p_ri<TC, 6>(a, r.epilogue, st);
+    case 5: return launch_nt8p_ri<TC, 5>(a, r.epilogue, st);
+    default: return launch_nt8p_ri<TC, 4>(a, r.epilogue, st);
   }
 }
-int launch_nt8p_f32(const NtArgs& a, int epi, int ri, hipStream_t st) { return launch_nt8p<float>(a, epi, ri, st); }
-int launch_nt8p_bf16(const NtArgs& a, int epi, int ri, hipStream_t st) { return launch_nt8p<bf16_t>(a, epi, ri, st); }
-bool nt8p_takes(const NtArgs& a, bool a_f32) { return nt8p_ok(a, a_f32); }
+
+}  // namespace
+
+extern "C" int uvc_gemm_nt_ln_supported(int32_t M, int32_t N, int32_t K, int32_t dtype, int32_t epilogue) {
+  // N = 384: k_gemm_row384_lnbwd<.., 1>, bf16 C / R only; its rows are bit-identical to the unfused pair, so the row threshold does not show in results
+  if (dtype == UVC_BF16 && N == 384) return M >= 4096 && K % 64 == 0 && K >= 384 && epi_resid(epilogue) && row384_fwd_fits(M, K);
+  if (dtype != UVC_BF16 || N != 192 || M < 16) return 0;      // any row count from 16 up: whether norm is fused must not depend on the batch
+  return ((K == 768 || K == 512 || K == 256) && epi_resid(epilogue)) || (K == 192 && epilogue == UVC_EPI_BIAS_RESID);
+}
+
+extern "C" int uvc_gemm_nt_q8_supported(int32_t M, int32_t hidden, int32_t embed_dim, int32_t dtype) {
+  return dtype == UVC_BF16 && embed_dim == 192 && hidden > 0 && hidden % 256 == 0 && M >= 4096;
+}
+
+extern "C" int uvc_gemm_nt_rows_supported(int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t ldc, int32_t dtype, int32_t epilogue) {
+  return dtype == UVC_BF16 && M >= 1 && M <= RP_MAX_M && K >= 8 && K <= RP_MAX_K && K % 8 == 0 && N >= 8 && N % 8 == 0 && lda >= K && ldb >= K && ldc >= N &&
+         lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && nt_rows_epilogue(epilogue);
+}
+
+extern "C" int uvc_gemm_nt_route(const uvc_gemm_nt_args* p, uvc_gemm_route* r) {
+  if (!p || !r) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: null pointer");
+  return nt_route(*p, r);
+}
+
+#define NT_BY_TC(F, ...) (r.c_f32 ? F<float>(__VA_ARGS__) : F<bf16_t>(__VA_ARGS__))
+#define NT_BY_TA_TC(F, ...) (r.a_f32 ? (r.c_f32 ? F<float, float>(__VA_ARGS__) : F<float, bf16_t>(__VA_ARGS__)) \
+                                     : (r.c_f32 ? F<bf16_t, float>(__VA_ARGS__) : F<bf16_t, bf16_t>(__VA_ARGS__)))
+extern "C" int uvc_gemm_nt(const uvc_gemm_nt_args* p, void* stream) {
+  uvc_gemm_route r;
+  if (const int rc = uvc_gemm_nt_route(p, &r)) return rc;
+  const NtArgs a = nt_args(*p);
+  const int e = r.epilogue;
+  hipStream_t st = (hipStream_t)stream;
+  switch (r.family) {
+    case UVC_ROUTE_NT:
+      if (r.t_f32) return launch_nt_epi<float, float, float>(a, e, st);
+      if (r.a_f32) return r.c_f32 ? launch_nt_epi<float, bf16_t, float>(a, e, st) : launch_nt_epi<float, bf16_t, bf16_t>(a, e, st);
+      return r.c_f32 ? launch_nt_epi<bf16_t, bf16_t, float>(a, e, st) : launch_nt_epi<bf16_t, bf16_t, bf16_t>(a, e, st);
+    case UVC_ROUTE_NT_ROWS: return NT_BY_TA_TC(launch_nt_rows, a, e, st);
+    case UVC_ROUTE_WS: return NT_BY_TA_TC(launch_ws, r, a, st);
+    case UVC_ROUTE_WS384: return r.nw == 8 ? launch_ws384<bf16_t, 8>(a, e, st) : NT_BY_TC(launch_ws384, a, e, st);
+    case UVC_ROUTE_WSN:
+    case UVC_ROUTE_WSN16: return NT_BY_TC(launch_wsn, r, a, st);
+    case UVC_ROUTE_WSN16_DMA: return r.c_f32 ? launch_ring<false>(r, a, st) : launch_ring<true>(r, a, st);
+    case UVC_ROUTE_ROW384: return launch_row384_fwd(a, e, st);
+    case UVC_ROUTE_NT256: return NT_BY_TC(launch_nt256, a, e, st);
+    case UVC_ROUTE_NT8P: return NT_BY_TC(launch_nt8p, r, a, st);
+    default: return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: route");
+  }
+}
+#undef NT_BY_TA_TC
+#undef NT_BY_TC
+#undef NT_EPI9
+#undef NT_LAUNCH
+
 
 // ================================================================================================
 //                                            TN (wgrad)
@@ -3619,142 +3603,158 @@ __global__ __launch_bounds__(256) void k_tn_reduce(const float* __restrict__ par
   for (int e = 0; e < VEC; ++e) dst[e] = (beta != 0.f ? beta * dst[e] : 0.f) + alpha * s[e];
 }
 
-// 0 = generic 128x64 tiles; 1 = 192x256, 2 = 256x192, 3 = 192x192, 4 = 96x192 (bf16 big tiles)
-static int tn_config(int N1, int N2) {
-  // 5 = 256 x 256 (LDS-DMA kernel, bf16 operands): DeiT-Base's shapes.  131 flop per operand byte through LDS against 108 for 192 x 256; the
-  // split-M kernels are bound by the L2 -> LDS rate of their 32-row stages (pipe 31 % busy at 0.75 PFLOP/s).  Wide matrices only: at
-  // DeiT-Tiny / Small widths the 192-wide tiles divide the shapes and leave more splits.
-  if (N1 % 256 == 0 && N2 % 256 == 0 && (N1 / 256) * (N2 / 256) >= 9) return 5;     // (r4: k_gemm_tn8p; 9 tiles = DeiT-Base's dW_proj)
+// ================================================================================================
+//                      TN: routing, launchers and the entry point (host code)
+// ================================================================================================
+namespace {
+
+using TnLaunch = int (*)(const TnArgs&, dim3, hipStream_t);
+template <int RI, int RJ>
+int launch_tn8p(const TnArgs& a, dim3 grid, hipStream_t st) {
+  UVC_MAX_LDS(T8_LDS, k_gemm_tn8p<RI, RJ>);
+  k_gemm_tn8p<RI, RJ><<<grid, 512, T8_LDS, st>>>(a);
+  return UVC_OK;
+}
+template <int B1, int B2, int W1, int W2>
+int launch_tn_dma(const TnArgs& a, dim3 grid, hipStream_t st) {
+  const int sh = TD_NST * (((TD_BM * ((B1 * 2 + 32) / 16 + (B2 * 2 + 32) / 16) + 63) / 64) * 1024) + 1024;
+  UVC_MAX_LDS(sh, k_gemm_tn_dma<B1, B2, W1, W2>);
+  k_gemm_tn_dma<B1, B2, W1, W2><<<grid, 512, sh, st>>>(a);
+  return UVC_OK;
+}
+template <int B1, int B2, int W1, int W2>
+int launch_tn_big(const TnArgs& a, dim3 grid, hipStream_t st) {      // float32 A (converted on load): the register-staged kernel
+  k_gemm_tn_big<float, B1, B2, W1, W2><<<grid, 512, 0, st>>>(a);
+  return UVC_OK;
+}
+
+// cfg -> tile and the kernels built for it.  k_gemm_tn8p (two-group schedule): dW2 79.4 -> 64.6 us, dW1 77.4 -> 60.9, dW_qkv 45.9 -> 40.9 against the ring
+// kernel k_gemm_tn_dma, bit-identical partial tiles (profiles/r6h_tn_probes.txt); k_gemm_tn_big takes float32 A.  cfg 0 is the generic 128 x 64 kernel.
+struct TnTile { int b1, b2; TnLaunch tn8p, dma, big; };
+const TnTile TN_TILES[7] = {
+    {TN_B1, TN_B2, nullptr, nullptr, nullptr},
+    {192, 256, launch_tn8p<6, 4>, launch_tn_dma<192, 256, 2, 4>, launch_tn_big<192, 256, 2, 4>},
+    {256, 192, launch_tn8p<8, 3>, launch_tn_dma<256, 192, 4, 2>, launch_tn_big<256, 192, 4, 2>},
+    {192, 192, launch_tn8p<6, 3>, launch_tn_dma<192, 192, 2, 4>, launch_tn_big<192, 192, 2, 4>},
+    {96, 192, nullptr, launch_tn_dma<96, 192, 2, 4>, nullptr},        // dW_proj of DeiT-Tiny: two tiles x 128 splits (the generic kernel ran it at 1.75 TB/s)
+    {256, 256, launch_tn8p<8, 4>, nullptr, nullptr},                  // DeiT-Base: 131 flop per operand byte through LDS against 108 for 192 x 256
+    {128, 256, launch_tn8p<4, 4>, nullptr, nullptr},                  // UVC_TN_128X256 only: not the default (profiles/r6n_tn_variants_base.txt)
+};
+
+// the tile configuration a shape takes with bf16 operands
+int tn_shape_cfg(int N1, int N2) {
+  if (N1 % 256 == 0 && N2 % 256 == 0 && (N1 / 256) * (N2 / 256) >= 9) return 5;     // 9 tiles = DeiT-Base's dW_proj; narrower shapes divide into 192-wide tiles
   if (N1 % 192 == 0 && N2 % 256 == 0) return 1;
   if (N1 % 256 == 0 && N2 % 192 == 0) return 2;
-  if (N1 % 192 == 0 && N2 % 192 == 0 && (N1 / 192) * (N2 / 192) >= 2) return 3;   // a single 192x192 tile would need 256 splits
-  if (N1 == 192 && N2 == 192) return 4;       // dW_proj of DeiT-Tiny: two 96x192 tiles x 128 splits (the generic kernel ran it at 1.75 TB/s)
+  if (N1 % 192 == 0 && N2 % 192 == 0 && (N1 / 192) * (N2 / 192) >= 2) return 3;     // a single 192 x 192 tile would need 256 splits
+  if (N1 == 192 && N2 == 192) return 4;
   return 0;
 }
-static void tn_tile(int cfg, int& b1, int& b2) { b1 = (cfg == 2 || cfg == 5) ? 256 : cfg == 4 ? 96 : cfg == 6 ? 128 : 192; b2 = (cfg == 1 || cfg == 5 || cfg == 6) ? 256 : 192; }
-static int tn_splits(int M, int N1, int N2, int cfg) {
+int tn_splits(int M, int N1, int N2, int cfg) {
   int tiles, target;
   if (cfg == 0) { tiles = ceil_div(N1, TN_B1) * ceil_div(N2, TN_B2); target = 768; }
   else {
-    int b1, b2; tn_tile(cfg, b1, b2); tiles = (N1 / b1) * (N2 / b2);
-    // one 8-wave group per CU -- on HALF the CUs where the output is a handful of tiles (DeiT-Tiny's 192-wide weights: 2-3 tiles): a split writes a float32 partial
-    // tile and the reduce reads it back, so 128 workgroups of twice the rows move half the partial bytes (50 MB of dW2's 245), and the dgrad chain on the other
-    // stream gets the CUs this HBM-bound GEMM does not need.  Measured in the step, same box (profiles/r5t): 256 / 192 / 128 / 96 / 64 workgroups
-    // 11.58 / 11.44 / 11.38 / 11.64 / 12.31 ms (the stand-alone sum RISES, 11.2 -> 11.9 ms: these GEMMs are slower alone on half the chip).
-    // The wider models keep the whole chip: DeiT-Small 15.6 -> 16.7 ms and DeiT-Base 23.4 -> 24.5 at 128 (192: +- 0 / -0.7 %), T2T-ViT-14 +0.7 %.
-    // Measured again once the side stream had become the backward's critical path (one event per block, vit_engine.hip): 128 / 160 / 192 / 256 workgroups
-    // 11.14 / 11.18 / 11.23 / 11.44 ms (profiles/r5z_ab_wgrad_targets.txt).
-    // (r6, with the two-group schedule for these tiles: 96 / 128 / 192 / 256 workgroups measured again, profiles/r6i_ab_wgrad_targets.txt)
-#ifndef UVC_TN_TARGET_FEW
-#define UVC_TN_TARGET_FEW 128
-#endif
-    target = tiles <= 4 ? UVC_TN_TARGET_FEW : 256;
+    tiles = (N1 / TN_TILES[cfg].b1) * (N2 / TN_TILES[cfg].b2);
+    // one workgroup per CU; on HALF the CUs where the output is a handful of tiles (DeiT-Tiny's 192-wide weights): half the float32 partial bytes, and the dgrad
+    // chain on the other stream gets the CUs.  128 / 160 / 192 / 256 workgroups: 11.14 / 11.18 / 11.23 / 11.44 ms per step (profiles/r5z_ab_wgrad_targets.txt,
+    // profiles/r6i_ab_wgrad_targets.txt)
+    target = tiles <= 4 ? 128 : 256;
   }
-  int splits = cfg == 0 ? ceil_div(target, tiles) : target / tiles;       // big tiles: one workgroup per CU (LDS), so at most 256 of them -- one more is a second round
+  int splits = cfg == 0 ? ceil_div(target, tiles) : target / tiles;       // big tiles: at most 256 workgroups -- one more is a second round
   const int max_splits = ceil_div(M, TN_BM);
   if (splits > max_splits) splits = max_splits;
-  // (r4) not more splits than rows justify: a split writes and the reduce re-reads a whole float32 tile, and below ~1 k rows per split that traffic is what the
-  // kernel moves (dW_proj of DeiT-Tiny: 128 splits of 788 rows; T2T-ViT-14 at 25 k rows: partial bytes = operand bytes).  Measured in the step, same box:
-  // >= 1024 rows: DeiT-Tiny 12.19 -> 12.06 ms (1536: 12.5), DeiT-Small / Base unchanged; the 192 x 192 tiles at M < 32 k (T2T-ViT-14) >= 2048 rows: 13.22 -> 12.88 ms
+  // not more splits than rows justify (a split writes and the reduce re-reads a float32 tile): >= 1024 rows per split, DeiT-Tiny 12.19 -> 12.06 ms; the
+  // 192 x 192 tiles at M < 32 k (T2T-ViT-14) >= 2048 rows, 13.22 -> 12.88 ms
   const int rmin = (cfg == 3 && M < 32768) ? 2048 : 1024;
   if (cfg != 0 && M >= 2 * rmin && splits > M / rmin) splits = M / rmin;
   return splits < 1 ? 1 : splits;
 }
+int tn_workspace_splits(int M, int N1, int N2) {             // large enough for the generic kernel and for the shape's own configuration
+  const int s0 = tn_splits(M, N1, N2, 0), s1 = tn_splits(M, N1, N2, tn_shape_cfg(N1, N2));
+  return s0 > s1 ? s0 : s1;
+}
+int64_t tn_workspace_bytes(int splits, int N1, int N2) { return (int64_t)splits * ((int64_t)N1 * N2 + N1) * 4; }   // partial tiles + partial column sums
+
+// Every check of uvc_gemm_tn, then configuration, kernel family, splits and rows per split.  No HIP call; pointers are read as integers only.
+int tn_route(const uvc_gemm_tn_args& p, uvc_gemm_route* r) {
+  *r = uvc_gemm_route{};
+  if (!p.A || !p.B || !p.C || !p.workspace) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_tn: null pointer");
+  if (p.M <= 0 || p.N1 <= 0 || p.N2 <= 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_tn: empty problem");
+  const int ch = (p.dtype == UVC_F32) ? 4 : 8;
+  if (p.N1 % ch || p.N2 % ch || p.lda % ch || p.ldb % ch)
+    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_tn: N1, N2, lda, ldb must be multiples of a 16-byte chunk");
+  if (p.workspace_bytes < tn_workspace_bytes(tn_workspace_splits(p.M, p.N1, p.N2), p.N1, p.N2))
+    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_tn: workspace too small");
+  if (p.dtype == UVC_F32 && !p.a_is_f32) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_tn: float32 mode needs float32 A");
+  if (p.dtype != UVC_F32 && p.dtype != UVC_BF16) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_tn: dtype must be UVC_F32 or UVC_BF16");
+  const bool a_f32 = p.a_is_f32 != 0;
+  int cfg = (p.dtype == UVC_BF16 && p.lda % 8 == 0 && p.ldb % 8 == 0) ? tn_shape_cfg(p.N1, p.N2) : 0;
+  // float32 A: k_gemm_tn_big's tiles (cfgs 1, 2, 3) or the generic kernel
+  if (cfg == 4 && a_f32) cfg = 0;
+  if (cfg == 5 && a_f32) cfg = (p.N1 % 192 == 0 && p.N2 % 256 == 0) ? 1 : (p.N1 % 256 == 0 && p.N2 % 192 == 0) ? 2 : 0;
+  // k_gemm_tn8p addresses its operands with 32-bit buffer offsets, the requests up to 256 rows past a split's end included: every offset below 2 GB.  Beyond,
+  // cfgs 1, 2, 3 take the ring kernel (64-bit offsets; same tiles, splits and k order: the same bits) and the 256 x 256 tiles the generic kernel -- checked
+  // on the configuration that will RUN
+  const bool tn8p_fits = (int64_t)(p.M + 256) * (p.lda > p.ldb ? p.lda : p.ldb) * 2 < (1ll << 31);
+  if (cfg == 5 && !tn8p_fits) cfg = 0;
+  if (cfg == 5 && p.variant == UVC_TN_128X256) cfg = 6;
+  const TnTile& t = TN_TILES[cfg];
+  r->cfg = cfg; r->b1 = t.b1; r->b2 = t.b2; r->a_f32 = a_f32; r->t_f32 = p.dtype == UVC_F32;
+  r->family = cfg == 0 ? UVC_ROUTE_TN : a_f32 ? UVC_ROUTE_TN_BIG : (t.tn8p && (!t.dma || (tn8p_fits && p.variant != UVC_TN_RING))) ? UVC_ROUTE_TN8P : UVC_ROUTE_TN_DMA;
+  const int rps = ceil_div(ceil_div(p.M, tn_splits(p.M, p.N1, p.N2, cfg)), TN_BM) * TN_BM;
+  r->rows_per_split = rps; r->splits = ceil_div(p.M, rps);
+  return UVC_OK;
+}
+
+}  // namespace
 
 extern "C" int uvc_gemm_tn_workspace_bytes(int M, int N1, int N2, int64_t* bytes, int* splits_out) {
   if (!bytes) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_tn_workspace_bytes: null");
-  const int s0 = tn_splits(M, N1, N2, 0), s1 = tn_splits(M, N1, N2, tn_config(N1, N2));
-  const int splits = s0 > s1 ? s0 : s1;                      // large enough for either kernel
-  *bytes = (int64_t)splits * ((int64_t)N1 * N2 + N1) * 4;   // partial tiles + partial column sums
+  const int splits = tn_workspace_splits(M, N1, N2);
+  *bytes = tn_workspace_bytes(splits, N1, N2);
   if (splits_out) *splits_out = splits;
   return UVC_OK;
 }
 
+extern "C" int uvc_gemm_tn_route(const uvc_gemm_tn_args* p, uvc_gemm_route* r) {
+  if (!p || !r) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_tn: null pointer");
+  return tn_route(*p, r);
+}
+
 extern "C" int uvc_gemm_tn(const uvc_gemm_tn_args* p, void* stream) {
-  if (!p || !p->A || !p->B || !p->C || !p->workspace) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_tn: null pointer");
-  if (p->M <= 0 || p->N1 <= 0 || p->N2 <= 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_tn: empty problem");
-  const int ch = (p->dtype == UVC_F32) ? 4 : 8;
-  if (p->N1 % ch || p->N2 % ch || p->lda % ch || p->ldb % ch)
-    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_tn: N1, N2, lda, ldb must be multiples of a 16-byte chunk");
-  int64_t need; int splits;
-  uvc_gemm_tn_workspace_bytes(p->M, p->N1, p->N2, &need, &splits);
-  if (p->workspace_bytes < need) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_tn: workspace too small");
-  int cfg = (p->dtype == UVC_BF16 && p->lda % 8 == 0 && p->ldb % 8 == 0) ? tn_config(p->N1, p->N2) : 0;
-  if (cfg == 4 && p->a_is_f32) cfg = 0;                      // the 96x192 tile exists as an LDS-DMA (bf16 operands) kernel only
-  if (cfg == 5 && p->a_is_f32) cfg = (p->N1 % 192 == 0 && p->N2 % 256 == 0) ? 1 : (p->N1 % 256 == 0 && p->N2 % 192 == 0) ? 2 : 0;
-  // k_gemm_tn8p (cfgs 1, 2, 3 with bf16 A outside variant 2; cfgs 5, 6) addresses its operands with 32-bit buffer offsets and marks the
-  // columns a tile lacks with offset 0x80000000: every offset, the requests up to 256 rows past a split's end included, must stay below
-  // 2 GB.  Beyond that, cfgs 1, 2, 3 take the ring kernel k_gemm_tn_dma (64-bit offsets; same tiles, splits and k order: the same bits) and
-  // the 256 x 256 tiles the generic kernel (the workspace is sized for either, see uvc_gemm_tn_workspace_bytes) -- checked on the
-  // configuration that will RUN
-  const bool tn8p_fits = (int64_t)(p->M + 256) * (p->lda > p->ldb ? p->lda : p->ldb) * 2 < (1ll << 31);
-  if (cfg == 5 && !tn8p_fits) cfg = 0;
-  const bool tn8p = tn8p_fits && p->variant != 2;
-  // variant 3 (A/B, r6): 128 x 256 tiles for the shapes that take 256 x 256 -- twice the tiles, half the splits: half the float32 partial bytes (DeiT-Base dW1: 66 -> 28 MB
-  // written and read back per launch) for 25 % fewer MFMAs per fragment read.  Measured (profiles/r6n_tn_variants_base.txt, GEMM + reduce, M = 25 344): dW2 141.9 -> 168.1 us,
-  // dW1 131.3 -> 154.2, dWqkv 98.4 -> 110.8, dWproj 49.4 -> 44.6: not the default
-  if (cfg == 5 && p->variant == 3) cfg = 6;
-  splits = tn_splits(p->M, p->N1, p->N2, cfg);
+  uvc_gemm_route r;
+  if (const int rc = uvc_gemm_tn_route(p, &r)) return rc;
   TnArgs a;
   a.A = p->A; a.B = p->B; a.part = (float*)p->workspace; a.M = p->M; a.N1 = p->N1; a.N2 = p->N2; a.lda = p->lda; a.ldb = p->ldb;
-  int rps = ceil_div(p->M, splits);
-  rps = ceil_div(rps, TN_BM) * TN_BM;
-  splits = ceil_div(p->M, rps);
-  a.rows_per_split = rps;
+  a.rows_per_split = r.rows_per_split;
   a.xcd_remap = 1;
-  a.bpart = p->colsum_out ? a.part + (size_t)splits * p->N1 * p->N2 : nullptr;
+  a.bpart = p->colsum_out ? a.part + (size_t)r.splits * p->N1 * p->N2 : nullptr;
   hipStream_t st = (hipStream_t)stream;
-  if (p->dtype == UVC_F32) {
-    if (!p->a_is_f32) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_tn: float32 mode needs float32 A");
-    dim3 grid(ceil_div(p->N1, TN_B1), ceil_div(p->N2, TN_B2), splits);
-    k_gemm_tn<float, float><<<grid, 256, 0, st>>>(a);
-  } else if (p->dtype == UVC_BF16) {
-    if (cfg == 0) {
-      dim3 grid(ceil_div(p->N1, TN_B1), ceil_div(p->N2, TN_B2), splits);
-      if (p->a_is_f32) k_gemm_tn<float, bf16_t><<<grid, 256, 0, st>>>(a);
+  const TnTile& t = TN_TILES[r.cfg];
+  const dim3 grid(ceil_div(p->N1, t.b1), ceil_div(p->N2, t.b2), r.splits);      // (the big tiles divide their shapes)
+  switch (r.family) {
+    case UVC_ROUTE_TN:
+      if (r.t_f32) k_gemm_tn<float, float><<<grid, 256, 0, st>>>(a);
+      else if (r.a_f32) k_gemm_tn<float, bf16_t><<<grid, 256, 0, st>>>(a);
       else k_gemm_tn<bf16_t, bf16_t><<<grid, 256, 0, st>>>(a);
-    } else {
-      int b1, b2;
-      tn_tile(cfg, b1, b2);
-      dim3 grid(p->N1 / b1, p->N2 / b2, splits);
-#define TN_BIG(TA_) \
-      if (cfg == 1) k_gemm_tn_big<TA_, 192, 256, 2, 4><<<grid, 512, 0, st>>>(a); \
-      else if (cfg == 2) k_gemm_tn_big<TA_, 256, 192, 4, 2><<<grid, 512, 0, st>>>(a); \
-      else k_gemm_tn_big<TA_, 192, 192, 2, 4><<<grid, 512, 0, st>>>(a);
-#define TN_DMA_ONE(B1_, B2_, W1_, W2_) { \
-        const int sh_ = TD_NST * (((TD_BM * (((B1_) * 2 + 32) / 16 + ((B2_) * 2 + 32) / 16) + 63) / 64) * 1024) + 1024; \
-        UVC_MAX_LDS(sh_, k_gemm_tn_dma<B1_, B2_, W1_, W2_>); \
-        k_gemm_tn_dma<B1_, B2_, W1_, W2_><<<grid, 512, sh_, st>>>(a); }
-      if (p->a_is_f32) { TN_BIG(float) }           // float32 A (converted on load): register-staged kernel
-      // (r6: these two stood BEHIND the unconditional cfg == 1 / cfg == 2 cases until now, i.e. variant 1 never reached them and the r4 / r6c "equal" were
-      //  the ring kernel measured against itself)
-      // r6: the two-group schedule for the 192 x 256 / 256 x 192 tiles too.  tools/tn_probes.sh on 126 workgroups (profiles/r6h_tn_probes.txt): the ring kernel's
-      // operand ring ALONE 32 us, its compute ALONE (no requests) 60 us of the 68 -- [24 transposing reads | wait | 32 MFMAs] in lock step add up to ~1 900 clocks per
-      // 32-row stage where either half needs ~800; k_gemm_tn8p requests a phase's fragments inside the MFMA block of the phase before: dW2 79.4 -> 64.6 us, dW1
-      // 77.4 -> 60.9 (bit-identical partial tiles).  variant 2: the ring kernel.
-      else if (tn8p && cfg == 1) { UVC_MAX_LDS(T8_LDS, k_gemm_tn8p<6, 4>); k_gemm_tn8p<6, 4><<<grid, 512, T8_LDS, st>>>(a); }
-      else if (tn8p && cfg == 2) { UVC_MAX_LDS(T8_LDS, k_gemm_tn8p<8, 3>); k_gemm_tn8p<8, 3><<<grid, 512, T8_LDS, st>>>(a); }
-      else if (cfg == 1) TN_DMA_ONE(192, 256, 2, 4)
-      else if (cfg == 2) TN_DMA_ONE(256, 192, 4, 2)
-      else if (cfg == 4) TN_DMA_ONE(96, 192, 2, 4)
-      else if (cfg == 5) { UVC_MAX_LDS(T8_LDS, k_gemm_tn8p<8, 4>); k_gemm_tn8p<8, 4><<<grid, 512, T8_LDS, st>>>(a); }
-      else if (cfg == 6) { UVC_MAX_LDS(T8_LDS, k_gemm_tn8p<4, 4>); k_gemm_tn8p<4, 4><<<grid, 512, T8_LDS, st>>>(a); }
-      // 192 x 192 tiles (dW_qkv of DeiT-Tiny / Small, every block weight of T2T-ViT-14): the two-group schedule by default -- 45.9 -> 40.9 us at
-      // 100 864 x 576 x 192, 67.6 -> 55.6 at 50 432 x 1152 x 384, 44 -> 37 on T2T's three shapes; bit-identical partial tiles (variant 2: the ring kernel).
-      // (The 192 x 256 / 256 x 192 tiles moved to the two-group schedule in r6 too, above.)  Past the 2 GB bound all three run on the ring kernel.
-      else if (tn8p && cfg == 3) { UVC_MAX_LDS(T8_LDS, k_gemm_tn8p<6, 3>); k_gemm_tn8p<6, 3><<<grid, 512, T8_LDS, st>>>(a); }
-      else TN_DMA_ONE(192, 192, 2, 4)
-#undef TN_DMA_ONE
-#undef TN_BIG
-    }
-  } else return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_tn: dtype must be UVC_F32 or UVC_BF16");
+      break;
+    case UVC_ROUTE_TN_BIG: if (const int rc = t.big(a, grid, st)) return rc; break;
+    case UVC_ROUTE_TN_DMA: if (const int rc = t.dma(a, grid, st)) return rc; break;
+    case UVC_ROUTE_TN8P: if (const int rc = t.tn8p(a, grid, st)) return rc; break;
+    default: return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_tn: route");
+  }
   UVC_CHECK_LAUNCH();
   const int n = p->N1 * p->N2;
   const int tot = n + (a.bpart ? p->N1 : 0);
   if (n % 4 == 0 && p->N2 % 4 == 0 && p->ldc % 4 == 0 && p->N1 % 4 == 0)
-    k_tn_reduce<4><<<ceil_div(tot / 4, 256), 256, 0, st>>>(a.part, p->C, n, p->ldc, p->N2, splits, p->alpha, p->alpha_ptr, p->beta, a.bpart, p->colsum_out, p->N1);
+    k_tn_reduce<4><<<ceil_div(tot / 4, 256), 256, 0, st>>>(a.part, p->C, n, p->ldc, p->N2, r.splits, p->alpha, p->alpha_ptr, p->beta, a.bpart, p->colsum_out, p->N1);
   else
-    k_tn_reduce<1><<<ceil_div(tot, 256), 256, 0, st>>>(a.part, p->C, n, p->ldc, p->N2, splits, p->alpha, p->alpha_ptr, p->beta, a.bpart, p->colsum_out, p->N1);
+    k_tn_reduce<1><<<ceil_div(tot, 256), 256, 0, st>>>(a.part, p->C, n, p->ldc, p->N2, r.splits, p->alpha, p->alpha_ptr, p->beta, a.bpart, p->colsum_out, p->N1);
   UVC_CHECK_LAUNCH();
   return UVC_OK;
 }
+
+static const char* const UVC_ROUTE_KERNELS[UVC_ROUTE_COUNT] = {
+    "k_gemm_nt", "k_gemm_nt_rows", "k_gemm_ws", "k_gemm_ws", "k_gemm_wsn", "k_gemm_wsn16", "k_gemm_wsn16_dma", "k_gemm_row384_lnbwd", "k_gemm_nt256", "k_gemm_nt8p",
+    "k_gemm_tn", "k_gemm_tn_big", "k_gemm_tn_dma", "k_gemm_tn8p"};
+extern "C" const char* uvc_gemm_route_kernel(int32_t family) { return family >= 0 && family < UVC_ROUTE_COUNT ? UVC_ROUTE_KERNELS[family] : nullptr; }

@@ -225,6 +225,29 @@ def gemm_nt_rows_supported(M, N, K, dtype, epilogue, lda=None, ldb=None, ldc=Non
     return bool(L.lib().uvc_gemm_nt_rows_supported(M, N, K, K if lda is None else lda, K if ldb is None else ldb, N if ldc is None else ldc, dtype, epilogue))
 
 
+def _route(fn, args, fields):
+    """(status, route) of a route query: args' members from `fields`; the route as a dict with the family's name and its kernel template."""
+    for k, v in fields.items():
+        setattr(args, k, v)
+    r = L.uvc_gemm_route()
+    rc = getattr(L.lib(), fn)(C.byref(args), C.byref(r))
+    out = {n: getattr(r, n) for n, _ in r._fields_}
+    out["family"] = L.ROUTE_FAMILIES[r.family]
+    out["kernel"] = L.lib().uvc_gemm_route_kernel(r.family).decode()
+    return rc, out
+
+
+def gemm_nt_route(**fields):
+    """Which kernel uvc_gemm_nt would run for the uvc_gemm_nt_args members given (integers; pointer members are never dereferenced, so any non-null
+    address stands for a tensor) -- no launch, no GPU.  Returns (status, route); the route means something where status is 0."""
+    return _route("uvc_gemm_nt_route", L.uvc_gemm_nt_args(), fields)
+
+
+def gemm_tn_route(**fields):
+    """The same for uvc_gemm_tn: kernel family, tile configuration, splits and rows per split."""
+    return _route("uvc_gemm_tn_route", L.uvc_gemm_tn_args(), fields)
+
+
 def gemm_lnbwd_supported(M, D, K, dtype) -> bool:
     return bool(L.lib().uvc_gemm_lnbwd_supported(M, D, K, dtype))
 
