@@ -558,7 +558,13 @@ __global__ __launch_bounds__(64 * WS_NW, (KT > 6 && WS_NW > 6) ? 1 : (NJ == 4 ||
       const size_t mo = (size_t)(ok ? m : 0);
       if (EPI == UVC_EPI_BIAS_RESID || EPI == UVC_EPI_BIAS_RESID_GATE) E.r[it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const TC*>(g.R) + mo * g.ldr + n);
       if (EPI == UVC_EPI_BIAS_RESID_GATE) E.r2[it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const TC*>(g.R2) + mo * g.ldr + n);
-      if (EPI == UVC_EPI_DGELU || EPI == UVC_EPI_MUL_AUX) E.ax[it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(g.aux) + mo * g.ldaux + n);
+      if (EPI == UVC_EPI_DGELU || EPI == UVC_EPI_MUL_AUX) {    // the lane's VN columns of aux (bf16): 16 bytes beside a bf16 C, 8 beside a float32 C
+        if constexpr (VN == 8) E.ax[it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(g.aux) + mo * g.ldaux + n);
+        else {
+          const u32x2 q = *reinterpret_cast<const u32x2*>(reinterpret_cast<const T*>(g.aux) + mo * g.ldaux + n);
+          E.ax[it][0] = q[0]; E.ax[it][1] = q[1];
+        }
+      }
       if (EPI == UVC_EPI_MUL_AUX_Q8) {          // 8 one-byte codes of GELU'(a) (include/uvc_kernels.h)
         const u32x2 q = *reinterpret_cast<const u32x2*>(reinterpret_cast<const unsigned char*>(g.aux) + mo * g.ldaux + n);
         E.ax[it][0] = q[0]; E.ax[it][1] = q[1];
@@ -608,14 +614,14 @@ __global__ __launch_bounds__(64 * WS_NW, (KT > 6 && WS_NW > 6) ? 1 : (NJ == 4 ||
         }
         if (EPI == UVC_EPI_DGELU) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
+          for (int e = 0; e < VN / 2; ++e) {
             v[2 * e] *= Gelu<T>::g(__uint_as_float(E.ax[it][e] << 16));
             v[2 * e + 1] *= Gelu<T>::g(__uint_as_float(E.ax[it][e] & 0xffff0000u));
           }
         }
         if (EPI == UVC_EPI_MUL_AUX) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
+          for (int e = 0; e < VN / 2; ++e) {
             v[2 * e] *= __uint_as_float(E.ax[it][e] << 16);
             v[2 * e + 1] *= __uint_as_float(E.ax[it][e] & 0xffff0000u);
           }
