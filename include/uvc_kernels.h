@@ -272,7 +272,7 @@ typedef struct uvc_ln_args {
                            all arithmetic and the dots stay float32 */
   int32_t defer_reduce; /* backward: leave the per-block partials of dgamma / dbeta / dots in `partial` (one private region per
                            call) and skip the two small reduction launches; uvc_layernorm_bwd_reduce_batch finishes many calls at once */
-  int32_t x_lowp;       /* x is stored as bf16 (statistics, normalisation and every sum stay float32); D % 64 == 0 only */
+  int32_t x_lowp;       /* x is stored as bf16 (statistics, normalisation and every sum stay float32) */
   int32_t reserved;
 } uvc_ln_args;
 /* one deferred uvc_layernorm_bwd call: its partial region and outputs (dots may be NULL) */

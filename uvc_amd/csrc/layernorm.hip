@@ -52,7 +52,9 @@ __global__ __launch_bounds__(256) void k_ln_fwd(uvc_ln_args a) {
   if (lane == 0) { a.mean[r] = mean; a.rstd[r] = rstd; }
 }
 
-template <typename TDY, int NV>
+// TX: element type of x; TG: element type of the gradient stream (dx, add1, add2) -- float32 or bf16, as in k_ln_bwd_v below (the engines'
+// bf16 mode hands both over at every embed_dim % 64 == 0 they accept, not only at the widths of the vector table)
+template <typename TX, typename TDY, typename TG, int NV>
 __global__ __launch_bounds__(256) void k_ln_bwd(uvc_ln_args a, int rpb) {
   __shared__ float red[4][2 * 64 * NV + 2];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd(uvc_ln_args a, int rpb) {
   const float invD = 1.0f / (float)a.D;
   for (int r = r0 + w; r < r1; r += 4) {
     const size_t off = row_off(r, a.rows_per_group, a.group_stride, a.D);
-    const float* x = reinterpret_cast<const float*>(a.x) + off;
+    const TX* x = reinterpret_cast<const TX*>(a.x) + off;
     const TDY* dy = reinterpret_cast<const TDY*>(a.dy) + (size_t)r * a.D;
     const float mean = a.mean[r], rstd = a.rstd[r];
     float xh[NV], gy[NV];
@@ -80,7 +82,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd(uvc_ln_args a, int rpb) {
       const int c = lane + 64 * i;
       const bool ok = c < a.D;
       const float d = ok ? ElemIO<TDY>::load(dy + c) : 0.f;
-      xh[i] = ok ? (x[c] - mean) * rstd : 0.f;
+      xh[i] = ok ? (ElemIO<TX>::load(x + c) - mean) * rstd : 0.f;
       gy[i] = d * gam[i];
       dgam[i] += d * xh[i];
       dbet[i] += d;
@@ -89,17 +91,17 @@ __global__ __launch_bounds__(256) void k_ln_bwd(uvc_ln_args a, int rpb) {
     }
     c1 = wave_sum(c1) * invD;
     c2 = wave_sum(c2) * invD;
-    float* dx = reinterpret_cast<float*>(a.dx) + off;
+    TG* dx = reinterpret_cast<TG*>(a.dx) + off;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c = lane + 64 * i;
       if (c < a.D) {
         float o = rstd * (gy[i] - c1 - xh[i] * c2);
-        const float xv = x[c];
-        if (a.add1) o += a1 * reinterpret_cast<const float*>(a.add1)[off + c];
-        if (a.add2) { const float t = reinterpret_cast<const float*>(a.add2)[off + c]; o += a2 * t; dotB += t * xv; }
-        dx[c] = o;
-        dotA += o * xv;
+        const float xv = ElemIO<TX>::load(x + c);
+        if (a.add1) o += a1 * ElemIO<TG>::load(reinterpret_cast<const TG*>(a.add1) + off + c);
+        if (a.add2) { const float t = ElemIO<TG>::load(reinterpret_cast<const TG*>(a.add2) + off + c); o += a2 * t; dotB += t * xv; }
+        ElemIO<TG>::store(dx + c, o);
+        dotA += o * xv;                     // (from the unrounded value, as in k_ln_bwd_v)
       }
     }
   }
@@ -452,13 +454,17 @@ template <typename T> int launch_bwd(const uvc_ln_args& a, hipStream_t st) {
     }
 #undef LNB_CASE
   }
-  if (!vec && (a.g_lowp || a.x_lowp)) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "layernorm_bwd: a bf16 gradient stream / bf16 x needs D % 64 == 0");
   if (!vec) {
-    if (nv <= 2) k_ln_bwd<T, 2><<<grid, 256, 0, st>>>(a, rpb);
-    else if (nv <= 3) k_ln_bwd<T, 3><<<grid, 256, 0, st>>>(a, rpb);
-    else if (nv <= 6) k_ln_bwd<T, 6><<<grid, 256, 0, st>>>(a, rpb);
-    else if (nv <= 12) k_ln_bwd<T, 12><<<grid, 256, 0, st>>>(a, rpb);
-    else k_ln_bwd<T, 16><<<grid, 256, 0, st>>>(a, rpb);
+    // any other width (and ragged group strides): one wave per row, scalar accesses, every combination of element types
+#define LNG(NV) do { \
+      if (a.x_lowp) { if (a.g_lowp) k_ln_bwd<bf16_t, T, bf16_t, NV><<<grid, 256, 0, st>>>(a, rpb); else k_ln_bwd<bf16_t, T, float, NV><<<grid, 256, 0, st>>>(a, rpb); } \
+      else { if (a.g_lowp) k_ln_bwd<float, T, bf16_t, NV><<<grid, 256, 0, st>>>(a, rpb); else k_ln_bwd<float, T, float, NV><<<grid, 256, 0, st>>>(a, rpb); } } while (0)
+    if (nv <= 2) LNG(2);
+    else if (nv <= 3) LNG(3);
+    else if (nv <= 6) LNG(6);
+    else if (nv <= 12) LNG(12);
+    else LNG(16);
+#undef LNG
   }
   UVC_CHECK_LAUNCH();
   if (a.defer_reduce) return UVC_OK;
