@@ -136,8 +136,9 @@ def make_bwd(family, rows, D, seed=0):
 
 
 # ----------------------------------------------------------------------------- references and bounds
-def fwd_reference(x, gamma, beta, eps=EPS):
-    """float64 LayerNorm of the rows x holds (any float type; taken as they are) with the data of its acceptance rules."""
+def fwd_reference(x, gamma, beta, eps=EPS, h=None):
+    """float64 LayerNorm of the rows x holds (any float type; taken as they are) with the data of its acceptance rules.  h: the summation depth of a
+    kernel outside layernorm.hip (tests/t2t_refs.py); None = h_of(D)."""
     x, gamma, beta = x.double(), gamma.double(), beta.double()
     D = x.shape[-1]
     mean = x.mean(-1)
@@ -145,7 +146,7 @@ def fwd_reference(x, gamma, beta, eps=EPS):
     var = (d * d).mean(-1)
     rstd = (var + eps).rsqrt()
     xh = d * rstd[:, None]
-    h = h_of(D)
+    h = h_of(D) if h is None else float(h)
     E_mean = 2.0 * h * U * x.abs().mean(-1)
     rho = (E_mean * E_mean + 2.0 * (h + 3.0) * U * var) / (2.0 * (var + eps)) + 4.0 * U
     E_y = gamma.abs() * (xh.abs() * rho[:, None] + rstd[:, None] * (E_mean[:, None] + U * mean.abs()[:, None] + U * d.abs())) \
@@ -153,7 +154,7 @@ def fwd_reference(x, gamma, beta, eps=EPS):
     return dict(y=xh * gamma + beta, mean=mean, var=var, rstd=rstd, E_mean=E_mean + U * mean.abs(), rho=rho, E_y=E_y)
 
 
-def bwd_reference(x, dy, gamma, mean, rstd, *, add1=None, a1=None, add2=None, a2=None, beta_acc=0.0, dg_old=None, db_old=None):
+def bwd_reference(x, dy, gamma, mean, rstd, *, add1=None, a1=None, add2=None, a2=None, beta_acc=0.0, dg_old=None, db_old=None, h=None):
     """float64 backward from the statistics handed over (see the module text) and its bounds.  a1 / a2 None means 1."""
     x, dy, gamma, mean, rstd = x.double(), dy.double(), gamma.double(), mean.double()[:, None], rstd.double()[:, None]
     rows, D = x.shape
@@ -166,7 +167,7 @@ def bwd_reference(x, dy, gamma, mean, rstd, *, add1=None, a1=None, add2=None, a2
         dx, T = dx + a1 * add1.double(), T + abs(a1) * add1.double().abs()
     if add2 is not None:
         dx, T = dx + a2 * add2.double(), T + abs(a2) * add2.double().abs()
-    h = h_of(D)
+    h = h_of(D) if h is None else float(h)
     E_c1 = 2.0 * h * U * gy.abs().mean(-1, keepdim=True)
     E_c2 = 2.0 * h * U * (gy * xh).abs().mean(-1, keepdim=True) + 2.0 * U * c2.abs()
     E_dx = rstd * (E_c1 + xh.abs() * E_c2) + 6.0 * U * T
