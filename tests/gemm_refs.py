@@ -1,7 +1,7 @@
 """Plain float64 references of uvc_gemm_nt (every epilogue of include/uvc_kernels.h) and uvc_gemm_tn, two seeded operand families and
 the acceptance rules that hold a kernel to them.  Torch only, CPU-runnable (every function works on the device of its operands), nothing
 from uvc_amd; tests/test_gemm_refs_cpu.py shows that the rules accept an honest float32 accumulation and reject subtly wrong results,
-tests/test_gemm_accuracy_gpu.py holds every kernel family of gemm.hip to them.
+tests/test_gemm_accuracy_gpu.py holds every kernel family of the gemm*.hip files to them.
 
 Operands are flat buffers with a leading dimension, as the C ABI takes them: ``view(buf, rows, cols, ld)`` is the [rows, cols] matrix.
 

@@ -1,4 +1,4 @@
-"""GPU: every kernel family of gemm.hip (UVC_ROUTE_*) against tests/gemm_refs.py -- exact results on the INTEGER operand family, the
+"""GPU: every kernel family of the gemm*.hip files (UVC_ROUTE_*) against tests/gemm_refs.py -- exact results on the INTEGER operand family, the
 float32 bound E on the RANDOM family -- at the smallest shapes that reach each tile edge.
 
 Every case first asks uvc_gemm_nt_route / uvc_gemm_tn_route for the route of exactly the arguments it is about to pass and asserts the

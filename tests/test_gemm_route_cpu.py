@@ -385,10 +385,20 @@ def test_tn_workspace_is_the_larger_of_generic_and_shape_cfg(tn, ops):
 
 
 # ---------------------------------------------------------------------------------------------------- every route
-def test_route_kernel_names_are_kernel_templates_of_gemm_hip(ops):
+def test_route_kernel_names_are_kernel_templates_of_one_gemm_family_file(ops):
+    """Every kernel template is defined in exactly one gemm*.hip (a kernel must not end up in two objects); the families that have a file of their
+    own are not in gemm.hip."""
+    import glob
     from uvc_amd import _lib as L
-    src = open(os.path.join(ROOT, "uvc_amd", "csrc", "gemm.hip")).read()
-    kernels = set(re.findall(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", src))
+    defined = {}                                              # kernel template name -> the files that define it
+    files = sorted(glob.glob(os.path.join(ROOT, "uvc_amd", "csrc", "gemm*.hip")))
+    for path in files:
+        for k in re.findall(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", open(path).read()):
+            defined.setdefault(k, []).append(os.path.basename(path))
+    assert "gemm.hip" in [os.path.basename(p) for p in files] and len(files) > 1
+    assert defined["k_gemm_nt"] == defined["k_gemm_nt_rows"] == ["gemm_nt_tiled.hip"] and defined["k_gemm_ws"] == ["gemm_nt_ws.hip"]
+    assert not {k: fs for k, fs in defined.items() if len(fs) != 1}, "a kernel template is defined in exactly one file"
+    kernels = set(defined)
     assert len(L.ROUTE_FAMILIES) == 14
     for fam in range(len(L.ROUTE_FAMILIES)):
         name = L.lib().uvc_gemm_route_kernel(fam)

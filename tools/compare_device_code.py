@@ -1,9 +1,15 @@
-"""Compare the gfx950 device code of two builds of one .hip file, kernel by kernel (run by hand after a change that must not touch kernels).
+"""Compare the gfx950 device code of two builds, kernel by kernel (run by hand after a change that must not touch kernels).
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-slp-vectorize -Iinclude --cuda-device-only -c uvc_amd/csrc/gemm.hip -o new.o   (and parent.o)
     python tools/compare_device_code.py parent.o new.o > profiles/<name>.txt
 
-Unbundles both objects, reads the kernel metadata (llvm-readelf --notes) and the symbol table (llvm-readelf -s), and compares for every kernel:
+Either side may be several objects, the two sides separated by `--` (a file split into several, or the reverse):
+
+    for f in uvc_amd/csrc/gemm*.hip; do hipcc <the same flags> --cuda-device-only -c $f -o new_$(basename $f .hip).o; done
+    python tools/compare_device_code.py parent.o -- new_gemm*.o > profiles/<name>.txt
+
+A side is the union of its objects' kernels by mangled name; a name that two objects of one side define is an error (a kernel must not end up in
+two objects).  Unbundles the objects, reads the kernel metadata (llvm-readelf --notes) and the symbol table (llvm-readelf -s), and compares for every kernel:
 function size, .vgpr_count, .agpr_count, .sgpr_count, .group_segment_fixed_size, .private_segment_fixed_size, .vgpr_spill_count, and the bytes
 of the function in .text.  Exit status 1 when anything differs."""
 import os
@@ -49,13 +55,26 @@ def load(obj, tmp, tag):
     return meta, syms
 
 
+def load_side(objs, tmp, tag):
+    """union of the objects' kernels; -> (metadata, functions, names defined by more than one object)"""
+    meta, syms, twice = {}, {}, []
+    for i, obj in enumerate(objs):
+        m, s = load(obj, tmp, f"{tag}{i}")
+        twice += [f"{k} ({obj})" for k in m if k in meta]
+        meta.update(m)
+        syms.update(s)
+        print(f"  {obj}: {len(m)} kernels")
+    return meta, syms, twice
+
+
 def main(a, b):
     with tempfile.TemporaryDirectory() as tmp:
-        ma, sa = load(a, tmp, "a")
-        mb, sb = load(b, tmp, "b")
+        ma, sa, ta = load_side(a, tmp, "a")
+        mb, sb, tb = load_side(b, tmp, "b")
     ka, kb = set(ma), set(mb)
-    print(f"kernels: {len(ka)} in {a}, {len(kb)} in {b}; only in first {sorted(ka - kb)}; only in second {sorted(kb - ka)}")
-    bad = len(ka ^ kb)
+    print(f"kernels: {len(ka)} in {' '.join(a)}, {len(kb)} in {' '.join(b)}; only in first {sorted(ka - kb)}; only in second {sorted(kb - ka)}")
+    print(f"defined by two objects of one side: {ta + tb}")
+    bad = len(ka ^ kb) + len(ta) + len(tb)
     nbytes = 0
     for k in sorted(ka & kb):
         diffs = [f"{f} {ma[k].get(f)} -> {mb[k].get(f)}" for f in FIELDS if ma[k].get(f) != mb[k].get(f)]
@@ -75,4 +94,7 @@ def main(a, b):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    args = sys.argv[1:]
+    if "--" in args:
+        sys.exit(main(args[:args.index("--")], args[args.index("--") + 1:]))
+    sys.exit(main(args[:1], args[1:2]))

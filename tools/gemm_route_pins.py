@@ -94,7 +94,7 @@ def run():
 
 
 def launches(d):
-    """The trace's launches of gemm.hip kernels in dispatch order: (kernel, grid, workgroup, LDS bytes)."""
+    """The trace's launches of the GEMM kernels (gemm*.hip) in dispatch order: (kernel, grid, workgroup, LDS bytes)."""
     f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
     if not f:
         raise SystemExit(f"no kernel_trace.csv under {d}")

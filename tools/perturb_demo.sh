@@ -2,7 +2,8 @@
 # Shows once that tests/test_streaming_batch_gpu.py (r3) and tests/test_wide_models_gpu.py (r4) go red when a production kernel is wrong.
 #   here (build container):  tools/perturb_demo.sh build     -> tools/perturb/libuvc_hip_{ws,lnbwd,wide,row384,tn8p,row384fwd}.so (git-ignored; they travel with gpurun)
 #   on the GPU box:          tools/perturb_demo.sh run       -> gpurun_out/perturb_demo.txt
-# The perturbed libraries are built from sed-edited COPIES of gemm.hip under /tmp: the product source carries no test switch.
+# The perturbed libraries are built from sed-edited COPIES of the file that holds the kernel (gemm_nt_ws.hip for k_gemm_ws, gemm.hip for the others) under /tmp:
+# the product source carries no test switch.
 set -u
 R=$(cd "$(dirname "$0")/.." && pwd)
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-slp-vectorize -Wno-unused-value -Wno-unused-result -I$R/include -I$R/uvc_amd/csrc"
@@ -10,7 +11,7 @@ if [ "${1:-}" = build ]; then
   python -m uvc_amd.build > /dev/null || exit 1
   mkdir -p /tmp/perturb "$R/tools/perturb"
   # 1. k_gemm_ws: every output tile of the K <= 192 streaming GEMM (qkv, fc1, dfc2, dproj) scaled by 1.02
-  sed 's|\*reinterpret_cast<f32x4\*>(stg + li \* EPW + j \* 16 + gq \* 4) = c;|*reinterpret_cast<f32x4*>(stg + li * EPW + j * 16 + gq * 4) = c * 1.02f;|' "$R/uvc_amd/csrc/gemm.hip" > /tmp/perturb/gemm_ws.hip
+  sed 's|\*reinterpret_cast<f32x4\*>(stg + li \* EPW + j \* 16 + gq \* 4) = c;|*reinterpret_cast<f32x4*>(stg + li * EPW + j * 16 + gq * 4) = c * 1.02f;|' "$R/uvc_amd/csrc/gemm_nt_ws.hip" > /tmp/perturb/gemm_ws.hip
   # 2. k_gemm_wsn_lnbwd_dma: dx of the fused dgrad + LayerNorm backward scaled by 1.02
   sed 's|o\[e\] = rstd \* (c0\[e\] - c1 - xh \* c2);   |o[e] = 1.02f * rstd * (c0[e] - c1 - xh * c2);   |' "$R/uvc_amd/csrc/gemm.hip" > /tmp/perturb/gemm_lnbwd.hip
   # 3. (r4) the wide-tile NT kernels of DeiT-Small / Base (k_gemm_nt256 and k_gemm_nt8p share NT_EPILOGUE_TILE): staged accumulator x 1.02
@@ -29,10 +30,11 @@ PY
   # 6. (r4) k_gemm_row384_lnbwd<.., 1> (D = 384: fc2 / attn.proj + residual + the next LayerNorm in one launch): the GEMM result x 1.02 before bias / residual
   sed 's|float t = epi_scale_bias(v\[i\]\[e\], 1.0f, bv\[e\]);|float t = epi_scale_bias(v[i][e] * 1.02f, 1.0f, bv[e]);|' "$R/uvc_amd/csrc/gemm.hip" > /tmp/perturb/gemm_row384fwd.hip
   for v in ws lnbwd wide row384 tn8p row384fwd; do
-    cmp -s /tmp/perturb/gemm_$v.hip "$R/uvc_amd/csrc/gemm.hip" && { echo "perturbation $v did not apply"; exit 1; }
-    sed -i 's|#include "common.h"|#include "'"$R"'/uvc_amd/csrc/common.h"|; s|#include "../../include/uvc_kernels.h"|#include "'"$R"'/include/uvc_kernels.h"|' /tmp/perturb/gemm_$v.hip
+    src=gemm; [ $v = ws ] && src=gemm_nt_ws      # the file the variant is a copy of: its object is the one the perturbed object replaces
+    cmp -s /tmp/perturb/gemm_$v.hip "$R/uvc_amd/csrc/$src.hip" && { echo "perturbation $v did not apply"; exit 1; }
+    sed -i 's|#include "gemm_common.h"|#include "'"$R"'/uvc_amd/csrc/gemm_common.h"|' /tmp/perturb/gemm_$v.hip
     /opt/rocm/bin/hipcc $FLAGS -c /tmp/perturb/gemm_$v.hip -o /tmp/perturb/gemm_$v.o || exit 1
-    objs=$(ls "$R"/uvc_amd/csrc/build/*.o | grep -v '/gemm.o$')
+    objs=$(ls "$R"/uvc_amd/csrc/build/*.o | grep -v "/$src.o\$")
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$R/tools/perturb/libuvc_hip_$v.so" $objs /tmp/perturb/gemm_$v.o || exit 1
   done
   ls -la "$R/tools/perturb"

@@ -9,724 +9,11 @@
 // or 32 B (TN) so ds_read_b128 / ds_read_b64_tr_b16 fragment reads are bank-conflict free.
 // Operands are swapped in the MFMA (a = B-fragment, b = A-fragment) so every lane ends up with 4
 // CONSECUTIVE output columns of one row -> 16-byte (fp32) / 8-byte (bf16) epilogue accesses.
-#include <type_traits>
-#include "common.h"
-#include "../../include/uvc_kernels.h"
-
-// ------------------------------------------------------------------------------------------------
-template <typename T> struct Mma;
-template <> struct Mma<bf16_t> {
-  static constexpr int CH = 8;     // elements per 16-byte chunk
-  static constexpr int KSTEP = 32; // k elements per MFMA step (4 lane groups x 1 chunk)
-  typedef bf16x8 Frag;
-  static __device__ __forceinline__ f32x4 mma(const Frag& a, const Frag& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct Mma<float> {
-  static constexpr int CH = 4;
-  static constexpr int KSTEP = 16;
-  typedef f32x4 Frag;
-  static __device__ __forceinline__ f32x4 mma(const Frag& a, const Frag& b, f32x4 c) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], c, 0, 0, 0);
-    return c;
-  }
-};
-
-// 16-byte chunk of compute type T loaded from a global array of type TS (convert on load)
-template <typename TS, typename T> struct ChunkLoad;
-template <typename T> struct ChunkLoad<T, T> {
-  static __device__ __forceinline__ u32x4 ld(const T* p) { return *reinterpret_cast<const u32x4*>(p); }
-};
-template <> struct ChunkLoad<float, bf16_t> {   // 8 floats -> 8 bf16
-  static __device__ __forceinline__ u32x4 ld(const float* p) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p);
-    const f32x4 b = *reinterpret_cast<const f32x4*>(p + 4);
-    u32x4 r;
-    r[0] = pack_bf16x2(a[0], a[1]); r[1] = pack_bf16x2(a[2], a[3]);
-    r[2] = pack_bf16x2(b[0], b[1]); r[3] = pack_bf16x2(b[2], b[3]);
-    return r;
-  }
-};
-
-template <typename T> __device__ __forceinline__ typename Mma<T>::Frag lds_frag(const char* p) {
-  return *reinterpret_cast<const typename Mma<T>::Frag*>(p);
-}
-
-// ================================================================================================
-//                                            NT
-// ================================================================================================
-constexpr int NT_BM = 128, NT_BN = 128;
-// LDS row stride in bytes (8 chunks + 32 B pad).  ds_read_b128 is served in the lane groups {0-3,12-15,20-27},
-// {4-11,16-19,28-31}, ...: a fragment read (row = lane & 15, chunk = lane >> 4) is conflict-free only when the stride
-// in words is 8, 24, 40 or 56 mod 64; the obvious +16 B pad (36 mod 64) costs 2 LDS cycles per group.
-constexpr int NT_ROWB = 128 + 32;
-
-template <typename T> struct OutIO;
-template <> struct OutIO<float> {
-  static __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-  static __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-};
-template <> struct OutIO<bf16_t> {
-  static __device__ __forceinline__ void st4(bf16_t* p, f32x4 v) {
-    u32x2 r; r[0] = pack_bf16x2(v[0], v[1]); r[1] = pack_bf16x2(v[2], v[3]);
-    *reinterpret_cast<u32x2*>(p) = r;
-  }
-  static __device__ __forceinline__ f32x4 ld4(const bf16_t* p) {
-    const u32x2 r = *reinterpret_cast<const u32x2*>(p);
-    f32x4 v; v[0] = __uint_as_float(r[0] << 16); v[1] = __uint_as_float(r[0] & 0xffff0000u);
-    v[2] = __uint_as_float(r[1] << 16); v[3] = __uint_as_float(r[1] & 0xffff0000u);
-    return v;
-  }
-};
-
-struct NtArgs {
-  const void* A; const void* B; void* C; void* C2;
-  const float* bias; const void* R; const void* R2; const void* aux; const float* dptr;      // R, R2: the residual rows, element type of C
-  int M, N, K, lda, ldb, ldc, ldr, ldaux;
-  float alpha;
-  const float* alpha_ptr;   // optional device scalar multiplied into alpha
-  // optional second output of the N == 192 residual epilogues: LayerNorm of the output rows (uvc_gemm_nt_args.ln_*)
-  const float* ln_gamma; const float* ln_beta; void* ln_out; float* ln_mean; float* ln_rstd; float ln_eps;
-  int no_dma;               // uvc_gemm_nt_args.force_generic == 2: the register-staged streaming kernels instead of the LDS-DMA rings
-};
-
-// vector of VN consecutive outputs in the coalesced epilogue layout
-template <typename TC> struct OutVec;
-template <> struct OutVec<float> {
-  static constexpr int VN = 4;
-  static __device__ __forceinline__ void st(float* p, const float* v) { *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]}; }
-};
-template <> struct OutVec<bf16_t> {
-  static constexpr int VN = 8;
-  static __device__ __forceinline__ void st(bf16_t* p, const float* v) {
-    u32x4 r;
-    r[0] = pack_bf16x2(v[0], v[1]); r[1] = pack_bf16x2(v[2], v[3]); r[2] = pack_bf16x2(v[4], v[5]); r[3] = pack_bf16x2(v[6], v[7]);
-    *reinterpret_cast<u32x4*>(p) = r;
-  }
-  static __device__ __forceinline__ void st_nt(bf16_t* p, const float* v) {      // streaming output: not read again before the caches have turned over
-    u32x4 r;
-    r[0] = pack_bf16x2(v[0], v[1]); r[1] = pack_bf16x2(v[2], v[3]); r[2] = pack_bf16x2(v[4], v[5]); r[3] = pack_bf16x2(v[6], v[7]);
-    __builtin_nontemporal_store(r, reinterpret_cast<u32x4*>(p));
-  }
-};
-template <typename T, int VN> __device__ __forceinline__ void load_vec(const T* p, float* v);
-template <> __device__ __forceinline__ void load_vec<float, 4>(const float* p, float* v) {
-  const f32x4 r = *reinterpret_cast<const f32x4*>(p); v[0] = r[0]; v[1] = r[1]; v[2] = r[2]; v[3] = r[3];
-}
-template <> __device__ __forceinline__ void load_vec<float, 8>(const float* p, float* v) { load_vec<float, 4>(p, v); load_vec<float, 4>(p + 4, v + 4); }
-template <> __device__ __forceinline__ void load_vec<bf16_t, 8>(const bf16_t* p, float* v) {
-  const u32x4 r = *reinterpret_cast<const u32x4*>(p);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { v[2 * e] = __uint_as_float(r[e] << 16); v[2 * e + 1] = __uint_as_float(r[e] & 0xffff0000u); }
-}
-template <> __device__ __forceinline__ void load_vec<bf16_t, 4>(const bf16_t* p, float* v) {
-  const u32x2 r = *reinterpret_cast<const u32x2*>(p);
-  v[0] = __uint_as_float(r[0] << 16); v[1] = __uint_as_float(r[0] & 0xffff0000u);
-  v[2] = __uint_as_float(r[1] << 16); v[3] = __uint_as_float(r[1] & 0xffff0000u);
-}
-
-// Residual operands have the element type of C (float32 stream: 4 floats per 16 bytes; bf16 stream: 8 per 16 bytes, 4 per 8 bytes)
-template <typename TC> struct Resid;
-template <> struct Resid<float> {
-  typedef u32x4 Raw4;                            // four consecutive columns
-  static __device__ __forceinline__ Raw4 ld4(const void* base, size_t elem) { return *reinterpret_cast<const u32x4*>(reinterpret_cast<const float*>(base) + elem); }
-  static __device__ __forceinline__ f32x4 f4(const Raw4& r) { return __builtin_bit_cast(f32x4, r); }
-  // VN = 4 consecutive columns in 16 bytes
-  static __device__ __forceinline__ void get(const u32x4& r, float* v) { const f32x4 f = __builtin_bit_cast(f32x4, r); v[0] = f[0]; v[1] = f[1]; v[2] = f[2]; v[3] = f[3]; }
-};
-template <> struct Resid<bf16_t> {
-  typedef u32x2 Raw4;
-  static __device__ __forceinline__ Raw4 ld4(const void* base, size_t elem) { return *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(base) + elem); }
-  static __device__ __forceinline__ f32x4 f4(const Raw4& r) {
-    return f32x4{__uint_as_float(r[0] << 16), __uint_as_float(r[0] & 0xffff0000u), __uint_as_float(r[1] << 16), __uint_as_float(r[1] & 0xffff0000u)};
-  }
-  // VN = 8 consecutive columns in 16 bytes
-  static __device__ __forceinline__ void get(const u32x4& r, float* v) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v[2 * e] = __uint_as_float(r[e] << 16); v[2 * e + 1] = __uint_as_float(r[e] & 0xffff0000u); }
-  }
-};
-
-// Epilogue arithmetic with the rounding points spelled out (hipcc contracts a*b + c*d differently from kernel to kernel):
-// every NT kernel computes the same bits for the same accumulator, so a row's result does not depend on which kernel the
-// problem size selects (tests/test_fullsize_gpu.py compares a 512-image run with an 8-image run bit for bit).
-__device__ __forceinline__ float epi_scale_bias(float acc, float alpha, float bias) { return __builtin_fmaf(acc, alpha, bias); }
-__device__ __forceinline__ float epi_gate_mix(float v, float r2, float d0, float d1) { return __builtin_fmaf(d1, v, __builtin_fmaf(d0, r2, 0.0f)); }
-constexpr int EP_LD = 68;   // floats per staged accumulator row (64 + 4 pad: conflict-free 16-byte LDS writes)
-
-// Epilogue of ROWS staged accumulator rows x 64 columns of one wave (row r = output row mrow0 + r, columns ncol0 .. ncol0 + 63):
-// scale / bias / residual / gate mix / activation, then 16-byte row-contiguous stores.  Shared by the NT kernels that leave through an
-// LDS transpose, so that a row's bits do not depend on the kernel that produced its accumulator.
-// Staging layouts: SWZ = false: [ROWS][EP_LD] floats (padded rows); SWZ = true: [ROWS][64] floats, the 16-byte column group cg of row r
-// at group cg ^ (r & 7) (no padding: 4 KB per 16 rows; conflict-free for the accumulator writes and for these reads).
-// bias_v: the VN bias values of this lane's columns (0 where the epilogue has no bias or the column is past N), loaded once per tile.
-template <bool SWZ> __device__ __forceinline__ float* stg_at(float* stg, int r, int cg) {
-  return SWZ ? stg + r * 64 + ((cg ^ (r & 7)) << 2) : stg + r * EP_LD + (cg << 2);
-}
-template <typename TC, int EPI> __device__ __forceinline__ void nt_load_bias(const NtArgs& g, int lane, int ncol0, float* bias_v) {
-  constexpr int VN = OutVec<TC>::VN, LPR = 64 / VN;
-  constexpr bool has_bias = EPI == UVC_EPI_BIAS || EPI == UVC_EPI_BIAS_GELU || EPI == UVC_EPI_BIAS_GELU_OUT || EPI == UVC_EPI_BIAS_RESID ||
-                            EPI == UVC_EPI_BIAS_RESID_GATE || EPI == UVC_EPI_BIAS_GELU_GRAD;
-  const int n = ncol0 + (lane % LPR) * VN;
-#pragma unroll
-  for (int e = 0; e < VN; ++e) bias_v[e] = (has_bias && n + e < g.N) ? g.bias[n + e] : 0.f;
-}
-// Operand rows of an epilogue (R, R2, aux) requested AHEAD of the rows they meet: the epilogue of a big tile is a chain of [transpose 16 rows
-// through LDS | load their operands | arithmetic | store]; with the loads inside the chain every 16-row step was a memory round trip (dfc2 x GELU'
-// of DeiT-Base: 24 us of epilogue per 256 x 256 tile against 16 us of k-loop).  bf16 C only (16 bytes = the lane's 8 columns); a lane whose
-// columns are not a whole aligned vector (ragged N, odd leading dimensions) keeps loading in place.
-template <int NIT> struct EpiPre { u32x4 r[NIT], r2[NIT], ax[NIT]; };
-template <int EPI> struct EpiOperands {
-  static constexpr bool R = EPI == UVC_EPI_BIAS_RESID || EPI == UVC_EPI_BIAS_RESID_GATE, R2 = EPI == UVC_EPI_BIAS_RESID_GATE,
-                        AUX = EPI == UVC_EPI_DGELU || EPI == UVC_EPI_MUL_AUX;
-  static constexpr int COUNT = (R ? 1 : 0) + (R2 ? 1 : 0) + (AUX ? 1 : 0);
-};
-template <int EPI, int ROWS>
-__device__ __forceinline__ void nt_epilogue_prefetch(const NtArgs& g, int lane, int mrow0, int ncol0, EpiPre<ROWS / 8>& P) {
-  const int cc = (lane & 7) * 8, n = ncol0 + cc;
-  const bool nfull = (n + 8 <= g.N) && ((g.ldc % 8) == 0);
-#pragma unroll
-  for (int it = 0; it < ROWS / 8; ++it) {
-    const int m = mrow0 + it * 8 + (lane >> 3);
-    if (m < g.M && nfull) {
-      const size_t mo = (size_t)m;
-      if (EpiOperands<EPI>::R && (g.ldr % 8) == 0) P.r[it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(g.R) + mo * g.ldr + n);
-      if (EpiOperands<EPI>::R2 && (g.ldr % 8) == 0) P.r2[it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(g.R2) + mo * g.ldr + n);
-      if (EpiOperands<EPI>::AUX && (g.ldaux % 8) == 0) P.ax[it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(g.aux) + mo * g.ldaux + n);
-    }
-  }
-}
-template <typename T, typename TC, int EPI, int ROWS = 32, bool SWZ = false, bool PRE = false>
-__device__ __forceinline__ void nt_epilogue_rows(const NtArgs& g, float* stg, int lane, int mrow0, int ncol0, float alpha, float d0, float d1,
-                                                 const float* bias_v, const EpiPre<ROWS / 8>* pre = nullptr) {
-  static_assert(!PRE || (sizeof(TC) == 2 && sizeof(T) == 2), "operand prefetch: bf16 C and operands only");
-  constexpr int VN = OutVec<TC>::VN;
-  constexpr int LPR = 64 / VN;                  // lanes per 64-column row
-  constexpr int RPI = 64 / LPR;                 // rows per wave instruction
-  TC* __restrict__ C = reinterpret_cast<TC*>(g.C);
-  const int cc = (lane % LPR) * VN;
-  const int n = ncol0 + cc;
-  const bool nfull = (n + VN <= g.N) && ((g.ldc % VN) == 0);
-#pragma unroll
-  for (int it = 0; it < ROWS / RPI; ++it) {
-    const int r = it * RPI + lane / LPR;
-    const int m = mrow0 + r;
-    float v[VN];
-    load_vec<float, 4>(stg_at<SWZ>(stg, r, cc >> 2), v);
-    if (VN == 8) load_vec<float, 4>(stg_at<SWZ>(stg, r, (cc >> 2) + 1), v + 4);
-    if (m < g.M && n < g.N) {
-      const size_t mo = (size_t)m;
-#pragma unroll
-      for (int e = 0; e < VN; ++e) v[e] = epi_scale_bias(v[e], alpha, bias_v[e]);
-      if (EPI == UVC_EPI_BIAS_GELU_OUT) {
-#pragma unroll
-        for (int e = 0; e < VN; ++e) v[e] = Gelu<T>::f(v[e]);
-      }
-      if (EPI == UVC_EPI_BIAS_RESID || EPI == UVC_EPI_BIAS_RESID_GATE) {
-        const TC* rp = reinterpret_cast<const TC*>(g.R) + mo * g.ldr + n;
-        float rv[VN];
-        if (nfull && (g.ldr % VN) == 0) { if constexpr (PRE) Resid<TC>::get(pre->r[it], rv); else load_vec<TC, VN>(rp, rv); }
-        else {
-#pragma unroll
-          for (int e = 0; e < VN; ++e) rv[e] = (n + e < g.N) ? ElemIO<TC>::load(rp + e) : 0.f;
-        }
-#pragma unroll
-        for (int e = 0; e < VN; ++e) v[e] += rv[e];
-      }
-      if (EPI == UVC_EPI_BIAS_RESID_GATE) {
-        const TC* rp = reinterpret_cast<const TC*>(g.R2) + mo * g.ldr + n;
-        float rv[VN];
-        if (nfull && (g.ldr % VN) == 0) { if constexpr (PRE) Resid<TC>::get(pre->r2[it], rv); else load_vec<TC, VN>(rp, rv); }
-        else {
-#pragma unroll
-          for (int e = 0; e < VN; ++e) rv[e] = (n + e < g.N) ? ElemIO<TC>::load(rp + e) : 0.f;
-        }
-#pragma unroll
-        for (int e = 0; e < VN; ++e) v[e] = epi_gate_mix(v[e], rv[e], d0, d1);
-      }
-      if (EPI == UVC_EPI_DGELU || EPI == UVC_EPI_MUL_AUX) {
-        const T* ap = reinterpret_cast<const T*>(g.aux) + mo * g.ldaux + n;
-        float av[VN];
-        if (nfull && (g.ldaux % VN) == 0) { if constexpr (PRE) Resid<TC>::get(pre->ax[it], av); else load_vec<T, VN>(ap, av); }
-        else {
-#pragma unroll
-          for (int e = 0; e < VN; ++e) av[e] = (n + e < g.N) ? ElemIO<T>::load(ap + e) : 0.f;
-        }
-#pragma unroll
-        for (int e = 0; e < VN; ++e) v[e] *= (EPI == UVC_EPI_MUL_AUX) ? av[e] : Gelu<T>::g(av[e]);
-      }
-      float u[VN];
-      if (EPI == UVC_EPI_BIAS_GELU_GRAD) {
-#pragma unroll
-        for (int e = 0; e < VN; ++e) { float fo, go; Gelu<T>::fg(v[e], fo, go); u[e] = fo; v[e] = go; }
-      }
-      TC* cp = C + mo * g.ldc + n;
-      // (GELU' / GELU of the training forward: streaming outputs, non-temporal -- DeiT-Base 23.31 -> 23.06 ms, profiles/r5zz_ab_nt_wide.txt)
-      if constexpr (EPI == UVC_EPI_BIAS_GELU_GRAD && sizeof(TC) == 2) { if (nfull) OutVec<TC>::st_nt(cp, v); }
-      else
-      if (nfull) OutVec<TC>::st(cp, v);
-      if (nfull) {}
-      else {
-#pragma unroll
-        for (int e = 0; e < VN; ++e) if (n + e < g.N) ElemIO<TC>::store(cp + e, v[e]);
-      }
-      if (EPI == UVC_EPI_BIAS_GELU || EPI == UVC_EPI_BIAS_GELU_GRAD) {
-        TC* c2 = reinterpret_cast<TC*>(g.C2) + mo * g.ldc + n;
-        if (EPI == UVC_EPI_BIAS_GELU) {
-#pragma unroll
-          for (int e = 0; e < VN; ++e) u[e] = Gelu<T>::f(v[e]);
-        }
-        if constexpr (EPI == UVC_EPI_BIAS_GELU_GRAD && sizeof(TC) == 2) { if (nfull) OutVec<TC>::st_nt(c2, u); }
-        else
-        if (nfull) OutVec<TC>::st(c2, u);
-        if (nfull) {}
-        else {
-#pragma unroll
-          for (int e = 0; e < VN; ++e) if (n + e < g.N) ElemIO<TC>::store(c2 + e, u[e]);
-        }
-      }
-    }
-  }
-}
-
-template <typename TA, typename T, typename TC, int EPI>
-__global__ __launch_bounds__(256, 2) void k_gemm_nt(NtArgs g) {
-  typedef Mma<T> MM;
-  constexpr int CH = MM::CH;
-  constexpr int BK = 8 * CH;                    // elements per K tile (128 B of T per row)
-  __shared__ __attribute__((aligned(16))) char smem[(NT_BM + NT_BN) * NT_ROWB];
-  char* sA = smem;
-  char* sB = smem + NT_BM * NT_ROWB;
-  const TA* __restrict__ A = reinterpret_cast<const TA*>(g.A);
-  const T* __restrict__ B = reinterpret_cast<const T*>(g.B);
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wm = w >> 1, wn = w & 1;
-  // XCD-aware tile order.  Workgroups are dispatched round-robin over the 8 XCDs (block b -> XCD b % 8),
-  // each with a private L2.  All N tiles of one M tile get block ids that are congruent mod 8 and
-  // adjacent in dispatch order, so the A panel is fetched from HBM once and re-read from that XCD's L2.
-  const int ntn = (g.N + NT_BN - 1) / NT_BN;
-  const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-  const int bn = q % ntn, bm = (q / ntn) * 8 + xcd;
-  const int m0 = bm * NT_BM, n0 = bn * NT_BN;
-  if (m0 >= g.M) return;
-  const int lc = tid & 7, lr = tid >> 3;        // chunk column / first row of this thread's loads
-
-  u32x4 ra[4], rb[4];
-  auto gload = [&](int k0) {
-    const int kc = k0 + lc * CH;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = lr + 32 * i;
-      const int m = m0 + row, n = n0 + row;
-      u32x4 z = {0u, 0u, 0u, 0u};
-      ra[i] = (m < g.M && kc < g.K) ? ChunkLoad<TA, T>::ld(A + (size_t)m * g.lda + kc) : z;
-      rb[i] = (n < g.N && kc < g.K) ? ChunkLoad<T, T>::ld(B + (size_t)n * g.ldb + kc) : z;
-    }
-  };
-  auto lstore = [&]() {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = lr + 32 * i;
-      *reinterpret_cast<u32x4*>(sA + row * NT_ROWB + lc * 16) = ra[i];
-      *reinterpret_cast<u32x4*>(sB + row * NT_ROWB + lc * 16) = rb[i];
-    }
-  };
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nk = (g.K + BK - 1) / BK;
-  gload(0);
-  lstore();
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    if (kt + 1 < nk) gload((kt + 1) * BK);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      typename MM::Frag fa[4], fb[4];
-      const int coff = (ks * 4 + (lane >> 4)) * 16;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) fa[i] = lds_frag<T>(sA + (wm * 64 + i * 16 + (lane & 15)) * NT_ROWB + coff);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) fb[j] = lds_frag<T>(sB + (wn * 64 + j * 16 + (lane & 15)) * NT_ROWB + coff);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = MM::mma(fb[j], fa[i], acc[i][j]);
-    }
-    if (kt + 1 < nk) {
-      __syncthreads();
-      lstore();
-      __syncthreads();
-    }
-  }
-
-  // ---- epilogue.  The MFMA leaves lane (l) with row m = (l&15), columns (l>>4)*4+{0..3} of each 16x16
-  // tile.  Each wave transposes its 64x64 sub-tile through LDS, 32 rows at a time, so that global
-  // accesses are whole 128-byte (bf16) / 256-byte (fp32) row segments: 16 bytes per lane.
-  float alpha = g.alpha;
-  if (g.alpha_ptr) alpha *= *g.alpha_ptr;
-  float d0 = 0.f, d1 = 1.f;
-  if (EPI == UVC_EPI_BIAS_RESID_GATE) { d0 = g.dptr[0]; d1 = g.dptr[1]; }
-  float* stg = reinterpret_cast<float*>(smem) + w * (32 * EP_LD);
-  float bias_v[OutVec<TC>::VN];
-  nt_load_bias<TC, EPI>(g, lane, n0 + wn * 64, bias_v);
-  __syncthreads();
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-#pragma unroll
-    for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        *reinterpret_cast<f32x4*>(stg + (ii * 16 + (lane & 15)) * EP_LD + j * 16 + (lane >> 4) * 4) = acc[2 * h + ii][j];
-    __syncthreads();
-    nt_epilogue_rows<T, TC, EPI>(g, stg, lane, m0 + wm * 64 + h * 32, n0 + wn * 64, alpha, d0, d1, bias_v);
-    __syncthreads();
-  }
-}
-
-// ================================================================================================
-//                          NT, row panels (bf16, M <= 1024, K <= 1024)
-// ================================================================================================
-// The step's turnaround (the last block's class-token rows, the head, their backward) and the teacher's tail are GEMMs on a few hundred rows:
-// 128 x 128 tiles put M = 512 on 8 of the 256 CUs, and their k loop is one 64-element tile in flight between two barriers -- 12 to 16 serial
-// memory round trips for 0.1 GFLOP.  Here a workgroup owns 16 rows x 64 columns (M = 512, N = 192: 96 workgroups; the head's N = 1000: 512), wave w
-// the 16 columns 16w..16w+15, and a wave requests its A and W fragments of 16 k-steps (512 elements of K: 128 VGPRs) before the first MFMA: one
-// memory latency per half instead of one per tile.  No LDS in the k loop (the four waves read the same 16 A rows: 24 KB at K = 768, from L2).
-// The accumulator is k_gemm_nt's: one k-ordered chain of 2 * ceil(K / 64) MFMA steps, zero-padded past K, leaving through the same staged
-// epilogue -- the same bits (tests/test_row_gemm_gpu.py).
-constexpr int RP_BM = 16, RP_BN = 64, RP_KS = 16;      // rows, columns of a workgroup; k-steps (of 32) requested at a time
-constexpr int RP_MAX_M = 1024, RP_MAX_K = 1024;
-
-// NS k-steps of a wave's chain from step s0: every fragment requested first (straight-line code, no branch: one batch of loads, answered in order),
-// then the MFMAs.  A lane whose row is past M / N, or whose chunk is past K, reads a valid address and multiplies zeros.
-template <typename TA, int NS>
-__device__ __forceinline__ f32x4 rp_steps(const TA* __restrict__ Ap, const bf16_t* __restrict__ Bp, int s0, int K, int gq, bool mv, bool nv, f32x4 acc) {
-  typedef Mma<bf16_t> MM;
-  u32x4 fa[NS], fb[NS];
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    const int kc = (s0 + s) * 32 + gq * 8, kl = kc < K ? kc : K - 8;
-    fa[s] = ChunkLoad<TA, bf16_t>::ld(Ap + kl);
-    fb[s] = ChunkLoad<bf16_t, bf16_t>::ld(Bp + kl);
-  }
-  const u32x4 z = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    const bool in = (s0 + s) * 32 + gq * 8 < K;
-    acc = MM::mma(__builtin_bit_cast(MM::Frag, (nv && in) ? fb[s] : z), __builtin_bit_cast(MM::Frag, (mv && in) ? fa[s] : z), acc);
-  }
-  return acc;
-}
-
-template <typename TA, typename TC, int EPI>
-__global__ __launch_bounds__(256) void k_gemm_nt_rows(NtArgs g) {
-  typedef bf16_t T;
-  typedef Mma<T> MM;
-  __shared__ __attribute__((aligned(16))) float stg[RP_BM * EP_LD];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, li = lane & 15, gq = lane >> 4;
-  const int ntn = (g.N + RP_BN - 1) / RP_BN;
-  const int m0 = ((int)blockIdx.x / ntn) * RP_BM, n0 = ((int)blockIdx.x % ntn) * RP_BN;
-  const int m = m0 + li, n = n0 + w * 16 + li;
-  const bool mv = m < g.M, nv = n < g.N;
-  // (rows past M / N: row 0's addresses, the values replaced by zeros -- every load unconditional, so that they leave as one batch)
-  const TA* __restrict__ Ap = reinterpret_cast<const TA*>(g.A) + (size_t)(mv ? m : 0) * g.lda;
-  const T* __restrict__ Bp = reinterpret_cast<const T*>(g.B) + (size_t)(nv ? n : 0) * g.ldb;
-  float alpha = g.alpha;
-  if (g.alpha_ptr) alpha *= *g.alpha_ptr;
-  float d0 = 0.f, d1 = 1.f;
-  if (EPI == UVC_EPI_BIAS_RESID_GATE) { d0 = g.dptr[0]; d1 = g.dptr[1]; }
-  float bias_v[OutVec<TC>::VN];
-  nt_load_bias<TC, EPI>(g, lane, n0, bias_v);
-
-  // k_gemm_nt's chain is 2 * ceil(K / 64) steps of 32; the steps run here in batches of 16 or 8, and a step past the chain's end multiplies two zero
-  // fragments like any step past K: it adds +0 to an accumulator that started at +0 and so is never -0 -- the same bits
-  const int nsteps = 2 * ((g.K + 63) / 64);
-  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-  int s0 = 0;
-  for (; nsteps - s0 > RP_KS / 2; s0 += RP_KS) acc = rp_steps<TA, RP_KS>(Ap, Bp, s0, g.K, gq, mv, nv, acc);
-  if (s0 < nsteps) acc = rp_steps<TA, RP_KS / 2>(Ap, Bp, s0, g.K, gq, mv, nv, acc);
-  // lane (li, gq) holds row li, columns 4 gq .. 4 gq + 3 of the wave's 16: the 16 x 64 tile is staged once and leaves as whole row segments,
-  // eight rows per wave (waves 0 and 1)
-  *reinterpret_cast<f32x4*>(stg + li * EP_LD + w * 16 + gq * 4) = acc;
-  __syncthreads();
-  if (w < 2) nt_epilogue_rows<T, TC, EPI, 8>(g, stg + w * 8 * EP_LD, lane, m0 + w * 8, n0, alpha, d0, d1, bias_v);
-}
-
-// ================================================================================================
-//                     NT, weights-stationary / activation-streaming (bf16, K <= 192)
-// ================================================================================================
-// The DeiT GEMMs are skinny: M = B*197 rows (1e5) against K, N of a few hundred, i.e. HBM-bound
-// streaming of A and C with a weight matrix that fits in registers.  Each wave keeps the MFMA B
-// fragments of its 64 output columns in VGPRs for its whole life (KT*4 fragments), the workgroup
-// (3 waves = 192 columns) walks M persistently in 64-row tiles, A is staged once per tile through a
-// double-buffered LDS image (register prefetch of tile i+1 under the MFMAs of tile i) and shared by
-// the three waves, and C leaves through a wave-private LDS transpose as whole 128/256-byte rows.
-// LDS traffic per MFMA is half of the generic kernel's (no B reads) and A is read exactly once per
-// 192-column group; groups of one tile sequence are placed on one XCD so they share its L2.
-constexpr int WS_BM = 64;
-
-// NJ = 16-column accumulator tiles per wave: 4 (64 columns, 96 VGPRs of W at K = 192, two waves per SIMD) or 2 (32 columns, 48 VGPRs,
-// eight waves per workgroup, four per SIMD: the GELU epilogues of fc1 overlap its stores better)
-// KT = 12 (K = 384: DeiT-Small / T2T-ViT widths) runs as 6 waves x 32 columns: the wave's W slice is 96 VGPRs again, the two A images
-// (64 rows x 800 B) and the transpose buffers take 116 KB of dynamic LDS, one workgroup per CU.
-template <typename TA, typename TC, int EPI, int KT, int WS_NW, int NJ = 4>
-__global__ __launch_bounds__(64 * WS_NW, (KT > 6 && WS_NW > 6) ? 1 : (NJ == 4 || KT > 6) ? 2 : 4) void k_gemm_ws(NtArgs g, int ngroups, int nslots) {
-  typedef bf16_t T;
-  typedef Mma<T> MM;
-  constexpr int ROWB = KT * 64 + 32;             // bytes per staged A row (KT*32 bf16 + pad; words = 8 or 40 mod 64, see NT_ROWB)
-  constexpr int CPR = KT * 4;                    // 16-byte chunks per row
-  constexpr int NLD = (WS_BM * CPR + 64 * WS_NW - 1) / (64 * WS_NW);
-  constexpr int CW = 16 * NJ, EPW = CW + 4;         // columns per wave; floats per staged accumulator row
-  constexpr int VN = OutVec<TC>::VN, LPR = CW / VN, RPI = 64 / LPR;
-  constexpr bool DYN = KT > 6;
-  constexpr int IMGB = WS_BM * ROWB;
-  extern __shared__ __attribute__((aligned(16))) char ws_dyn[];
-  __shared__ __attribute__((aligned(16))) char sA_st[DYN ? 16 : 2 * IMGB];
-  __shared__ __attribute__((aligned(16))) float sStage_st[DYN ? 4 : WS_NW * 16 * EPW];
-  char* const sAb = DYN ? ws_dyn : sA_st;
-  float* const sStg = DYN ? reinterpret_cast<float*>(ws_dyn + 2 * IMGB) : sStage_st;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, gq = lane >> 4, li = lane & 15;
-  const int L = blockIdx.x;
-  const int grp = (L >> 3) % ngroups, slot = (L / (8 * ngroups)) * 8 + (L & 7);
-  const int n0 = grp * CW * WS_NW + w * CW;
-  const bool active = n0 < g.N;                  // N % 64 == 0: a wave is either fully inside or idle
-  const TA* __restrict__ A = reinterpret_cast<const TA*>(g.A);
-  const T* __restrict__ W = reinterpret_cast<const T*>(g.B);
-  TC* __restrict__ C = reinterpret_cast<TC*>(g.C);
-  const int ntiles = (g.M + WS_BM - 1) / WS_BM;
-
-  typename MM::Frag bf[NJ][KT];
-  if (active) {
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int ks = 0; ks < KT; ++ks)
-        bf[j][ks] = __builtin_bit_cast(typename MM::Frag, *reinterpret_cast<const u32x4*>(W + (size_t)(n0 + j * 16 + li) * g.ldb + (ks * 4 + gq) * 8));
-  }
-  float alpha = g.alpha;
-  if (g.alpha_ptr) alpha *= *g.alpha_ptr;
-  float d0 = 0.f, d1 = 1.f;
-  if (EPI == UVC_EPI_BIAS_RESID_GATE) { d0 = g.dptr[0]; d1 = g.dptr[1]; }
-  const int cc = (lane % LPR) * VN;
-  const int n = n0 + cc;
-  float bias_v[VN];
-#pragma unroll
-  for (int e = 0; e < VN; ++e) bias_v[e] = 0.f;
-  if (active && (EPI == UVC_EPI_BIAS || EPI == UVC_EPI_BIAS_GELU || EPI == UVC_EPI_BIAS_GELU_OUT || EPI == UVC_EPI_BIAS_RESID || EPI == UVC_EPI_BIAS_RESID_GATE ||
-                 EPI == UVC_EPI_BIAS_GELU_GRAD || EPI == UVC_EPI_BIAS_GELU_GRAD_Q8)) {
-#pragma unroll
-    for (int e = 0; e < VN; ++e) bias_v[e] = g.bias[n + e];
-  }
-
-  u32x4 ra[NLD];
-  auto gload = [&](int tile) {
-    const int m0 = tile * WS_BM;
-    const u32x4 z = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int id = tid + 64 * WS_NW * i, row = id / CPR, c = id % CPR;
-      const int m = m0 + row;
-      ra[i] = (row < WS_BM && m < g.M) ? ChunkLoad<TA, T>::ld(A + (size_t)m * g.lda + c * 8) : z;
-    }
-  };
-  auto lstore = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int id = tid + 64 * WS_NW * i, row = id / CPR, c = id % CPR;
-      if (row < WS_BM) *reinterpret_cast<u32x4*>(sAb + buf * IMGB + row * ROWB + c * 16) = ra[i];
-    }
-  };
-
-  // epilogue operands (residual rows / GELU pre-activation) are prefetched one 16-row sub-tile ahead into
-  // registers, so their HBM latency hides under the epilogue math of the previous sub-tile and the MFMAs
-  // of the current one.  The accumulator transpose buffer is private to a wave: DS operations of one wave
-  // execute in order, so only a compiler-level wave barrier separates its writes from its reads.
-  constexpr int IT = 16 / RPI;
-  struct Epi { u32x4 r[IT]; u32x4 r2[IT]; u32x4 ax[IT]; };      // r, r2: VN residual values of C's element type in 16 bytes
-  auto eload = [&](Epi& E, int tile_, int sub_) {
-    if (!active) return;
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-      const int m = tile_ * WS_BM + sub_ * 16 + it * RPI + lane / LPR;
-      const bool ok = m < g.M && tile_ < ntiles;
-      const size_t mo = (size_t)(ok ? m : 0);
-      if (EPI == UVC_EPI_BIAS_RESID || EPI == UVC_EPI_BIAS_RESID_GATE) E.r[it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const TC*>(g.R) + mo * g.ldr + n);
-      if (EPI == UVC_EPI_BIAS_RESID_GATE) E.r2[it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const TC*>(g.R2) + mo * g.ldr + n);
-      if (EPI == UVC_EPI_DGELU || EPI == UVC_EPI_MUL_AUX) {    // the lane's VN columns of aux (bf16): 16 bytes beside a bf16 C, 8 beside a float32 C
-        if constexpr (VN == 8) E.ax[it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(g.aux) + mo * g.ldaux + n);
-        else {
-          const u32x2 q = *reinterpret_cast<const u32x2*>(reinterpret_cast<const T*>(g.aux) + mo * g.ldaux + n);
-          E.ax[it][0] = q[0]; E.ax[it][1] = q[1];
-        }
-      }
-      if (EPI == UVC_EPI_MUL_AUX_Q8) {          // 8 one-byte codes of GELU'(a) (include/uvc_kernels.h)
-        const u32x2 q = *reinterpret_cast<const u32x2*>(reinterpret_cast<const unsigned char*>(g.aux) + mo * g.ldaux + n);
-        E.ax[it][0] = q[0]; E.ax[it][1] = q[1];
-      }
-    }
-  };
-  auto subtile = [&](int buf_, int m0_, int sub_, const Epi& E) {
-    if (!active) return;
-    float* stg = sStg + w * (16 * EPW);
-    {
-      typename MM::Frag fa[KT];
-#pragma unroll
-      for (int ks = 0; ks < KT; ++ks) fa[ks] = lds_frag<T>(sAb + buf_ * IMGB + (sub_ * 16 + li) * ROWB + (ks * 4 + gq) * 16);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        f32x4 c = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < KT; ++ks) c = MM::mma(bf[j][ks], fa[ks], c);
-        *reinterpret_cast<f32x4*>(stg + li * EPW + j * 16 + gq * 4) = c;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    unsigned qc[IT][2];                                     // UVC_EPI_BIAS_GELU_GRAD_Q8: the lane's 8 one-byte codes of each of its rows
-#pragma unroll
-    for (int it = 0; it < IT; ++it) { qc[it][0] = 0u; qc[it][1] = 0u; }
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-      const int r = it * RPI + lane / LPR;
-      const int m = m0_ + sub_ * 16 + r;
-      float v[VN];
-      load_vec<float, VN>(stg + r * EPW + cc, v);
-      if (m < g.M) {
-        const size_t mo = (size_t)m;
-#pragma unroll
-        for (int e = 0; e < VN; ++e) v[e] = epi_scale_bias(v[e], alpha, bias_v[e]);
-        if (EPI == UVC_EPI_BIAS_RESID || EPI == UVC_EPI_BIAS_RESID_GATE) {
-          float rv[VN];
-          Resid<TC>::get(E.r[it], rv);
-#pragma unroll
-          for (int e = 0; e < VN; ++e) v[e] += rv[e];
-        }
-        if (EPI == UVC_EPI_BIAS_RESID_GATE) {
-          float rv[VN];
-          Resid<TC>::get(E.r2[it], rv);
-#pragma unroll
-          for (int e = 0; e < VN; ++e) v[e] = epi_gate_mix(v[e], rv[e], d0, d1);
-        }
-        if (EPI == UVC_EPI_DGELU) {
-#pragma unroll
-          for (int e = 0; e < VN / 2; ++e) {
-            v[2 * e] *= Gelu<T>::g(__uint_as_float(E.ax[it][e] << 16));
-            v[2 * e + 1] *= Gelu<T>::g(__uint_as_float(E.ax[it][e] & 0xffff0000u));
-          }
-        }
-        if (EPI == UVC_EPI_MUL_AUX) {
-#pragma unroll
-          for (int e = 0; e < VN / 2; ++e) {
-            v[2 * e] *= __uint_as_float(E.ax[it][e] << 16);
-            v[2 * e + 1] *= __uint_as_float(E.ax[it][e] & 0xffff0000u);
-          }
-        }
-        if constexpr (EPI == UVC_EPI_MUL_AUX_Q8) {
-          static_assert(VN == 8, "q8 epilogue: bf16 C");
-#pragma unroll
-          for (int e = 0; e < 8; ++e)            // (byte -> float is one v_cvt_f32_ubyteN)
-            v[e] *= __builtin_fmaf((float)((E.ax[it][e >> 2] >> (8 * (e & 3))) & 0xffu), UVC_Q8_STEP, UVC_Q8_LO);
-        }
-        if (EPI == UVC_EPI_BIAS_GELU_OUT) {
-#pragma unroll
-          for (int e = 0; e < VN; ++e) v[e] = Gelu<T>::f(v[e]);
-        }
-        float u[VN];
-        if (EPI == UVC_EPI_BIAS_GELU_GRAD || EPI == UVC_EPI_BIAS_GELU_GRAD_Q8) {
-#pragma unroll
-          for (int e = 0; e < VN; ++e) { float fo, go; Gelu<T>::fg(v[e], fo, go); u[e] = fo; v[e] = go; }
-        }
-        if constexpr (EPI == UVC_EPI_BIAS_GELU_GRAD_Q8) {
-          // GELU'(a) as one byte per activation (include/uvc_kernels.h): 8 codes = 8 bytes per lane, 64-byte row pieces per wave; GELU(a) as before.  Both stream
-          // past the caches (read again in the backward / by fc2)
-          static_assert(VN == 8, "q8 epilogue: bf16 C2");
-          unsigned qw[2] = {0u, 0u};
-#pragma unroll
-          for (int e = 0; e < 8; ++e)       // v_cvt_pk_u8_f32: round to nearest, saturate to [0, 255], pack into byte e & 3 -- two VALU instructions per code
-            qw[e >> 2] = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_fmaf(v[e], 1.0f / UVC_Q8_STEP, -UVC_Q8_LO / UVC_Q8_STEP), e & 3, qw[e >> 2]);
-          qc[it][0] = qw[0]; qc[it][1] = qw[1];            // stored behind the loop: 16 bytes per lane (below)
-          OutVec<TC>::st_nt(reinterpret_cast<TC*>(g.C2) + mo * g.ldc + n, u);
-        } else {
-        // GELU'(a) and GELU(a) of the training forward are STREAMING outputs (310 MB per block, read again in the backward / by fc2 after the caches have
-        // turned over): non-temporal stores.  Alone 90.2 -> 83.1 us; in the step 11.19 -> 10.96 ms (GELU' only: 79.8 us alone, 11.09 in the step) -- the rest of
-        // the step keeps the Infinity Cache (profiles/r5zz_ab_nt_stores.txt).  K = 192 only: at K = 384 (DeiT-Small, T2T-ViT-14) the same stores are within
-        // noise or 0.5 % slower (profiles/r5zz_ab_nt_wide.txt)
-        if constexpr (EPI == UVC_EPI_BIAS_GELU_GRAD && sizeof(TC) == 2 && KT == 6) OutVec<TC>::st_nt(C + mo * g.ldc + n, v);
-        else
-        // (also tried, each within +- 0.4 % of the step: non-temporal dA stores of dfc2 x GELU', non-temporal loads of its GELU' operand, nt on the LDS-DMA loads
-        //  of the weight gradients and of the attention backward -- profiles/r5zz_ab_nt_sites.txt)
-        OutVec<TC>::st(C + mo * g.ldc + n, v);
-        if (EPI == UVC_EPI_BIAS_GELU || EPI == UVC_EPI_BIAS_GELU_GRAD) {
-          if (EPI == UVC_EPI_BIAS_GELU) {
-#pragma unroll
-            for (int e = 0; e < VN; ++e) u[e] = Gelu<T>::f(v[e]);
-          }
-          if constexpr (EPI == UVC_EPI_BIAS_GELU_GRAD && sizeof(TC) == 2 && KT == 6) OutVec<TC>::st_nt(reinterpret_cast<TC*>(g.C2) + mo * g.ldc + n, u);
-          else
-          OutVec<TC>::st(reinterpret_cast<TC*>(g.C2) + mo * g.ldc + n, u);
-        }
-        }
-      }
-    }
-    if constexpr (EPI == UVC_EPI_BIAS_GELU_GRAD_Q8) {
-      // The codes leave as 16 bytes per lane, ONE store instruction per 16-row sub-tile instead of two of 8 bytes: fc1's epilogue is bound by its store
-      // instructions as much as by its bytes (8-byte stores of the codes: the step 10.93 -> 10.90 ms where the tensor not written at all gives 10.70,
-      // profiles/r6d, r6b).  Lanes l, l ^ 1 hold neighbouring 8-column groups of the SAME two rows (it = 0, 1): the even lane takes both groups of row 0,
-      // the odd lane both groups of row 1 (one DPP quad permute per dword).
-      const bool odd = lane & 1;
-      if constexpr (IT == 2) {
-        static_assert(LPR == 8 && RPI == 8, "q8 epilogue: four waves x 64 columns");
-        const unsigned s0 = odd ? qc[0][0] : qc[1][0], s1 = odd ? qc[0][1] : qc[1][1];      // what the partner stores: my codes of ITS row
-        const unsigned r0 = (unsigned)__builtin_amdgcn_mov_dpp((int)s0, 0xB1, 0xF, 0xF, true);      // quad_perm [1, 0, 3, 2]: lane ^ 1
-        const unsigned r1 = (unsigned)__builtin_amdgcn_mov_dpp((int)s1, 0xB1, 0xF, 0xF, true);
-        const int m = m0_ + sub_ * 16 + (odd ? RPI : 0) + lane / LPR;
-        if (m < g.M) {
-          const u32x4 o = odd ? u32x4{r0, r1, qc[1][0], qc[1][1]} : u32x4{qc[0][0], qc[0][1], r0, r1};
-          __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(reinterpret_cast<unsigned char*>(g.C) + (size_t)m * g.ldc + (n & ~15)));
-        }
-      } else {
-        // eight waves x 32 columns: one row per lane and sub-tile; the even lane of a pair stores both 8-column groups of the row
-        static_assert(IT == 1 && LPR == 4, "q8 epilogue: eight waves x 32 columns");
-        const unsigned r0 = (unsigned)__builtin_amdgcn_mov_dpp((int)qc[0][0], 0xB1, 0xF, 0xF, true);
-        const unsigned r1 = (unsigned)__builtin_amdgcn_mov_dpp((int)qc[0][1], 0xB1, 0xF, 0xF, true);
-        const int m = m0_ + sub_ * 16 + lane / LPR;
-        if (m < g.M && !odd)
-          __builtin_nontemporal_store(u32x4{qc[0][0], qc[0][1], r0, r1}, reinterpret_cast<u32x4*>(reinterpret_cast<unsigned char*>(g.C) + (size_t)m * g.ldc + n));
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-  };
-
-  int tile = slot;
-  if (tile >= ntiles) return;
-  Epi E0, E1;
-  gload(tile);
-  eload(E0, tile, 0);
-  lstore(0);
-  __syncthreads();
-  int buf = 0;
-  for (; tile < ntiles; tile += nslots) {
-    const int next = tile + nslots;
-    if (next < ntiles) gload(next);
-    const int m0 = tile * WS_BM;
-    eload(E1, tile, 1);
-    subtile(buf, m0, 0, E0);
-    eload(E0, tile, 2);
-    subtile(buf, m0, 1, E1);
-    eload(E1, tile, 3);
-    subtile(buf, m0, 2, E0);
-    eload(E0, next, 0);
-    subtile(buf, m0, 3, E1);
-    if (next < ntiles) lstore(buf ^ 1);
-    __syncthreads();
-    buf ^= 1;
-  }
-}
+//
+// Two kernel families have files of their own, each with its launchers: gemm_nt_tiled.hip (k_gemm_nt, k_gemm_nt_rows) and gemm_nt_ws.hip (k_gemm_ws);
+// uvc_gemm_nt reaches them through uvc_gemm::launch_* (gemm_common.h, which also holds what the NT kernels share).  The other families, the routing
+// of uvc_gemm_nt and all of uvc_gemm_tn are here.
+#include "gemm_common.h"
 
 // ================================================================================================
 //        NT, weights-stationary, one 16-column slice of the FULL reduction per wave (bf16, N == 192)
@@ -2483,7 +1770,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt8p(NtArgs g, int tiles_m, int
 //                      NT: routing, launchers and the entry point (host code)
 // ================================================================================================
 // nt_route() decides which kernel runs a problem and with which template arguments; uvc_gemm_nt() is nt_route() and one switch
-// over the family.  The launchers below compute grid and LDS bytes and decide nothing.  DESIGN.md ("GEMM routing") has the table
+// over the family.  The launchers (below, and uvc_gemm::launch_* next to the kernels that have a file of their own) compute grid and LDS bytes and decide nothing.  DESIGN.md ("GEMM routing") has the table
 // family -> kernel -> rule -> where measured; NOTEBOOK.md ("gemm.hip dispatcher comments") the history of each rule.
 namespace {
 
@@ -2674,84 +1961,6 @@ int nt_route(const uvc_gemm_nt_args& p, uvc_gemm_route* r) {
   return UVC_OK;
 }
 
-// ---- launchers: grid, LDS bytes, launch.  NT_LAUNCH(epi, cases): the launch of the case that is `epi` (nt_route has checked that the family takes it)
-#define NT_LAUNCH(epi, ...) \
-  switch (epi) { __VA_ARGS__ default: return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: epilogue not built for the routed kernel"); } \
-  UVC_CHECK_LAUNCH(); \
-  return UVC_OK;
-#define NT_EPI9(X) X(UVC_EPI_NONE) X(UVC_EPI_BIAS) X(UVC_EPI_BIAS_GELU) X(UVC_EPI_BIAS_RESID) X(UVC_EPI_BIAS_RESID_GATE) X(UVC_EPI_DGELU) X(UVC_EPI_BIAS_GELU_OUT) \
-                   X(UVC_EPI_BIAS_GELU_GRAD) X(UVC_EPI_MUL_AUX)
-
-template <typename TA, typename T, typename TC>
-int launch_nt_epi(const NtArgs& a, int epi, hipStream_t st) {
-  const int grid = ceil_div(ceil_div(a.M, NT_BM), 8) * 8 * ceil_div(a.N, NT_BN);   // M tiles padded to the 8 XCDs
-#define NT_CASE(E) case E: k_gemm_nt<TA, T, TC, E><<<grid, 256, 0, st>>>(a); break;
-  NT_LAUNCH(epi, NT_EPI9(NT_CASE))
-#undef NT_CASE
-}
-
-template <typename TA, typename TC>
-int launch_nt_rows(const NtArgs& a, int epi, hipStream_t st) {
-  const int grid = ceil_div(a.M, RP_BM) * ceil_div(a.N, RP_BN);
-#define RP_CASE(E) case E: k_gemm_nt_rows<TA, TC, E><<<grid, 256, 0, st>>>(a); break;
-  NT_LAUNCH(epi, RP_CASE(UVC_EPI_NONE) RP_CASE(UVC_EPI_BIAS) RP_CASE(UVC_EPI_BIAS_RESID) RP_CASE(UVC_EPI_BIAS_RESID_GATE) RP_CASE(UVC_EPI_BIAS_GELU_GRAD) RP_CASE(UVC_EPI_MUL_AUX))
-#undef RP_CASE
-}
-
-// k_gemm_ws: `wgs` workgroups in all (512 at K = 192 / 128: ~2 per CU -- 1024 / 2048 cost +0.10 / +0.15 ms in the step, profiles/r6o_ab_ws_slots_not_kept.txt;
-// 256 at K = 384: one per CU), slots a multiple of the 8 XCDs
-int ws_slots(const NtArgs& a, int ngroups, int wgs) {
-  const int ntiles = ceil_div(a.M, WS_BM);
-  int nslots = (wgs / ngroups) & ~7;
-  if (nslots < 8) nslots = 8;
-  if (nslots > ((ntiles + 7) & ~7)) nslots = (ntiles + 7) & ~7;
-  return nslots;
-}
-template <typename TA, typename TC, int KT, int WS_NW>
-int launch_ws_epi(const NtArgs& a, int epi, hipStream_t st) {
-  const int ngroups = ceil_div(a.N, 64 * WS_NW), nslots = ws_slots(a, ngroups, 512);
-  const int grid = nslots * ngroups;
-  if (epi == UVC_EPI_BIAS_GELU_GRAD_Q8) {                  // (bf16 operands and outputs, K = 192, four waves x 64 columns: nt_route checked)
-    if constexpr (sizeof(TA) == 2 && sizeof(TC) == 2 && KT == 6 && WS_NW == 4) {
-      k_gemm_ws<TA, TC, UVC_EPI_BIAS_GELU_GRAD_Q8, KT, WS_NW><<<grid, 64 * WS_NW, 0, st>>>(a, ngroups, nslots);
-      UVC_CHECK_LAUNCH();
-      return UVC_OK;
-    } else return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_gemm_nt: UVC_EPI_BIAS_GELU_GRAD_Q8 outside uvc_gemm_nt_q8_supported");
-  }
-#define WS_CASE(E) case E: k_gemm_ws<TA, TC, E, KT, WS_NW><<<grid, 64 * WS_NW, 0, st>>>(a, ngroups, nslots); break;
-  NT_LAUNCH(epi, NT_EPI9(WS_CASE))
-#undef WS_CASE
-}
-template <typename TA, typename TC, int KT>
-int launch_ws_narrow(const NtArgs& a, int epi, hipStream_t st) {      // 8 waves x 32 columns
-  const int ngroups = ceil_div(a.N, 256), nslots = ws_slots(a, ngroups, 512);
-  const int grid = nslots * ngroups;
-#define WS_CASE(E) case E: k_gemm_ws<TA, TC, E, KT, 8, 2><<<grid, 512, 0, st>>>(a, ngroups, nslots); break;
-  NT_LAUNCH(epi, WS_CASE(UVC_EPI_DGELU) WS_CASE(UVC_EPI_MUL_AUX) WS_CASE(UVC_EPI_MUL_AUX_Q8) WS_CASE(UVC_EPI_BIAS_GELU_GRAD_Q8))
-#undef WS_CASE
-}
-template <typename TA, typename TC>
-int launch_ws(const uvc_gemm_route& r, const NtArgs& a, hipStream_t st) {
-  if constexpr (sizeof(TC) == 2 && sizeof(TA) == 2) {
-    if (r.nw == 8) return launch_ws_narrow<TA, TC, 6>(a, r.epilogue, st);
-  }
-  if (r.kt == 6) return r.nw == 4 ? launch_ws_epi<TA, TC, 6, 4>(a, r.epilogue, st) : launch_ws_epi<TA, TC, 6, 3>(a, r.epilogue, st);
-  return r.nw == 4 ? launch_ws_epi<TA, TC, 4, 4>(a, r.epilogue, st) : launch_ws_epi<TA, TC, 4, 3>(a, r.epilogue, st);
-}
-template <typename TC, int NW = 6>
-int launch_ws384(const NtArgs& a, int epi, hipStream_t st) {
-  constexpr int KT = 12, NJ = 2;
-  const int ngroups = ceil_div(a.N, 32 * NW), nslots = ws_slots(a, ngroups, 256);     // (a last group with idle waves: N = 1152 on eight waves is 4.5 groups)
-  const int grid = nslots * ngroups;
-  const int sh = 2 * WS_BM * (KT * 64 + 32) + NW * 16 * (16 * NJ + 4) * 4;
-#define WS_CASE(E) case E: { \
-    UVC_MAX_LDS(sh, k_gemm_ws<bf16_t, TC, E, KT, NW, NJ>); \
-    k_gemm_ws<bf16_t, TC, E, KT, NW, NJ><<<grid, 64 * NW, sh, st>>>(a, ngroups, nslots); } break;
-  NT_LAUNCH(epi, WS_CASE(UVC_EPI_NONE) WS_CASE(UVC_EPI_BIAS) WS_CASE(UVC_EPI_BIAS_GELU) WS_CASE(UVC_EPI_BIAS_RESID) WS_CASE(UVC_EPI_BIAS_RESID_GATE)
-                      WS_CASE(UVC_EPI_BIAS_GELU_OUT) WS_CASE(UVC_EPI_BIAS_GELU_GRAD) WS_CASE(UVC_EPI_MUL_AUX))
-#undef WS_CASE
-}
-
 // k_gemm_wsn (ROWS = 32: plain and bias epilogues) and k_gemm_wsn16 (ROWS = 16): one persistent workgroup per CU
 template <typename TC, int KT, int ROWS>
 int launch_wsn_rows(const NtArgs& a, int epi, hipStream_t st) {
@@ -2872,9 +2081,6 @@ extern "C" int uvc_gemm_nt_route(const uvc_gemm_nt_args* p, uvc_gemm_route* r) {
   return nt_route(*p, r);
 }
 
-#define NT_BY_TC(F, ...) (r.c_f32 ? F<float>(__VA_ARGS__) : F<bf16_t>(__VA_ARGS__))
-#define NT_BY_TA_TC(F, ...) (r.a_f32 ? (r.c_f32 ? F<float, float>(__VA_ARGS__) : F<float, bf16_t>(__VA_ARGS__)) \
-                                     : (r.c_f32 ? F<bf16_t, float>(__VA_ARGS__) : F<bf16_t, bf16_t>(__VA_ARGS__)))
 extern "C" int uvc_gemm_nt(const uvc_gemm_nt_args* p, void* stream) {
   uvc_gemm_route r;
   if (const int rc = uvc_gemm_nt_route(p, &r)) return rc;
@@ -2882,13 +2088,10 @@ extern "C" int uvc_gemm_nt(const uvc_gemm_nt_args* p, void* stream) {
   const int e = r.epilogue;
   hipStream_t st = (hipStream_t)stream;
   switch (r.family) {
-    case UVC_ROUTE_NT:
-      if (r.t_f32) return launch_nt_epi<float, float, float>(a, e, st);
-      if (r.a_f32) return r.c_f32 ? launch_nt_epi<float, bf16_t, float>(a, e, st) : launch_nt_epi<float, bf16_t, bf16_t>(a, e, st);
-      return r.c_f32 ? launch_nt_epi<bf16_t, bf16_t, float>(a, e, st) : launch_nt_epi<bf16_t, bf16_t, bf16_t>(a, e, st);
-    case UVC_ROUTE_NT_ROWS: return NT_BY_TA_TC(launch_nt_rows, a, e, st);
-    case UVC_ROUTE_WS: return NT_BY_TA_TC(launch_ws, r, a, st);
-    case UVC_ROUTE_WS384: return r.nw == 8 ? launch_ws384<bf16_t, 8>(a, e, st) : NT_BY_TC(launch_ws384, a, e, st);
+    case UVC_ROUTE_NT: return uvc_gemm::launch_nt(r, a, st);
+    case UVC_ROUTE_NT_ROWS: return uvc_gemm::launch_nt_rows(r, a, st);
+    case UVC_ROUTE_WS: return uvc_gemm::launch_ws(r, a, st);
+    case UVC_ROUTE_WS384: return uvc_gemm::launch_ws384(r, a, st);
     case UVC_ROUTE_WSN:
     case UVC_ROUTE_WSN16: return NT_BY_TC(launch_wsn, r, a, st);
     case UVC_ROUTE_WSN16_DMA: return r.c_f32 ? launch_ring<false>(r, a, st) : launch_ring<true>(r, a, st);
@@ -2898,10 +2101,6 @@ extern "C" int uvc_gemm_nt(const uvc_gemm_nt_args* p, void* stream) {
     default: return uvc_set_error_msg(UVC_ERR_ARG, "uvc_gemm_nt: route");
   }
 }
-#undef NT_BY_TA_TC
-#undef NT_BY_TC
-#undef NT_EPI9
-#undef NT_LAUNCH
 
 
 // ================================================================================================
@@ -3190,7 +2389,6 @@ __global__ __launch_bounds__(512, 2) void k_gemm_tn_big(TnArgs g) {
 // (r5: a ring of FIVE stages, 151 KB: dW2 on 128 workgroups 84 us against 78 -- at 19.6 GB/s per CU the kernel is not waiting for a deeper ring; profiles/r5zz)
 constexpr int TD_BM = 32, TD_NST = 4;
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // Transposing fragment read issued as inline assembly: for a compiler-visible LDS load hipcc inserts s_waitcnt vmcnt(0) (any
 // outstanding LDS-DMA may alias it), which would drain the whole ring before every step.  Same k-slot map as TrFrag<bf16_t>.
 __device__ __forceinline__ s16x4 ds_tr16_asm(const char* p) {
@@ -3328,9 +2526,9 @@ __global__ __launch_bounds__(512, 2) void k_gemm_tn_dma(TnArgs g) {
   for (int t = 0; t < TD_NST - 1 && t < nfull; ++t) issue(t);
   for (int t = 0; t < nfull; ++t) {
     const int younger = min(TD_NST - 2, nfull - 1 - t);      // stages issued after t that may stay in flight
-    if (younger >= 2) wait_vmcnt<2 * PER>();
-    else if (younger == 1) wait_vmcnt<PER>();
-    else wait_vmcnt<0>();
+    if (younger >= 2) wait_vm<2 * PER>();
+    else if (younger == 1) wait_vm<PER>();
+    else wait_vm<0>();
     __builtin_amdgcn_s_barrier();                            // stage t complete for every wave; image (t-1) % 4 is free again
     compute(smem_td + (t % TD_NST) * IMG, t + TD_NST - 1 < nfull ? t + TD_NST - 1 : -1);
   }
