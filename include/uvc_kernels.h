@@ -210,6 +210,27 @@ typedef struct uvc_attn_rollout_args {
 /* r_out[b,j] = keep * r_in[b,j] + (mix / H) * sum_h sum_i r_in[b,i] * exp(scale * q[b,h,i].k[b,h,j] - lse[b,h,i]) */
 int uvc_attention_rollout_step(const uvc_attn_rollout_args* a, void* stream);
 
+/* One step of the gradient-weighted rollout (Chefer, Gur & Wolf, ICCV 2021, self-attention rule) seen from the readout token(s): the row vector
+ * pushed back through (P . dP)^+ of one attention block, head mean, with dP = dO V^T the gradient of the explained logit with respect to the
+ * softmax matrix.  P is recomputed from q, k and the forward's lse as in uvc_attention_rollout_step, dP per 16 x 16 tile from the streamed dO rows
+ * and the keys' V rows (the second MFMA of the dK/dV kernel at a value width); the ReLU is per head and per entry, before the head mean; no
+ * [N, N] matrix exists anywhere.  Limits as uvc_attention_rollout_step: 1 <= N <= 1026 (UVC_ERR_UNSUPPORTED beyond), head_dim 64 (otherwise
+ * UVC_ERR_UNSUPPORTED), v_dim 16 / 32 / 48 / 64, UVC_F32 or UVC_BF16 operands; r, p, dP and the sums are float32.  No atomics: every r_out element
+ * has one writer, the result is bit-identical on a repeat and independent of the batch an image sits in.  Null pointers, overlapping r_in /
+ * r_out, a bad dtype or v_dim, an empty problem, qkv or dout not 16-byte aligned: UVC_ERR_ARG, and nothing is launched. */
+typedef struct uvc_attn_relevance_args {
+  const void* qkv;      /* T [B, N, H*(128 + v_dim)], rows [q H*64 | k H*64 | v H*v_dim] (the compact layout; v IS read) */
+  const float* lse;     /* [B, H, N], as uvc_attention_fwd wrote it (natural log) */
+  const void* dout;     /* T [B, N, H*v_dim]: the gradient at the attention output, before attn.proj */
+  const float* r_in;    /* [B, N] */
+  float* r_out;         /* [B, N], must not overlap r_in */
+  int32_t B, N, H, head_dim, v_dim, dtype;
+  float scale, keep, mix;
+} uvc_attn_relevance_args;
+/* r_out[b,j] = keep * r_in[b,j] + (mix / H) * sum_h sum_i r_in[b,i] * max(0, P_h[i,j] * (dout[b,i,h,:] . v[b,h,j,:])),
+ * P_h[i,j] = exp(scale * q[b,h,i].k[b,h,j] - lse[b,h,i]) */
+int uvc_attention_relevance_step(const uvc_attn_relevance_args* a, void* stream);
+
 /* The qkv Linear and the attention forward of a block as ONE kernel (UVC/models/model_distilled.py:175-185: `self.qkv(x)` ... `attn @ v`):
  * h [B*N, D] (the LayerNorm-1 rows) and the qkv weight [3D, D] in, o [B,N,H*64] and lse out; qkv [B,N,3,H,64] is written only when the
  * pointer is given (the backward needs it; a no-grad forward does not).  Same bits as uvc_gemm_nt (UVC_EPI_BIAS) + uvc_attention_fwd.

@@ -217,6 +217,26 @@ int uvc_vit_compact_train_forward(const uvc_vit_cfg* cfg, const uvc_compact_bloc
  * proj.bias, one without units to fc2.bias.  The mode-1 token mask (io->patch_mask) is a constant: patch_gating gets no gradient. */
 int uvc_vit_compact_backward(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* stream);
 
+/* Class-specific relevance maps: the gradient-weighted attention rollout of Chefer, Gur & Wolf (ICCV 2021, "Generic Attention-Model
+ * Explainability", self-attention rule) for the eval logit y of one class per image -- head(cls)[t], or (head(cls)[t] + head_dist(dist)[t]) / 2
+ * with the distillation token.  Per block with heads A = (1/H) sum_h (P_h . dy/dP_h)^+, R <- R + A R from R = I; `relevance` (device float32
+ * [B, N] over the model's tokens) is the readout row of the result (class token, or the mean of the class and distillation rows), computed as
+ * that row vector pushed back from the last block to the first, r <- r + r A.  It is non-negative, NOT normalised (every row sums to >= 1, every
+ * readout entry is >= 1 / ntok); a block without heads is the identity.
+ * One stream: uvc_vit_compact_train_forward's walk (logits / logits_dist are the eval forward's bits), a small kernel that picks the target and
+ * writes the one-hot logit gradient, then uvc_vit_compact_backward's walk without any weight-gradient GEMM, column sum or LayerNorm parameter
+ * reduction, with one uvc_attention_relevance_step (uvc_kernels.h; keep = mix = 1) per block with heads right behind the attn.proj dgrad; the
+ * walk ends behind the step of the lowest block with heads.  The gradient is the full one: the paths through later blocks' q and k included.
+ * io: params, the TRAINING shadow (uvc_vit_compact_train_update_shadows: the dgrads read the transposed copies), workspace (of
+ * uvc_vit_compact_attribution_workspace_bytes), x, logits, logits_dist, patch_mask, patches_in, batch; accumulate must be 0; grads is not read.
+ * target: device [B] class indices, or NULL for the first maximum of the eval logits over [0, num_labels) (ties: the lowest index).  A given
+ * index outside [0, num_labels) is clamped into it by the kernel -- callers check it on the host (uvc_amd/compact_attribution.py refuses it).
+ * 1 <= num_labels <= num_classes, otherwise UVC_ERR_ARG.  target_out: optional device [B], the class explained.
+ * Sequences above 256 tokens: UVC_ERR_UNSUPPORTED and -1 from the workspace query, as every compact training entry point.  Deterministic. */
+int64_t uvc_vit_compact_attribution_workspace_bytes(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int32_t batch);
+int uvc_vit_compact_attribution(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, const int32_t* target,
+                                int32_t num_labels, float* relevance, int32_t* target_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,11 @@ class uvc_attn_rollout_args(C.Structure):
                [(n, C.c_int32) for n in ("B", "N", "H", "head_dim", "v_dim", "dtype")] + [(n, C.c_float) for n in ("scale", "keep", "mix")]
 
 
+class uvc_attn_relevance_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("qkv", "lse", "dout", "r_in", "r_out")] + \
+               [(n, C.c_int32) for n in ("B", "N", "H", "head_dim", "v_dim", "dtype")] + [(n, C.c_float) for n in ("scale", "keep", "mix")]
+
+
 class uvc_compact_block(C.Structure):          # include/uvc_vit.h
     _fields_ = [(n, C.c_int32) for n in ("heads", "v_dim", "hidden", "reserved")]
 
@@ -203,6 +208,7 @@ _SIGNATURES = {
     "uvc_attention_bwd": [C.POINTER(uvc_attn_args), VP],
     "uvc_attention_bwd_vdim": [C.POINTER(uvc_attn_args), VP],
     "uvc_attention_rollout_step": [C.POINTER(uvc_attn_rollout_args), VP],
+    "uvc_attention_relevance_step": [C.POINTER(uvc_attn_relevance_args), VP],
     "uvc_qkv_attention_supported": [I32, I32, I32, I32, I32],
     "uvc_qkv_attention_fwd": [C.POINTER(uvc_qkv_attn_args), VP],
     "uvc_attention_tok_fwd": [C.POINTER(uvc_attn_tok_args), VP],
@@ -272,7 +278,8 @@ VIT_SYMBOLS = ["uvc_vit_layout", "uvc_vit_workspace_bytes", "uvc_vit_ws_offsets"
                "uvc_vit_compact_forward",   # (the compact-model entry points: bound in uvc_amd/compact.py)
                "uvc_vit_compact_train_layout", "uvc_vit_compact_train_workspace_bytes", "uvc_vit_compact_train_update_shadows",
                "uvc_vit_compact_frozen_ranges", "uvc_vit_compact_train_forward", "uvc_vit_compact_backward",   # (uvc_amd/compact_train.py)
-               "uvc_vit_compact_rollout_workspace_bytes", "uvc_vit_compact_rollout"]   # (attention rollout maps: uvc_amd/compact.py)
+               "uvc_vit_compact_rollout_workspace_bytes", "uvc_vit_compact_rollout",   # (attention rollout maps: uvc_amd/compact.py)
+               "uvc_vit_compact_attribution_workspace_bytes", "uvc_vit_compact_attribution"]   # (uvc_amd/compact_attribution.py)
 
 
 def side_stream(device, priority_class=None):

@@ -18,13 +18,15 @@ zero ``b1`` and zero fc2 columns (GELU(0) = 0 meets a zero column).
     python -m uvc_amd.compact finetune --compact model.compact.pt --output tuned.compact.pt [Stage 2's flags]
     python -m uvc_amd.compact predict --compact model.compact.pt --images PATH [PATH ...] [--output preds.jsonl]
     python -m uvc_amd.compact explain --compact model.compact.pt --images PATH [PATH ...] [--output maps.jsonl] [--overlay_dir DIR]
+    python -m uvc_amd.compact attribute --compact model.compact.pt --images PATH [PATH ...] [--target INT] [--output maps.jsonl] [--overlay_dir DIR]
 
 ``reference_forward`` is the written spec of the format (plain PyTorch, CPU or GPU, any dtype); ``CompactVisionTransformer``
 runs it through ``uvc_vit_compact_forward`` (include/uvc_vit.h).  ``predict`` classifies image files with it (file -> eval transform -> patch rows -> compact forward -> softmax + top-k, all of it
 behind the decode on the device).  ``reference_logits`` is the same network with the two heads kept
 apart: the function ``compact_train.CompactTrainer`` fine-tunes (a fine-tuned file is an ordinary version-1 compact file).
 ``explain`` adds to ``predict``'s records what the model looked at: the attention rollout of the readout token(s) over the patches
-(``uvc_vit_compact_rollout``; ``reference_rollout`` is its written spec).
+(``uvc_vit_compact_rollout``; ``reference_rollout`` is its written spec).  ``attribute`` maps the patches that speak for ONE label, the
+gradient-weighted rollout (``uvc_vit_compact_attribution`` through ``compact_attribution.CompactAttributionViT``; ``reference_attribution``).
 """
 from __future__ import annotations
 
@@ -191,6 +193,7 @@ def reference_logits(export: dict, x: torch.Tensor):
 
 
 METHODS = ("rollout", "last")
+GRAD_METHODS = ("attribution",)                     # class-specific maps: they need a backward (compact_attribution.CompactAttributionViT)
 
 
 def reference_rollout(export: dict, x: torch.Tensor, method: str = "rollout") -> torch.Tensor:
@@ -216,9 +219,49 @@ def reference_rollout(export: dict, x: torch.Tensor, method: str = "rollout") ->
     return r
 
 
-def _reference_walk(export: dict, x: torch.Tensor, keep_attention: bool = False):
-    """The block loop behind ``reference_logits`` and ``reference_rollout``: ``(logits, logits_dist, atts)``; with ``keep_attention``
-    ``atts`` lists the head-mean softmax ``[B, N, N]`` of every block that has heads, in block order (else it is empty)."""
+def reference_attribution(export: dict, x: torch.Tensor, target=None, num_labels=None):
+    """Class-specific relevance maps of a compact model in plain PyTorch -- the gradient-weighted attention rollout of Chefer, Gur & Wolf
+    (ICCV 2021, "Generic Attention-Model Explainability", self-attention rule): ``(relevance float64 [B, N], target int64 [B])``.
+    y is the eval logit of class t (``head(cls)[t]``, or the mean of the two heads with the distillation token), the network and its block
+    loop are ``reference_logits``' (in x's dtype) with every kept head's softmax matrix A_l^h in the autograd graph.  Per block with heads
+    ``Abar_l = mean_h (A_l^h * dy/dA_l^h)^+`` -- the full gradient, nothing detached; the ReLU per head and entry, before the head mean --
+    and the readout row of ``R_L``, ``R_l = R_{l-1} + Abar_l R_{l-1}`` from ``R_0 = I``, is the row vector ``r <- r + r Abar_l`` pushed
+    back from the last block to the first, in float64, from the uniform vector over the readout tokens (as ``reference_rollout``).  A block
+    without heads is the identity.  The map is non-negative and NOT normalised: every row sums to at least 1, every readout entry is at
+    least 1 / ntok.  ``target``: an int, or B indices (sequence or tensor); None: the argmax of the eval logits over the first
+    ``num_labels`` columns (default num_classes), ties to the lowest index."""
+    cfg = check_export(export)["cfg"]
+    nl = cfg["num_classes"] if num_labels is None else int(num_labels)
+    if not 1 <= nl <= cfg["num_classes"]:
+        raise ValueError(f"num_labels {nl} must lie in [1, {cfg['num_classes']}] (the model's head)")
+    B = x.shape[0]
+    with torch.enable_grad():
+        xg = x.detach().clone().requires_grad_(True)              # a leaf above every softmax matrix: they all join the graph
+        o, od, atts = _reference_walk(export, xg, keep_heads=True)
+        logits = (o + od) / 2 if cfg["enable_dist"] else o
+        if target is None:
+            z = logits.detach()[:, :nl]
+            cols = torch.arange(nl, device=z.device).expand(B, nl)
+            t = torch.where(z == z.max(dim=1, keepdim=True).values, cols, torch.full_like(cols, nl)).min(dim=1).values
+        else:
+            t = torch.as_tensor(target, dtype=torch.int64, device=x.device).reshape(-1)
+            t = t.expand(B) if t.numel() == 1 else t
+            if t.numel() != B or int(t.min()) < 0 or int(t.max()) >= nl:
+                raise ValueError(f"target must be {B} indices in [0, {nl}), not {t.tolist()}")
+        grads = torch.autograd.grad(logits.gather(1, t[:, None]).sum(), atts) if atts else ()
+    ntok = 2 if cfg["enable_dist"] else 1
+    r = torch.zeros(B, _seq(cfg), dtype=torch.float64, device=x.device)
+    r[:, :ntok] = 1.0 / ntok
+    for a, g in zip(reversed(atts), reversed(grads)):
+        abar = (a.detach().double() * g.double()).clamp_min(0).mean(dim=1)
+        r = r + torch.einsum("bi,bij->bj", r, abar)
+    return r, t.clone()
+
+
+def _reference_walk(export: dict, x: torch.Tensor, keep_attention: bool = False, keep_heads: bool = False):
+    """The block loop behind ``reference_logits``, ``reference_rollout`` and ``reference_attribution``: ``(logits, logits_dist, atts)``;
+    with ``keep_attention`` ``atts`` lists the head-mean softmax ``[B, N, N]`` of every block that has heads, in block order, with
+    ``keep_heads`` the per-head softmax ``[B, H_l, N, N]`` itself, the very tensor the block goes on with (else it is empty)."""
     check_export(export)
     cfg = export["cfg"]
     P = {k: v.to(device=x.device, dtype=x.dtype) for k, v in export["state_dict"].items()}
@@ -246,7 +289,9 @@ def _reference_walk(export: dict, x: torch.Tensor, keep_attention: bool = False)
             kk = qkv[..., nh * 64:2 * nh * 64].reshape(B, N, nh, 64).transpose(1, 2)
             v = qkv[..., 2 * nh * 64:].reshape(B, N, nh, dv).transpose(1, 2)
             att = ((q @ kk.transpose(-2, -1)) * HEAD_DIM ** -0.5).softmax(dim=-1)
-            if keep_attention:
+            if keep_heads:
+                atts.append(att)
+            elif keep_attention:
                 atts.append(att.mean(dim=1))
             o = (att @ v).transpose(1, 2).reshape(B, N, nh * dv)
             h = h + F.linear(o, P[p + "attn.proj.weight"], P[p + "attn.proj.bias"])
@@ -353,7 +398,7 @@ _SLOTS = ["norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "att
 
 
 def _bind():
-    """The library with the argument types of the twelve compact entry points (include/uvc_vit.h, uvc_vit_compact_*) set."""
+    """The library with the argument types of the fourteen compact entry points (include/uvc_vit.h, uvc_vit_compact_*) set."""
     from . import _lib as L
     from .model_distilled import uvc_vit_cfg, uvc_vit_io, uvc_vit_offsets, uvc_vit_shadow_offsets
     lib = L.lib()
@@ -363,10 +408,11 @@ def _bind():
         tails = {"layout": [C.POINTER(uvc_vit_offsets), C.POINTER(uvc_vit_shadow_offsets)], "workspace_bytes": [C.c_int32],
                  "update_shadows": [C.c_void_p, C.c_void_p, C.c_void_p], "forward": run, "train_forward": run, "backward": run,
                  "frozen_ranges": [C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)],
-                 "rollout": [C.POINTER(uvc_vit_io), C.c_void_p, C.c_int32, C.c_void_p]}
+                 "rollout": [C.POINTER(uvc_vit_io), C.c_void_p, C.c_int32, C.c_void_p],
+                 "attribution": [C.POINTER(uvc_vit_io), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]}
         for n in ("layout", "workspace_bytes", "update_shadows"):
             tails["train_" + n] = tails[n]
-        tails["rollout_workspace_bytes"] = tails["workspace_bytes"]
+        tails["rollout_workspace_bytes"] = tails["attribution_workspace_bytes"] = tails["workspace_bytes"]
         for n, tail in tails.items():
             f = getattr(lib, "uvc_vit_compact_" + n)
             f.argtypes, f.restype = head + tail, C.c_int64 if n.endswith("workspace_bytes") else C.c_int
@@ -461,14 +507,14 @@ class _CompactModule(nn.Module):
         return patches.shape[0] // npatch
 
     def _workspace(self, B, training):
-        """One workspace per mode (eval, training, or "rollout": the eval forward that keeps qkv and lse per block), for the last
-        batch size seen."""
-        mode = training if training == "rollout" else bool(training)
+        """One workspace per mode (eval, training, "rollout": the eval forward that keeps qkv and lse per block, or "attribution": the
+        training set plus what the relevance walk adds), for the last batch size seen."""
+        mode = training if isinstance(training, str) else bool(training)
         key = (B, mode)
         if key not in self._ws:
             from . import _lib as L
             entry = {False: "uvc_vit_compact_workspace_bytes", True: "uvc_vit_compact_train_workspace_bytes",
-                     "rollout": "uvc_vit_compact_rollout_workspace_bytes"}[mode]
+                     "rollout": "uvc_vit_compact_rollout_workspace_bytes", "attribution": "uvc_vit_compact_attribution_workspace_bytes"}[mode]
             n = self._lib_call(entry, B)
             if n < 0:
                 L.check(-1, entry)
@@ -593,9 +639,12 @@ def topk_reference(logits, k, n_valid=None):
     return np.take_along_axis(p, index, axis=1), index.astype(np.int32)
 
 
-def _classify(model, files, method, overlay_dir, topk, batch_size, preset, interpolation, crop_pct, num_labels, classes, num_workers, fused_input):
+def _classify(model, files, method, overlay_dir, topk, batch_size, preset, interpolation, crop_pct, num_labels, classes, num_workers, fused_input,
+              target=None):
     """The generator behind ``predict`` (``method`` None) and ``explain``: the checked arguments, the tolerant dataset over ``files``,
-    the preset's eval loader, the forward (with the rollout maps when a method is given), top-k, one record per file."""
+    the preset's eval loader, the forward (with the rollout maps when a method is given), top-k, one record per file.  ``method``
+    "attribution": image batches, ``model.attribution`` for ``target`` (None: every image's top-1 label among ``num_labels``), the
+    relevance row divided by its sum (at least 1), and ``"target"`` in the record."""
     from . import data, ops
     if preset not in PRESETS:
         raise ValueError(f"preset must be one of {PRESETS}, not {preset!r}")
@@ -610,6 +659,10 @@ def _classify(model, files, method, overlay_dir, topk, batch_size, preset, inter
         raise ValueError(f"{len(classes)} class names for {num_labels} labels")
     if not 1 <= topk <= min(MAX_TOPK, num_labels):
         raise ValueError(f"topk {topk} must lie in [1, {min(MAX_TOPK, num_labels)}]")
+    grad = method in GRAD_METHODS
+    if target is not None and not 0 <= int(target) < num_labels:
+        raise ValueError(f"target {target} must lie in [0, {num_labels}) (num_labels)")
+    fused_input = bool(fused_input) and not grad              # the backward's forward rearranges the images itself
     ds = files if hasattr(files, "load") else data.FileListDataset(files, tolerant=True)
     names = ds.paths if hasattr(ds, "paths") else list(range(len(ds)))
     errors = getattr(ds, "errors", {})
@@ -626,13 +679,15 @@ def _classify(model, files, method, overlay_dir, topk, batch_size, preset, inter
         import os
         os.makedirs(overlay_dir, exist_ok=True)
 
-    def records(first, probs, index, maps):
+    def records(first, probs, index, maps, chosen=None):
         for b, (pr, ix) in enumerate(zip(probs.tolist(), index.tolist())):
             i = first + b
             if i in errors:
                 yield dict(file=names[i], error=errors[i])
                 continue
             rec = dict(file=names[i], top=[dict(index=j, label=None if classes is None else classes[j], prob=q) for j, q in zip(ix, pr)])
+            if chosen is not None:
+                rec.update(target=int(chosen[b]))
             if maps is not None:
                 row = maps[b].tolist()
                 rec.update(grid=[g, g], tokens=row[:ntok], map=row[ntok:])
@@ -646,14 +701,19 @@ def _classify(model, files, method, overlay_dir, topk, batch_size, preset, inter
     with torch.cuda.device(dev):
         for x, _ in loader:
             inp = dict(patches=x) if fused_input else dict(x=x)
-            logits, maps = (model._eval_logits(**inp), None) if method is None else model.rollout(method=method, **inp)
+            chosen = None
+            if grad:
+                logits, maps, chosen = model.attribution(x, None if target is None else int(target), num_labels)
+                maps = maps / maps.sum(dim=1, keepdim=True)
+            else:
+                logits, maps = (model._eval_logits(**inp), None) if method is None else model.rollout(method=method, **inp)
             probs, index = ops.logits_topk(logits, topk, num_labels)
             if pending is not None:
-                yield from records(pending[0], pending[1].cpu(), pending[2].cpu(), host(pending[3]))
-            pending = (first, probs, index, maps)
+                yield from records(pending[0], pending[1].cpu(), pending[2].cpu(), host(pending[3]), host(pending[4]))
+            pending = (first, probs, index, maps, chosen)
             first += len(probs)
         if pending is not None:
-            yield from records(pending[0], pending[1].cpu(), pending[2].cpu(), host(pending[3]))
+            yield from records(pending[0], pending[1].cpu(), pending[2].cpu(), host(pending[3]), host(pending[4]))
 
 
 def write_overlay(overlay_dir, index, name, pixels, patch_map, img_size, preset="imagenet", interpolation="bilinear", crop_pct=None):
@@ -701,16 +761,27 @@ def predict(model, files, *, topk=5, batch_size=64, preset="imagenet", interpola
 
 
 def explain(model, files, *, method="rollout", overlay_dir=None, topk=5, batch_size=64, preset="imagenet", interpolation="bilinear", crop_pct=None,
-            num_labels=None, classes=None, num_workers=8, fused_input=bool(FUSED_INPUT_DEFAULT)):
+            num_labels=None, classes=None, num_workers=8, fused_input=bool(FUSED_INPUT_DEFAULT), target=None):
     """``predict``'s records plus what the model looked at: ``"grid": [g, g]`` (patches per side), ``"tokens"``: the map's mass on the
     readout token(s) ``[r_cls(, r_dist)]``, ``"map"``: g * g floats, row-major, the mass on every patch -- ``CompactVisionTransformer.rollout``
     with ``method`` "rollout" or "last"; tokens and map sum to 1.  A file that cannot be read stays ``{"file", "error"}``.
     ``overlay_dir``: one PNG per readable image (``write_overlay``), named ``<running index>_<basename>.png``.  The other keywords are
-    ``predict``'s."""
-    if method not in METHODS:
-        raise ValueError(f"method must be one of {METHODS}, not {method!r}")
+    ``predict``'s.
+
+    ``method="attribution"`` (``GRAD_METHODS``): class-specific maps, which patches speak for ONE label -- ``model`` must be a
+    ``compact_attribution.CompactAttributionViT`` (``TypeError`` otherwise); ``target``: the class explained for every image, or None for
+    each image's own top-1 label among ``num_labels``.  The record gains ``"target"``; ``"tokens"`` and ``"map"`` are the relevance row
+    (``reference_attribution``) divided by its sum, so they still sum to 1.  The loader yields image batches: ``fused_input`` is ignored."""
+    if method not in METHODS + GRAD_METHODS:
+        raise ValueError(f"method must be one of {METHODS + GRAD_METHODS}, not {method!r}")
+    if method in GRAD_METHODS:
+        from .compact_attribution import CompactAttributionViT
+        if not isinstance(model, CompactAttributionViT):
+            raise TypeError(f"method {method!r} needs a CompactAttributionViT, not {type(model).__name__}")
+    elif target is not None:
+        raise ValueError(f"target goes with method 'attribution': the {method!r} map is the same for every class")
     yield from _classify(model, files, method, overlay_dir, topk, batch_size, preset, interpolation, crop_pct, num_labels, classes, num_workers,
-                         fused_input)
+                         fused_input, target)
 
 
 def _int_in(lo, hi, what):
@@ -732,22 +803,30 @@ def _crop_pct_arg(v):
 
 
 def predict_command(args, dev):
-    """``predict`` and ``explain``: one JSON line per image to --output (or stdout), then the summary line
-    ``{"images", "errors", "batches", "img_per_s"}``."""
+    """``predict``, ``explain`` and ``attribute``: one JSON line per image to --output (or stdout), then the summary line
+    ``{"images", "errors", "batches", "img_per_s"}``.  ``attribute`` is ``explain`` with method "attribution" on a ``CompactAttributionViT``:
+    a file with more than 256 tokens fails here, before any image is listed or read."""
     import sys
     import time
     from . import data
     export = load_compact(args.compact)
     classes = read_classes(args.classes) if args.classes else None
+    if args.cmd == "attribute":                     # (its refusal of a long sequence comes first)
+        from .compact_attribution import CompactAttributionViT
+        cm = CompactAttributionViT(export, precision=args.precision, device=dev)
     files = data.list_images(args.images)
-    cm = CompactVisionTransformer(export, precision=args.precision, device=dev)
+    if args.cmd != "attribute":
+        cm = CompactVisionTransformer(export, precision=args.precision, device=dev)
     out = open(args.output, "w", encoding="utf-8") if args.output else sys.stdout
     n = nerr = 0
     t0 = time.perf_counter()
     try:
         kw = dict(topk=args.topk, batch_size=args.batch_size, preset=args.preset, interpolation=args.interpolation, crop_pct=args.crop_pct,
                   num_labels=args.num_labels, classes=classes, num_workers=args.num_workers, fused_input=bool(args.fused_input))
-        recs = explain(cm, files, method=args.method, overlay_dir=args.overlay_dir, **kw) if args.cmd == "explain" else predict(cm, files, **kw)
+        if args.cmd == "attribute":
+            recs = explain(cm, files, method="attribution", target=args.target, overlay_dir=args.overlay_dir, **kw)
+        else:
+            recs = explain(cm, files, method=args.method, overlay_dir=args.overlay_dir, **kw) if args.cmd == "explain" else predict(cm, files, **kw)
         for rec in recs:
             out.write(json.dumps(rec) + "\n")
             n += 1
@@ -793,6 +872,12 @@ def _parser():
     f.add_argument("--compact", required=True, help="the compact file to fine-tune")
     f.add_argument("--output", required=True, help="where the best model (validation top-1) is written, a version-1 compact file")
     add_stage2_flags(f, skip=("checkpoint_dir", "eval_only"))
+    # `attribute`: explain's records with class-specific relevance maps (explain(method="attribution")) -- predict's flags, --overlay_dir, --target
+    t = sub.add_parser("attribute")
+    _add_predict_flags(t)
+    t.add_argument("--target", type=_int_in(0, (1 << 20) - 1, "--target"), default=None,
+                   help="the class whose evidence is mapped, in [0, num_labels); default: every image's own top-1 label among --num_labels")
+    t.add_argument("--overlay_dir", default=None, help="write <index>_<basename>.png per readable image: the model's view with the map in red")
     # classify image files with a compact file; `explain` adds the attention rollout maps to the records
     for name in ("predict", "explain"):
         _add_predict_flags(sub.add_parser(name))
@@ -881,7 +966,7 @@ def main(argv=None):
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
     if args.cmd == "finetune":
         return finetune(args, dev)
-    if args.cmd in ("predict", "explain"):
+    if args.cmd in ("predict", "explain", "attribute"):
         return predict_command(args, dev)
     if args.cmd == "export" or not args.compact:
         model = _dense_model(args, dev)

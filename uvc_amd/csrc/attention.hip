@@ -1587,6 +1587,128 @@ template <typename T> int launch_rollout(const RolloutArgs& a, hipStream_t st) {
   return UVC_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Gradient-weighted rollout, one step (uvc_attention_relevance_step): r_out = keep * r_in + (mix / H) * sum_h ((P_h . dP_h)^+)^T r_in with
+// dP_h = dO_h V_h^T.  k_attn_rollout_step's shape -- one workgroup of 8 waves per (image, block of LQ = 128 keys) walking all heads, one writer per
+// output element, no atomics -- plus the dP chain of k_attn_bwd_dkv_long at a value width: per head a wave also holds its 16 keys' V fragments
+// (VFrag: in bf16 DV = 16 and 48 end on half a k-step, the missing chunks are zero in both operands), and the streamed tile carries the dO rows
+// (DV columns at VGeom's stride) beside the Q rows, lse * log2(e) (+inf on padded queries: p = 0) and r (0 there).  The ReLU sits between the two
+// products, so the second one stays on the VALU: acc += max(0, p * dp) * r in float32.  Padded keys (zero K and V fragments) may hold anything,
+// inf and NaN included: their lanes share no sum with a real key's and are not written.
+struct RelevanceArgs {
+  const void* qkv; const float* lse; const void* dout; const float* r_in; float* r_out;
+  int B, N, H;
+  float scale, keep, mix;
+};
+
+template <typename T, int DV>
+__global__ __launch_bounds__(512) void k_attn_relevance_step(RelevanceArgs a) {
+  typedef Mma<T> MM;
+  typedef Geom<T> G;
+  typedef LongTile<T> LT;
+  typedef LongTile<T, DV> LTD;
+  typedef VFrag<T, DV> VF;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int BUF = LT::BYTES + LTD::BYTES + 2 * LK * (int)sizeof(float);       // Q, dO, lse, r
+  const int nkb = (a.N + LQ - 1) / LQ;
+  const int kblk = blockIdx.x % nkb, b = blockIdx.x / nkb;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, li = lane & 15;
+  const size_t ldq = (size_t)a.H * (2 * HD + DV), ldo = (size_t)a.H * DV;
+  const T* qb = reinterpret_cast<const T*>(a.qkv) + (size_t)b * a.N * ldq;      // q of head 0; head h: + h * HD, its k: + (H + h) * HD
+  const T* vb = qb + 2 * a.H * HD;                                              // v of head 0; head h: + h * DV
+  const T* dob = reinterpret_cast<const T*>(a.dout) + (size_t)b * a.N * ldo;    // dO of head 0; head h: + h * DV
+  const float* lse = a.lse + (size_t)b * a.H * a.N;
+  const float* rin = a.r_in + (size_t)b * a.N;
+  const int key = kblk * LQ + w * 16 + li;
+  const float c2 = a.scale * 1.44269504088896340736f;
+  // threads 0 .. LK-1 carry lse * log2(e) of head h, LK .. 2 LK-1 the r of the same queries
+  auto ld_row = [&](int h, int r0) -> float {
+    const int i = r0 + ((int)threadIdx.x & (LK - 1));
+    if (threadIdx.x < LK) return i < a.N ? lse[(size_t)h * a.N + i] * 1.44269504088896340736f : INFINITY;
+    return i < a.N ? rin[i] : 0.f;
+  };
+  auto ld_kv = [&](typename MM::Frag (&f)[G::KS], typename MM::Frag (&fv)[VF::KS], int h) {
+#pragma unroll
+    for (int ks = 0; ks < G::KS; ++ks) f[ks] = row_frag_global<T>(qb + (a.H + h) * HD, ldq, key, a.N, ks * 4 + g);
+#pragma unroll
+    for (int ks = 0; ks < VF::KS; ++ks) fv[ks] = VF::global(vb + h * DV, ldq, key, a.N, ks * 4 + g);
+  };
+  typename MM::Frag kf[G::KS], kn[G::KS], vf[VF::KS], vn[VF::KS];
+  ld_kv(kn, vn, 0);
+  u32x4 pq[LT::NCL], pd[LTD::NCL];
+  float pr = 0.f;
+  LT::load(pq, qb, ldq, 0, a.N);
+  LTD::load(pd, dob, ldo, 0, a.N);
+  if (threadIdx.x < 2 * LK) pr = ld_row(0, 0);
+  LT::store(smem, pq);
+  LTD::store(smem + LT::BYTES, pd);
+  if (threadIdx.x < 2 * LK) reinterpret_cast<float*>(smem + LT::BYTES + LTD::BYTES)[threadIdx.x] = pr;
+  __syncthreads();
+  const int nqt = (a.N + LK - 1) / LK;
+  float acc = 0.f;
+  int it = 0;
+  for (int h = 0; h < a.H; ++h) {
+#pragma unroll
+    for (int ks = 0; ks < G::KS; ++ks) kf[ks] = kn[ks];
+#pragma unroll
+    for (int ks = 0; ks < VF::KS; ++ks) vf[ks] = vn[ks];
+    for (int j = 0; j < nqt; ++j, ++it) {
+      const char* sQ = smem + (it & 1) * BUF;
+      const char* sDO = sQ + LT::BYTES;
+      const float* sLse = reinterpret_cast<const float*>(sDO + LTD::BYTES);
+      const float* sR = sLse + LK;
+      const bool last = j + 1 == nqt;
+      const int h1 = last ? h + 1 : h, j1 = last ? 0 : j + 1;          // the tile behind this one
+      if (h1 < a.H) {
+        LT::load(pq, qb + h1 * HD, ldq, j1 * LK, a.N);
+        LTD::load(pd, dob + h1 * DV, ldo, j1 * LK, a.N);
+        if (threadIdx.x < 2 * LK) pr = ld_row(h1, j1 * LK);
+        if (last) ld_kv(kn, vn, h1);
+      }
+#pragma unroll
+      for (int t = 0; t < LK / 16; ++t) {
+        f32x4 c = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < G::KS; ++ks) {
+          c = MM::mma(row_frag_lds<T>(sQ, t * 16 + li, ks * 4 + g), kf[ks], c);
+          if (ks < VF::KS) dp = MM::mma(VF::lds(sDO, t * 16 + li, ks * 4 + g), vf[ks], dp);
+        }
+        const f32x4 l4 = *reinterpret_cast<const f32x4*>(sLse + t * 16 + g * 4);
+        const f32x4 r4 = *reinterpret_cast<const f32x4*>(sR + t * 16 + g * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc += fmaxf(__builtin_amdgcn_exp2f(c[e] * c2 - l4[e]) * dp[e], 0.f) * r4[e];
+      }
+      if (h1 < a.H) {
+        char* nQ = smem + ((it + 1) & 1) * BUF;                        // read in tile it - 1: every wave has passed the barrier behind it
+        LT::store(nQ, pq);
+        LTD::store(nQ + LT::BYTES, pd);
+        if (threadIdx.x < 2 * LK) reinterpret_cast<float*>(nQ + LT::BYTES + LTD::BYTES)[threadIdx.x] = pr;
+      }
+      __syncthreads();
+    }
+  }
+  acc = sum_rows4(acc);
+  if (key < a.N && g == 0) a.r_out[(size_t)b * a.N + key] = a.keep * rin[key] + (a.mix / (float)a.H) * acc;
+}
+
+template <typename T, int DV> int launch_relevance(const RelevanceArgs& a, hipStream_t st) {
+  const int64_t grid = (int64_t)a.B * ((a.N + LQ - 1) / LQ);
+  if (grid > 0x7fffffff) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_attention_relevance_step: too many workgroups");
+  constexpr int SH = 2 * (LongTile<T>::BYTES + LongTile<T, DV>::BYTES + 2 * LK * (int)sizeof(float));   // float32, DV = 64: 69 KiB
+  UVC_MAX_LDS(SH, k_attn_relevance_step<T, DV>);
+  k_attn_relevance_step<T, DV><<<(int)grid, 512, SH, st>>>(a);
+  UVC_CHECK_LAUNCH();
+  return UVC_OK;
+}
+template <typename T> int dispatch_relevance(const RelevanceArgs& a, int v_dim, hipStream_t st) {
+  switch (v_dim) {
+    case 16: return launch_relevance<T, 16>(a, st);
+    case 32: return launch_relevance<T, 32>(a, st);
+    case 48: return launch_relevance<T, 48>(a, st);
+    default: return launch_relevance<T, 64>(a, st);
+  }
+}
+
 template <typename T, int DV = HD> int launch_long(const AttnArgs& a, int which, hipStream_t st) {
   const int nblk = (a.N + LQ - 1) / LQ;
   const int64_t grid = (int64_t)a.B * a.H * nblk;
@@ -1804,4 +1926,20 @@ extern "C" int uvc_attention_rollout_step(const uvc_attn_rollout_args* p, void* 
   a.qkv = p->qkv; a.lse = p->lse; a.r_in = p->r_in; a.r_out = p->r_out;
   a.B = p->B; a.N = p->N; a.H = p->H; a.v_dim = p->v_dim; a.scale = p->scale; a.keep = p->keep; a.mix = p->mix;
   return p->dtype == UVC_F32 ? launch_rollout<float>(a, (hipStream_t)stream) : launch_rollout<bf16_t>(a, (hipStream_t)stream);
+}
+
+extern "C" int uvc_attention_relevance_step(const uvc_attn_relevance_args* p, void* stream) {
+  if (!p || !p->qkv || !p->lse || !p->dout || !p->r_in || !p->r_out) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_attention_relevance_step: null pointer");
+  if (p->head_dim != HD) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_attention_relevance_step: head_dim must be 64");
+  if (p->B <= 0 || p->N <= 0 || p->H <= 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_attention_relevance_step: empty problem");
+  if (p->dtype != UVC_F32 && p->dtype != UVC_BF16) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_attention_relevance_step: bad dtype");
+  if (p->v_dim != 16 && p->v_dim != 32 && p->v_dim != 48 && p->v_dim != 64) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_attention_relevance_step: v_dim must be 16, 32, 48 or 64");
+  if (p->N > LONG_MAX_N) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_attention_relevance_step: sequence length > 1026 not supported");
+  const int64_t n = (int64_t)p->B * p->N;
+  if (p->r_out < p->r_in + n && p->r_in < p->r_out + n) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_attention_relevance_step: r_out overlaps r_in");
+  if ((((uintptr_t)p->qkv | (uintptr_t)p->dout) & 15) != 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_attention_relevance_step: qkv and dout must be 16-byte aligned");
+  RelevanceArgs a;
+  a.qkv = p->qkv; a.lse = p->lse; a.dout = p->dout; a.r_in = p->r_in; a.r_out = p->r_out;
+  a.B = p->B; a.N = p->N; a.H = p->H; a.scale = p->scale; a.keep = p->keep; a.mix = p->mix;
+  return p->dtype == UVC_F32 ? dispatch_relevance<float>(a, p->v_dim, (hipStream_t)stream) : dispatch_relevance<bf16_t>(a, p->v_dim, (hipStream_t)stream);
 }

@@ -1,12 +1,13 @@
 // Compact-model sequencers (include/uvc_vit.h, uvc_vit_compact_*): a pruned DeiT exported at its kept widths (uvc_amd/compact.py) --
 // per block LayerNorm1, qkv GEMM, attention with a value head dim of its own (uvc_attn_args.v_dim), proj GEMM (+ bias + residual),
-// LayerNorm2, fc1 (+ bias, GELU), fc2 (+ bias + residual).  Host code (but for the start vector of the rollout); every arithmetic step is one of the kernels behind
+// LayerNorm2, fc1 (+ bias, GELU), fc2 (+ bias + residual).  Host code (but for the start vector of the rollout and the target pick of the attribution); every arithmetic step is one of the kernels behind
 // uvc_kernels.h, the embedding, token assembly, final norm and heads as uvc_vit_forward runs them.
 // ONE forward body serves evaluation (uvc_vit_compact_forward) and fine-tuning (uvc_vit_compact_train_forward): the same kernels in the
 // same order on one stream.  The modes differ in where a block's buffers live (carve: one shared set in eval, a set per block that
 // the backward reads in training) and in the fc1 epilogue (training also keeps GELU').  uvc_vit_compact_backward walks the blocks in
 // reverse: plain GEMMs and the attention backward at a value width.  uvc_vit_compact_rollout is the eval forward with qkv and lse kept
-// per attention block, then one uvc_attention_rollout_step per such block, last block first.
+// per attention block, then one uvc_attention_rollout_step per such block, last block first.  uvc_vit_compact_attribution is the training forward,
+// a target pick, and the same backward walk without any parameter gradient, with one uvc_attention_relevance_step per attention block.
 #include "engine_host.h"
 
 namespace {
@@ -65,8 +66,10 @@ int check_train(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nbl
 // Block k's buffers.  Training: its own, kept for the backward; x1 / xo (residual-stream rows [M, D]) only where the branch has a GEMM
 // (a bias-only branch adds in place).  Eval: every block points at one shared set sized by the widest block (h1 = h2, one mean / rstd
 // pair, no gp), and x1 / xo alternate between two residual-row buffers.  Rollout (CARVE_ROLLOUT): the eval set, but every block with heads
-// owns its qkv and lse (the reverse sweep reads them), and two [B, N] float vectors behind everything else.
-enum { CARVE_EVAL = 0, CARVE_TRAIN = 1, CARVE_ROLLOUT = 2 };
+// owns its qkv and lse (the reverse sweep reads them), and two [B, N] float vectors behind everything else.  Attribution (CARVE_ATTRIB): the
+// training set, and behind it the two [B, N] vectors, the one-hot logit gradients and 2 D floats the LayerNorm backward's parameter-gradient
+// pointers aim at (never reduced into: see ln_bwd).
+enum { CARVE_EVAL = 0, CARVE_TRAIN = 1, CARVE_ROLLOUT = 2, CARVE_ATTRIB = 3 };
 struct BlockBufs {
   void* h1; void* qkv; void* o; float* lse; float* mean1; float* rstd1; void* x1;
   void* h2; float* mean2; float* rstd2; void* gp; void* u; void* xo;
@@ -77,7 +80,8 @@ struct Work {
   // backward: the dL/dx stream ping-pongs between g[0] and g[1] (T: bf16, or float32 in the exact mode)
   void* g[2]; void* dA; void* dH; void* dO; void* dqkv; float* delta; float* ln_partial; int64_t ln_region; float* cs_partial;
   void* tn_ws; int64_t tn_ws_bytes; void* dhc; void* dpe;
-  float* roll[2];      // rollout: the row vector ping-pongs between them
+  float* roll[2];      // rollout, attribution: the row vector ping-pongs between them
+  float* dl[2]; float* ln_scratch;      // attribution: d_logits (/ d_logits_dist) [B, NC], the unused dgamma | dbeta [2 D]
 };
 
 int64_t train_tn_ws(const CDims& d, const uvc_compact_block* blocks, int nblocks) {
@@ -92,7 +96,7 @@ int64_t train_tn_ws(const CDims& d, const uvc_compact_block* blocks, int nblocks
 }
 
 int64_t carve(const CDims& d, const uvc_compact_block* blocks, int nblocks, int mode, char* base, Work& w) {
-  const bool training = mode == CARVE_TRAIN;
+  const bool training = mode == CARVE_TRAIN || mode == CARVE_ATTRIB;
   Carver c{base, 0};
   const int64_t M = d.M, MD = M * d.D;
   memset(&w, 0, sizeof(w));
@@ -154,6 +158,11 @@ int64_t carve(const CDims& d, const uvc_compact_block* blocks, int nblocks, int 
   w.tn_ws = c.take(w.tn_ws_bytes);
   w.dhc = c.take((int64_t)d.B * d.ntok * d.D * d.tsz);
   w.dpe = c.take((int64_t)d.B * d.np * d.D * d.tsz);
+  if (mode == CARVE_ATTRIB) {
+    w.roll[0] = (float*)c.take(M * 4); w.roll[1] = (float*)c.take(M * 4);
+    w.dl[0] = (float*)c.take((int64_t)d.B * d.NC * 4); w.dl[1] = (float*)c.take((int64_t)d.B * d.NC * 4);
+    w.ln_scratch = (float*)c.take((int64_t)2 * d.D * 4);
+  }
   return c.off;
 }
 
@@ -213,16 +222,20 @@ int flush_ln(Ctx& c) {
   c.n_ln = 0;
   return e;
 }
-// dx = LN'(dy; x) + add1; dgamma / dbeta through the batched reduction at the end of the pass
+// dx = LN'(dy; x) + add1; dgamma / dbeta through the batched reduction at the end of the pass.  dgamma == nullptr (attribution): uvc_layernorm_bwd
+// has no form without the per-block partial sums, so they go to the slot as ever, no reduction is queued, and the two pointers it insists on
+// aim at the workspace's 2 D scratch floats, which nothing writes
 int ln_bwd(Ctx& c, int slot, const void* dy, const void* x, const float* gamma, float* dgamma, float* dbeta, const float* mean, const float* rstd,
            void* dx, const void* add1, int rows, int rpg, int64_t gs) {
   if (c.n_ln == 64) TRY(flush_ln(c));
   uvc_ln_args a;
   memset(&a, 0, sizeof(a));
   a.x = x; a.x_lowp = c.d.rlow; a.gamma = gamma; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd); a.dy = dy; a.dx = dx; a.add1 = add1;
-  a.partial = c.w.ln_partial + c.w.ln_region * slot; a.dgamma = dgamma; a.dbeta = dbeta; a.defer_reduce = 1;
-  uvc_ln_reduce_item& it = c.ln_items[c.n_ln++];
-  it.partial = a.partial; it.dgamma = dgamma; it.dbeta = dbeta; it.dots = nullptr; it.nblocks = uvc_layernorm_bwd_nblocks(rows); it.reserved = 0;
+  a.partial = c.w.ln_partial + c.w.ln_region * slot; a.dgamma = dgamma ? dgamma : c.w.ln_scratch; a.dbeta = dgamma ? dbeta : c.w.ln_scratch + c.d.D; a.defer_reduce = 1;
+  if (dgamma) {
+    uvc_ln_reduce_item& it = c.ln_items[c.n_ln++];
+    it.partial = a.partial; it.dgamma = dgamma; it.dbeta = dbeta; it.dots = nullptr; it.nblocks = uvc_layernorm_bwd_nblocks(rows); it.reserved = 0;
+  }
   a.eps = c.d.eps; a.beta_acc = 0.f; a.rows = rows; a.D = c.d.D; a.rows_per_group = rpg; a.group_stride = gs; a.dtype = c.d.dtype;
   a.g_lowp = c.d.dtype == UVC_BF16;
   return uvc_layernorm_bwd(&a, c.st);
@@ -233,11 +246,11 @@ int zero_f32(const Ctx& c, float* p, int64_t n) {
   return e == hipSuccess ? UVC_OK : uvc_set_error(e, __FILE__, __LINE__);
 }
 
-int setup_train(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nblocks, const uvc_vit_io* io, void* stream) {
+int setup_train(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nblocks, const uvc_vit_io* io, void* stream, int mode = CARVE_TRAIN) {
   TRY(check_train(cfg, blocks, nblocks));
   if (!io || !io->params || !io->shadow || !io->workspace || io->batch <= 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact training: null io member (params, shadow, workspace) or batch <= 0");
   if (io->accumulate != 0.f) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_vit_compact training: gradient accumulation (io.accumulate must be 0)");
-  if (!bind(c, cfg, blocks, nblocks, io, stream, 1)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact training: workspace too small (uvc_vit_compact_train_workspace_bytes)");
+  if (!bind(c, cfg, blocks, nblocks, io, stream, mode)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact training: workspace too small (uvc_vit_compact_train_workspace_bytes; attribution: uvc_vit_compact_attribution_workspace_bytes)");
   return UVC_OK;
 }
 
@@ -424,7 +437,7 @@ extern "C" int uvc_vit_compact_train_update_shadows(const uvc_vit_cfg* cfg, cons
 }
 
 // ---- forward (eval, training) and backward -------------------------------------------------------------------------------------------
-// r[b, i] = 1 / ntok on the readout tokens (i < ntok), 0 elsewhere: the one device code of this file, too small for an entry point of its own
+// r[b, i] = 1 / ntok on the readout tokens (i < ntok), 0 elsewhere: device code of this file (with k_attrib_target), too small for an entry point of its own
 static __global__ void k_rollout_start(float* r, int64_t n, int N, int ntok) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) r[i] = (int)(i % N) < ntok ? 1.0f / (float)ntok : 0.f;
@@ -488,28 +501,36 @@ extern "C" int uvc_vit_compact_train_forward(const uvc_vit_cfg* cfg, const uvc_c
   return forward(c, cfg, blocks, nblocks, 1);
 }
 
-extern "C" int uvc_vit_compact_backward(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* stream) {
-  Ctx c;
-  TRY(setup_train(c, cfg, blocks, nblocks, io, stream));
-  if (!io->grads || !io->d_logits || (cfg->ntok == 2 && !io->d_logits_dist)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_backward: null io member");
+// The backward walk of uvc_vit_compact_backward and of uvc_vit_compact_attribution: dl / dld are dL/dlogits (/ dL/dlogits_dist).
+// G != nullptr (training): every parameter gradient goes to G, the walk runs down to the patch embedding.  G == nullptr (attribution): the
+// dgrad chain alone -- no weight-gradient GEMM, no column sum, no zeroed slot, no LayerNorm reduction -- with one uvc_attention_relevance_step
+// per block with heads right behind the attn.proj dgrad (*rel: the row vector, which ping-pongs with *rel_other); the walk ends behind the
+// step of the lowest block with heads.
+static int backward_walk(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nblocks, const float* dl, const float* dld, float* G,
+                         float** rel, float** rel_other) {
+  const uvc_vit_io* io = c.io;
+  void* stream = c.st;
   const CDims& d = c.d;
   Work& w = c.w;
   uvc_vit_offsets o; uvc_vit_shadow_offsets so;
   TRY(uvc_vit_compact_train_layout(cfg, blocks, nblocks, &o, &so));
   const float* P = io->params;
-  float* G = io->grads;
   hipStream_t hs = (hipStream_t)stream;
   auto wt = [&](int64_t soff) -> const void* { return (const char*)io->shadow + soff * d.tsz; };      // W^T copies (T; float32 in the exact mode)
   const int gf = d.dtype == UVC_F32 ? 1 : 0;
   const int rh = d.B * d.ntok;
   const Chain ch = chain_of(w, blocks, nblocks);
+  auto gp = [&](int64_t off) -> float* { return G ? G + off : nullptr; };      // a gradient slot; nullptr without parameter gradients
+  int low = nblocks;                                         // the lowest block with heads: where the attribution walk ends
+  for (int k = nblocks - 1; k >= 0; --k) if (blocks[k].heads > 0) low = k;
+  if (!G && low == nblocks) return UVC_OK;                   // no block has heads: the start vector is the answer
   // heads: dhc = dlogits . W, dW = dlogits^T . hc, db = colsum(dlogits)
-  TRY(nt(c, io->d_logits, 1, wt(so.head_wt), w.dhc, 0, d.B, d.D, d.NC, UVC_EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, d.ntok * d.D));
-  TRY(tn(c, io->d_logits, 1, w.hc, G + o.head_w, G + o.head_b, d.B, d.NC, d.D, 0, d.ntok * d.D));
+  TRY(nt(c, dl, 1, wt(so.head_wt), w.dhc, 0, d.B, d.D, d.NC, UVC_EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, d.ntok * d.D));
+  if (G) TRY(tn(c, dl, 1, w.hc, G + o.head_w, G + o.head_b, d.B, d.NC, d.D, 0, d.ntok * d.D));
   if (d.ntok == 2) {
-    TRY(nt(c, io->d_logits_dist, 1, wt(so.headd_wt), (char*)w.dhc + (size_t)d.D * d.tsz, 0, d.B, d.D, d.NC, UVC_EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0,
+    TRY(nt(c, dld, 1, wt(so.headd_wt), (char*)w.dhc + (size_t)d.D * d.tsz, 0, d.B, d.D, d.NC, UVC_EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0,
             d.ntok * d.D));
-    TRY(tn(c, io->d_logits_dist, 1, (const char*)w.hc + (size_t)d.D * d.tsz, G + o.headd_w, G + o.headd_b, d.B, d.NC, d.D, 0, d.ntok * d.D));
+    if (G) TRY(tn(c, dld, 1, (const char*)w.hc + (size_t)d.D * d.tsz, G + o.headd_w, G + o.headd_b, d.B, d.NC, d.D, 0, d.ntok * d.D));
   }
   // final norm on the token rows: dL/dx_L is zero on every other row
   int cur = 0, slot = 0;
@@ -517,7 +538,7 @@ extern "C" int uvc_vit_compact_backward(const uvc_vit_cfg* cfg, const uvc_compac
     const hipError_t he = hipMemsetAsync(w.g[cur], 0, (size_t)d.M * d.D * d.tsz, hs);
     if (he != hipSuccess) return uvc_set_error(he, __FILE__, __LINE__);
   }
-  TRY(ln_bwd(c, slot++, w.dhc, ch.xin[nblocks], P + o.norm_w, G + o.norm_w, G + o.norm_b, w.meanf, w.rstdf, w.g[cur], nullptr, rh, d.ntok, (int64_t)d.N * d.D));
+  TRY(ln_bwd(c, slot++, w.dhc, ch.xin[nblocks], P + o.norm_w, gp(o.norm_w), gp(o.norm_b), w.meanf, w.rstdf, w.g[cur], nullptr, rh, d.ntok, (int64_t)d.N * d.D));
   for (int k = nblocks - 1; k >= 0; --k) {
     const uvc_compact_block& bk = blocks[k];
     const BlockBufs& b = w.blk[k];
@@ -527,12 +548,12 @@ extern "C" int uvc_vit_compact_backward(const uvc_vit_cfg* cfg, const uvc_compac
     if (F > 0) {
       void* g = w.g[cur];
       TRY(nt(c, g, gf, wt(so.blk_wt[k][3]), w.dA, 0, d.M, F, d.D, UVC_EPI_MUL_AUX, nullptr, nullptr, b.gp));      // dA = (g . W2) * GELU'
-      TRY(tn(c, g, gf, b.u, G + q[10], G + q[11], d.M, d.D, F));
+      if (G) TRY(tn(c, g, gf, b.u, G + q[10], G + q[11], d.M, d.D, F));
       TRY(nt(c, w.dA, 0, wt(so.blk_wt[k][2]), w.dH, 0, d.M, d.D, F, UVC_EPI_NONE));
-      TRY(tn(c, w.dA, 0, b.h2, G + q[8], G + q[9], d.M, F, d.D));
-      TRY(ln_bwd(c, slot++, w.dH, ch.x1[k], P + q[6], G + q[6], G + q[7], b.mean2, b.rstd2, w.g[cur ^ 1], g, d.M, 1, d.D));      // dL/dx1
+      if (G) TRY(tn(c, w.dA, 0, b.h2, G + q[8], G + q[9], d.M, F, d.D));
+      TRY(ln_bwd(c, slot++, w.dH, ch.x1[k], P + q[6], gp(q[6]), gp(q[7]), b.mean2, b.rstd2, w.g[cur ^ 1], g, d.M, 1, d.D));      // dL/dx1
       cur ^= 1;
-    } else {      // the branch is fc2.bias: its gradient is the column sum of the stream, which passes through; norm2 is never read
+    } else if (G) {      // the branch is fc2.bias: its gradient is the column sum of the stream, which passes through; norm2 is never read
       TRY(uvc_colsum(w.g[cur], d.M, d.D, d.D, d.dtype, gf, w.cs_partial, G + q[11], 1.0f, nullptr, 0.f, nullptr, stream));
       TRY(zero_f32(c, G + q[6], q[11] - q[6]));
     }
@@ -540,25 +561,111 @@ extern "C" int uvc_vit_compact_backward(const uvc_vit_cfg* cfg, const uvc_compac
     if (bk.heads > 0) {
       void* gB = w.g[cur];
       TRY(nt(c, gB, gf, wt(so.blk_wt[k][1]), w.dO, 0, d.M, no, d.D, UVC_EPI_NONE));
-      TRY(tn(c, gB, gf, b.o, G + q[4], G + q[5], d.M, d.D, no));
+      if (G) TRY(tn(c, gB, gf, b.o, G + q[4], G + q[5], d.M, d.D, no));
+      if (rel) {
+        uvc_attn_relevance_args ra;
+        memset(&ra, 0, sizeof(ra));
+        ra.qkv = b.qkv; ra.lse = b.lse; ra.dout = w.dO; ra.r_in = *rel; ra.r_out = *rel_other;
+        ra.B = d.B; ra.N = d.N; ra.H = bk.heads; ra.head_dim = 64; ra.v_dim = bk.v_dim; ra.dtype = d.dtype; ra.scale = 0.125f; ra.keep = 1.0f; ra.mix = 1.0f;
+        TRY(uvc_attention_relevance_step(&ra, stream));
+        float* t = *rel; *rel = *rel_other; *rel_other = t;
+        if (k == low) return UVC_OK;                          // nothing below it is needed
+      }
       uvc_attn_args a;
       memset(&a, 0, sizeof(a));
       a.qkv = b.qkv; a.o = b.o; a.lse = b.lse; a.dout = w.dO; a.dqkv = w.dqkv; a.delta = w.delta;
       a.B = d.B; a.N = d.N; a.H = bk.heads; a.head_dim = 64; a.dtype = d.dtype; a.scale = 0.125f; a.v_dim = bk.v_dim;
       TRY(uvc_attention_bwd_vdim(&a, stream));
       TRY(nt(c, w.dqkv, 0, wt(so.blk_wt[k][0]), w.dH, 0, d.M, d.D, nq, UVC_EPI_NONE));
-      TRY(tn(c, w.dqkv, 0, b.h1, G + q[2], G + q[3], d.M, nq, d.D));
-      TRY(ln_bwd(c, slot++, w.dH, ch.xin[k], P + q[0], G + q[0], G + q[1], b.mean1, b.rstd1, w.g[cur ^ 1], gB, d.M, 1, d.D));      // dL/dx_k
+      if (G) TRY(tn(c, w.dqkv, 0, b.h1, G + q[2], G + q[3], d.M, nq, d.D));
+      TRY(ln_bwd(c, slot++, w.dH, ch.xin[k], P + q[0], gp(q[0]), gp(q[1]), b.mean1, b.rstd1, w.g[cur ^ 1], gB, d.M, 1, d.D));      // dL/dx_k
       cur ^= 1;
-    } else {
+    } else if (G) {
       TRY(uvc_colsum(w.g[cur], d.M, d.D, d.D, d.dtype, gf, w.cs_partial, G + q[5], 1.0f, nullptr, 0.f, nullptr, stream));
       TRY(zero_f32(c, G + q[0], q[5] - q[0]));
     }
   }
+  if (!G) return UVC_OK;
   TRY(flush_ln(c));
   // token assembly (the mode-1 token mask is a constant: no d_patch_mask) and the patch-embedding weight gradient
   TRY(uvc_assemble_tokens_bwd(w.g[cur], w.pe, io->patch_mask, w.dpe, G + o.pos_embed, G + o.cls_token, d.ntok == 2 ? G + o.dist_token : nullptr,
                               nullptr, d.B, d.np, d.D, d.ntok, d.dtype, 0, d.dtype == UVC_BF16, 0.f, stream));
   TRY(tn(c, w.dpe, 0, w.patches, G + o.patch_w, G + o.patch_b, d.B * d.np, d.D, d.K0));
   return UVC_OK;
+}
+
+extern "C" int uvc_vit_compact_backward(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* stream) {
+  Ctx c;
+  TRY(setup_train(c, cfg, blocks, nblocks, io, stream));
+  if (!io->grads || !io->d_logits || (cfg->ntok == 2 && !io->d_logits_dist)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_backward: null io member");
+  return backward_walk(c, cfg, blocks, nblocks, io->d_logits, io->d_logits_dist, io->grads, nullptr, nullptr);
+}
+
+// ---- class-specific relevance maps (gradient x attention) ------------------------------------------------------------------------------
+// One workgroup per image: the target class -- the given one, clamped into [0, nl), or the first maximum of the eval logits (lg, or
+// (lg + lgd) / 2 with the distillation token) over [0, nl) -- and the gradient of that eval logit with respect to the head outputs: onehot(t)
+// on lg, or onehot(t) / 2 on lg and lgd.
+static __global__ __launch_bounds__(256) void k_attrib_target(const float* lg, const float* lgd, const int32_t* target, int nl, int NC, float* dl, float* dld,
+                                                              int32_t* tout) {
+  __shared__ float sv[256];
+  __shared__ int si[256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float* a = lg + (size_t)b * NC;
+  const float* ad = lgd ? lgd + (size_t)b * NC : nullptr;
+  int t;
+  if (target) {
+    t = min(max(target[b], 0), nl - 1);
+  } else {
+    constexpr int NONE = 0x7fffffff;
+    float bv = 0.f; int bi = NONE;
+    for (int i = tid; i < nl; i += 256) {                    // ascending indices: a later equal value does not replace an earlier one
+      const float v = ad ? (a[i] + ad[i]) * 0.5f : a[i];
+      if (bi == NONE || v > bv) { bv = v; bi = i; }
+    }
+    sv[tid] = bv; si[tid] = bi;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if (tid < s) {
+        const float v = sv[tid + s]; const int i = si[tid + s];
+        if (i != NONE && (si[tid] == NONE || v > sv[tid] || (v == sv[tid] && i < si[tid]))) { sv[tid] = v; si[tid] = i; }
+      }
+      __syncthreads();
+    }
+    t = si[0];
+  }
+  const float one = ad ? 0.5f : 1.0f;
+  for (int i = tid; i < NC; i += 256) {
+    dl[(size_t)b * NC + i] = i == t ? one : 0.f;
+    if (ad) dld[(size_t)b * NC + i] = i == t ? one : 0.f;
+  }
+  if (tout && tid == 0) tout[b] = t;
+}
+
+extern "C" int64_t uvc_vit_compact_attribution_workspace_bytes(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int32_t batch) {
+  if (check_train(cfg, blocks, nblocks)) return -1;
+  if (batch <= 0) { uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_attribution_workspace_bytes: batch <= 0"); return -1; }
+  Work w;
+  return carve(cdims_of(*cfg, blocks, nblocks, batch), blocks, nblocks, CARVE_ATTRIB, nullptr, w);
+}
+
+extern "C" int uvc_vit_compact_attribution(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, const int32_t* target,
+                                           int32_t num_labels, float* relevance, int32_t* target_out, void* stream) {
+  if (!relevance) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_attribution: null relevance");
+  Ctx c;
+  TRY(setup_train(c, cfg, blocks, nblocks, io, stream, CARVE_ATTRIB));
+  if (!io->x || !io->logits || (cfg->ntok == 2 && !io->logits_dist)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_attribution: null io member");
+  const CDims& d = c.d;
+  if (num_labels < 1 || num_labels > d.NC) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_attribution: num_labels must lie in [1, num_classes]");
+  TRY(forward(c, cfg, blocks, nblocks, 1));
+  hipStream_t hs = (hipStream_t)stream;
+  k_attrib_target<<<(unsigned)d.B, 256, 0, hs>>>(io->logits, d.ntok == 2 ? io->logits_dist : nullptr, target, num_labels, d.NC, c.w.dl[0], c.w.dl[1], target_out);
+  UVC_CHECK_LAUNCH();
+  // the start vector: uniform over the readout tokens, as in uvc_vit_compact_rollout
+  float* r = c.w.roll[0];
+  float* other = c.w.roll[1];
+  k_rollout_start<<<(unsigned)((d.M + 255) / 256), 256, 0, hs>>>(r, d.M, d.N, d.ntok);
+  UVC_CHECK_LAUNCH();
+  TRY(backward_walk(c, cfg, blocks, nblocks, c.w.dl[0], c.w.dl[1], nullptr, &r, &other));
+  const hipError_t e = hipMemcpyAsync(relevance, r, (size_t)d.M * 4, hipMemcpyDeviceToDevice, hs);
+  return e == hipSuccess ? UVC_OK : uvc_set_error(e, __FILE__, __LINE__);
 }

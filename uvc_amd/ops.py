@@ -134,6 +134,18 @@ def attention_rollout_step(qkv, lse, r_in, r_out, B, N, H, v_dim, dtype, keep=0.
     L.check(L.lib().uvc_attention_rollout_step(C.byref(a), L.cur_stream()), "uvc_attention_rollout_step")
 
 
+def attention_relevance_step(qkv, lse, dout, r_in, r_out, B, N, H, v_dim, dtype, keep=1.0, mix=1.0):
+    """One step of the gradient-weighted rollout (include/uvc_kernels.h: uvc_attention_relevance_step):
+    r_out = keep * r_in + (mix / H) * sum_h ((P_h * dP_h)^+)^T r_in with dP_h = dout_h v_h^T, over qkv rows [q H*64 | k H*64 | v H*v_dim],
+    the forward's lse [B, H, N] and dout [B, N, H*v_dim] in the operand type; r_in / r_out float32 [B, N], distinct buffers."""
+    _chk(qkv, lse, dout, r_in, r_out)
+    a = L.uvc_attn_relevance_args()
+    a.qkv, a.lse, a.dout, a.r_in, a.r_out = (L.ptr(t) for t in (qkv, lse, dout, r_in, r_out))
+    a.B, a.N, a.H, a.head_dim, a.v_dim, a.dtype = B, N, H, 64, int(v_dim), dtype
+    a.scale, a.keep, a.mix = 64 ** -0.5, float(keep), float(mix)
+    L.check(L.lib().uvc_attention_relevance_step(C.byref(a), L.cur_stream()), "uvc_attention_relevance_step")
+
+
 def qkv_attention_supported(B, N, H, D, dtype):
     return bool(L.lib().uvc_qkv_attention_supported(B, N, H, D, dtype))
 
