@@ -374,6 +374,32 @@ int uvc_distill_loss(const uvc_loss_args* args, void* stream);
  * A NaN logit is never chosen; a row with fewer than k comparable logits reports index -1 and a NaN probability for the rest. */
 int uvc_logits_topk(const float* logits, int32_t B, int32_t ld, int32_t n_valid, int32_t k, float* probs, int32_t* index, void* stream);
 
+/* Perturbation tests of relevance maps (python -m uvc_amd.compact_perturb; Chefer, Gur & Wolf 2021, section 4): three kernels between two
+ * forwards.  Each returns UVC_OK or refuses before anything is launched; no atomics, one writer per output element, the same bits on a
+ * repeat and in any batch.
+ *
+ * uvc_patch_rank: the removal order of every image's patches.  scores float32 [B, ld]; the patches are columns [offset, offset + np), so a
+ * [B, N] map over the tokens goes in as it is with offset = ntok.  rank int32 [B, np]: rank[b, p] = the number of patches of image b
+ * that come before p.  descending = 1: j comes before p when s_j > s_p, or s_j == s_p and j < p; descending = 0: with <.  In both
+ * directions -0 equals +0, a NaN comes after every number, and NaNs are ordered among themselves by index: every row of rank is a
+ * permutation of 0 .. np - 1 whatever the input holds.  1 <= np (UVC_ERR_ARG), np <= 1024 (UVC_ERR_UNSUPPORTED), 0 <= offset and
+ * offset + np <= ld (UVC_ERR_ARG).  One workgroup per image, sized by np.
+ *
+ * uvc_patch_rows_perturb: rows [B * np, width] of dtype (UVC_F32 / UVC_BF16, uvc_patchify's layout), counts device int32 [nsteps],
+ * out [nsteps * B * np, width]: row (k, b, p) of out is row (b, p) of rows where rank[b, p] >= counts[k], else width elements of +0.0
+ * (selected, not multiplied: a NaN or inf in a removed source row gives exact zeros).  A count outside [0, np] is clamped on the device.
+ * Every source element is read once and written nsteps times; offsets are 64-bit.  16-byte loads and stores when width * sizeof(T) is a
+ * multiple of 16 and rows and out are 16-byte aligned, element by element otherwise (any width, any element-aligned pointers).
+ *
+ * uvc_logits_target: logits float32 [rows, ld], target int32 [period] with rows % period == 0; row r reads target[r % period], clamped
+ * into [0, n_valid).  prob[r] = exp(logit - row max) / sum over columns [0, n_valid) at the target, float32 arithmetic and reduction trees of
+ * uvc_logits_topk; hit[r] = 1 when the target is the FIRST maximum of those columns, else 0.  1 <= n_valid <= ld. */
+int uvc_patch_rank(const float* scores, int32_t B, int32_t ld, int32_t offset, int32_t np, int32_t descending, int32_t* rank, void* stream);
+int uvc_patch_rows_perturb(const void* rows, const int32_t* rank, const int32_t* counts, int32_t nsteps, int32_t B, int32_t np, int32_t width,
+                           int32_t dtype, void* out, void* stream);
+int uvc_logits_target(const float* logits, int32_t rows, int32_t ld, int32_t n_valid, const int32_t* target, int32_t period, float* prob,
+                      int32_t* hit, void* stream);
+
 /* clip_grad_norm_(max_norm) + AdamW over flat float32 buffers (joint_train.py:428-429;
  * torch.optim.AdamW(lr, betas, eps, weight_decay) semantics, decoupled decay).
  * uvc_grad_sqnorm accumulates sum(g^2) of a segment into sq[0] (accumulate = 0 for the first segment) and leaves sqrt(sq[0]) -- the

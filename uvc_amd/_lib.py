@@ -224,6 +224,9 @@ _SIGNATURES = {
     "uvc_gemm_nt_lnbwd": [C.POINTER(uvc_gemm_lnbwd_args), VP],
     "uvc_distill_loss": [C.POINTER(uvc_loss_args), VP],
     "uvc_logits_topk": [VP, I32, I32, I32, I32, VP, VP, VP],
+    "uvc_patch_rank": [VP, I32, I32, I32, I32, I32, VP, VP],
+    "uvc_patch_rows_perturb": [VP, VP, VP, I32, I32, I32, I32, I32, VP, VP],
+    "uvc_logits_target": [VP, I32, I32, I32, VP, I32, VP, VP, VP],
     "uvc_grad_sqnorm": [VP, I64, VP, VP, I32, VP],
     "uvc_adamw_step": [C.POINTER(uvc_adamw_args), VP],
     "uvc_scale_by_clip": [VP, I64, VP, F32, VP],

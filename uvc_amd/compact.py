@@ -27,6 +27,7 @@ apart: the function ``compact_train.CompactTrainer`` fine-tunes (a fine-tuned fi
 ``explain`` adds to ``predict``'s records what the model looked at: the attention rollout of the readout token(s) over the patches
 (``uvc_vit_compact_rollout``; ``reference_rollout`` is its written spec).  ``attribute`` maps the patches that speak for ONE label, the
 gradient-weighted rollout (``uvc_vit_compact_attribution`` through ``compact_attribution.CompactAttributionViT``; ``reference_attribution``).
+Whether such a map is faithful -- the perturbation test, deletion curves and their areas -- is ``python -m uvc_amd.compact_perturb``.
 """
 from __future__ import annotations
 

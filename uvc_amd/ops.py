@@ -637,6 +637,60 @@ def logits_topk(logits, k, n_valid=None):
     return probs, index
 
 
+def patch_rank(scores, offset=0, descending=True, np=None):
+    """int32 [B, np]: the removal order of every image's patches from float32 ``scores`` [B, ld], the patches being columns
+    [offset, offset + np) (default np: the rest of the row) -- rank[b, p] patches come before p; larger score first with ``descending``,
+    smaller first without, ties by index, -0 = +0, NaN last (uvc_patch_rank)."""
+    _chk(scores)
+    if scores.dim() != 2 or scores.dtype != torch.float32:
+        raise L.UvcHipError("patch_rank: scores must be float32 [B, ld]")
+    B, ld = scores.shape
+    offset = int(offset)
+    np = ld - offset if np is None else int(np)
+    rank = torch.empty(B, max(np, 0), dtype=torch.int32, device=scores.device)
+    L.check(L.lib().uvc_patch_rank(L.ptr(scores), B, ld, offset, np, int(bool(descending)), L.ptr(rank), L.cur_stream()), "uvc_patch_rank")
+    return rank
+
+
+def perturb_rows(rows, rank, counts, B, np, out=None):
+    """[nsteps * B * np, width] in ``rows``' type: per count, a copy of the patch rows [B * np, width] (float32 or bfloat16) in which the
+    rows of rank below the count are +0.0 (uvc_patch_rows_perturb).  ``rank`` int32 [B, np] (patch_rank), ``counts`` int32 [nsteps] on the
+    device."""
+    _chk(rows, rank, counts, out)
+    B, np = int(B), int(np)
+    if rows.dim() != 2 or rows.dtype not in (torch.float32, torch.bfloat16) or rows.shape[0] != B * np:
+        raise L.UvcHipError("perturb_rows: rows must be float32 or bfloat16 [B * np, width]")
+    if rank.dtype != torch.int32 or tuple(rank.shape) != (B, np) or counts.dtype != torch.int32 or counts.dim() != 1:
+        raise L.UvcHipError("perturb_rows: rank must be int32 [B, np] and counts int32 [nsteps]")
+    nsteps, width = counts.numel(), rows.shape[1]
+    if out is None:
+        out = torch.empty(nsteps * B * np, width, dtype=rows.dtype, device=rows.device)
+    elif out.dtype != rows.dtype or tuple(out.shape) != (nsteps * B * np, width):
+        raise L.UvcHipError("perturb_rows: out must be [nsteps * B * np, width] in rows' type")
+    L.check(L.lib().uvc_patch_rows_perturb(L.ptr(rows), L.ptr(rank), L.ptr(counts), nsteps, B, np, width,
+                                           UVC_F32 if rows.dtype == torch.float32 else UVC_BF16, L.ptr(out), L.cur_stream()),
+            "uvc_patch_rows_perturb")
+    return out
+
+
+def logits_target(logits, target, n_valid=None):
+    """(prob float32 [rows], hit int32 [rows]) of float32 ``logits`` [rows, ld]: the softmax over columns [0, n_valid) (default: all) at
+    ``target[r % period]`` (int32 [period] on the device, rows a multiple of period), and whether that column is the first maximum
+    (uvc_logits_target)."""
+    _chk(logits, target)
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise L.UvcHipError("logits_target: logits must be float32 [rows, ld]")
+    if target.dim() != 1 or target.dtype != torch.int32:
+        raise L.UvcHipError("logits_target: target must be int32 [period]")
+    rows, ld = logits.shape
+    n_valid = ld if n_valid is None else int(n_valid)
+    prob = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    hit = torch.empty(rows, dtype=torch.int32, device=logits.device)
+    L.check(L.lib().uvc_logits_target(L.ptr(logits), rows, ld, n_valid, L.ptr(target), target.numel(), L.ptr(prob), L.ptr(hit), L.cur_stream()),
+            "uvc_logits_target")
+    return prob, hit
+
+
 def image_crop_desc_dtype():
     """numpy dtype with the layout of uvc_image_crop_desc: a crop window inside an image of a resident store."""
     import numpy as np
