@@ -400,6 +400,35 @@ int uvc_patch_rows_perturb(const void* rows, const int32_t* rank, const int32_t*
 int uvc_logits_target(const float* logits, int32_t rows, int32_t ld, int32_t n_valid, const int32_t* target, int32_t period, float* prob,
                       int32_t* hit, void* stream);
 
+/* Pixel-resolution maps from the gradient of a class logit at the input (python -m uvc_amd.compact_pixel; uvc_vit_compact_input_grad of
+ * uvc_vit.h hands out the gradient as patch rows): saliency, gradient x input and integrated gradients (Sundararajan, Taly & Yan, ICML 2017).
+ * Bandwidth-bound kernels: every element is read once, 16-byte accesses where the row width and every pointer allow them and element by
+ * element otherwise (any width, any element-aligned pointers), 64-bit offsets, no atomics -- every sum has a fixed order, the same bits
+ * on a repeat.  Each returns UVC_OK or refuses before anything is launched.  "rows" are uvc_patchify's: [B * np, K0], K0 = C * P * P,
+ * k = c * P * P + ky * P + kx, np = (S / P)^2.  dtype (UVC_F32 / UVC_BF16) is the element type T of x, x0 and uvc_ig_rows' out.
+ *
+ * uvc_unpatchify: rows float32 [B * np, K0] -> out float32 [B, C, S, S], the exact inverse of uvc_patchify (a copy: no arithmetic).  Any
+ * P >= 1 with S % P == 0.
+ *
+ * uvc_ig_rows: the interpolated inputs of `count` steps of the midpoint rule: out[(s, b, p), :] = x0 + alpha_s * (x - x0),
+ * alpha_s = (first_step + s + 0.5) / steps, s < count, as fmaf(alpha_s, x - x0, x0) in float32, rounded once to T.  x T [nrows, width];
+ * x0 the same, or NULL for the zero baseline; out T [count * nrows, width].  0 <= first_step, first_step + count <= steps.
+ *
+ * uvc_ig_accumulate: acc float32 [n] = (first ? 0 : acc) + sum_{s < count} d_rows[s * n + i], s ascending (d_rows float32 [count, n]).
+ *
+ * uvc_pixel_maps: a float32 rows [B * np, K0] (a gradient, or uvc_ig_accumulate's sum); per element e = a * scale, or with x given
+ * e = (a * (x - x0)) * scale, every step in float32 (x, x0 T rows; x0 NULL: zero).  pixel float32 [B, S, S] = sum_c |e|, channels ascending; patch float32 [B, np] =
+ * the sum of |e| over the row and total float32 [B] = the signed sum of e over the image, both in fixed trees: one wave per row, a lane's
+ * elements in ascending order, the wave butterfly; for the total a second launch sums the image's np row sums the same way, its waves in
+ * order.  partial: float32 scratch [B * np].  Any of pixel / patch / total may be NULL (total needs partial).  x (and x0) are read
+ * 8 bytes at a time in bf16, beside the 16 bytes of a. */
+int uvc_unpatchify(const float* rows, float* out, int32_t B, int32_t C, int32_t S, int32_t P, void* stream);
+int uvc_ig_rows(const void* x, const void* x0, void* out, int64_t nrows, int32_t width, int32_t first_step, int32_t count, int32_t steps,
+                int32_t dtype, void* stream);
+int uvc_ig_accumulate(const float* d_rows, float* acc, int64_t n, int32_t count, int32_t first, void* stream);
+int uvc_pixel_maps(const float* a, const void* x, const void* x0, float scale, int32_t B, int32_t C, int32_t S, int32_t P, int32_t dtype,
+                   float* pixel, float* patch, float* total, float* partial, void* stream);
+
 /* clip_grad_norm_(max_norm) + AdamW over flat float32 buffers (joint_train.py:428-429;
  * torch.optim.AdamW(lr, betas, eps, weight_decay) semantics, decoupled decay).
  * uvc_grad_sqnorm accumulates sum(g^2) of a segment into sq[0] (accumulate = 0 for the first segment) and leaves sqrt(sq[0]) -- the

@@ -237,6 +237,23 @@ int64_t uvc_vit_compact_attribution_workspace_bytes(const uvc_vit_cfg* cfg, cons
 int uvc_vit_compact_attribution(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, const int32_t* target,
                                 int32_t num_labels, float* relevance, int32_t* target_out, void* stream);
 
+/* The gradient of one class's eval logit with respect to the INPUT, as patch rows: what saliency, gradient x input and integrated gradients
+ * (python -m uvc_amd.compact_pixel) are built on.  d_rows: device float32 [B * np, C * P * P] in uvc_patchify's layout (uvc_unpatchify of
+ * uvc_kernels.h turns them into [B, C, S, S]).
+ * One stream: uvc_vit_compact_train_forward's walk (logits / logits_dist are the eval forward's bits), uvc_vit_compact_attribution's target pick
+ * and one-hot logit gradient, then uvc_vit_compact_backward's walk with dgrads only -- no weight-gradient GEMM, column sum, LayerNorm parameter
+ * reduction or relevance step -- through EVERY block down to block 0 (a bias-only branch passes the stream through unchanged), the backward of
+ * token assembly (dpe = dtok patch rows * patch_mask; the sums over the batch it also makes go to scratch) and the patch-embedding dgrad
+ * d_rows = dpe [B * np, D] . W_patch [D, K0] through uvc_gemm_nt, whose [K0, D] operand is a transposed copy of the weight in the operand type
+ * made per call in this entry's workspace (the shadow layouts do not hold one).  With mode-1 hard gating the rows of zeroed patches are zeros.
+ * io as for uvc_vit_compact_attribution (the TRAINING shadow; workspace of uvc_vit_compact_input_grad_workspace_bytes), but patches_in is
+ * accepted and x may then be NULL, as in uvc_vit_compact_forward: the interpolated inputs of integrated gradients exist only as patch rows.
+ * target / num_labels / target_out as for uvc_vit_compact_attribution.  Sequences above 256 tokens: UVC_ERR_UNSUPPORTED and -1 from the
+ * workspace query, as every compact training entry point.  Deterministic. */
+int64_t uvc_vit_compact_input_grad_workspace_bytes(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int32_t batch);
+int uvc_vit_compact_input_grad(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, const int32_t* target,
+                               int32_t num_labels, float* d_rows, int32_t* target_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

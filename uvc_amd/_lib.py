@@ -227,6 +227,10 @@ _SIGNATURES = {
     "uvc_patch_rank": [VP, I32, I32, I32, I32, I32, VP, VP],
     "uvc_patch_rows_perturb": [VP, VP, VP, I32, I32, I32, I32, I32, VP, VP],
     "uvc_logits_target": [VP, I32, I32, I32, VP, I32, VP, VP, VP],
+    "uvc_unpatchify": [VP, VP, I32, I32, I32, I32, VP],
+    "uvc_ig_rows": [VP, VP, VP, I64, I32, I32, I32, I32, I32, VP],
+    "uvc_ig_accumulate": [VP, VP, I64, I32, I32, VP],
+    "uvc_pixel_maps": [VP, VP, VP, F32, I32, I32, I32, I32, I32, VP, VP, VP, VP, VP],
     "uvc_grad_sqnorm": [VP, I64, VP, VP, I32, VP],
     "uvc_adamw_step": [C.POINTER(uvc_adamw_args), VP],
     "uvc_scale_by_clip": [VP, I64, VP, F32, VP],
@@ -282,7 +286,8 @@ VIT_SYMBOLS = ["uvc_vit_layout", "uvc_vit_workspace_bytes", "uvc_vit_ws_offsets"
                "uvc_vit_compact_train_layout", "uvc_vit_compact_train_workspace_bytes", "uvc_vit_compact_train_update_shadows",
                "uvc_vit_compact_frozen_ranges", "uvc_vit_compact_train_forward", "uvc_vit_compact_backward",   # (uvc_amd/compact_train.py)
                "uvc_vit_compact_rollout_workspace_bytes", "uvc_vit_compact_rollout",   # (attention rollout maps: uvc_amd/compact.py)
-               "uvc_vit_compact_attribution_workspace_bytes", "uvc_vit_compact_attribution"]   # (uvc_amd/compact_attribution.py)
+               "uvc_vit_compact_attribution_workspace_bytes", "uvc_vit_compact_attribution",   # (uvc_amd/compact_attribution.py)
+               "uvc_vit_compact_input_grad_workspace_bytes", "uvc_vit_compact_input_grad"]   # (input gradients: uvc_amd/compact_pixel.py)
 
 
 def side_stream(device, priority_class=None):

@@ -399,7 +399,7 @@ _SLOTS = ["norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "att
 
 
 def _bind():
-    """The library with the argument types of the fourteen compact entry points (include/uvc_vit.h, uvc_vit_compact_*) set."""
+    """The library with the argument types of the compact entry points (include/uvc_vit.h, uvc_vit_compact_*) set."""
     from . import _lib as L
     from .model_distilled import uvc_vit_cfg, uvc_vit_io, uvc_vit_offsets, uvc_vit_shadow_offsets
     lib = L.lib()
@@ -413,7 +413,8 @@ def _bind():
                  "attribution": [C.POINTER(uvc_vit_io), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]}
         for n in ("layout", "workspace_bytes", "update_shadows"):
             tails["train_" + n] = tails[n]
-        tails["rollout_workspace_bytes"] = tails["attribution_workspace_bytes"] = tails["workspace_bytes"]
+        tails["input_grad"] = tails["attribution"]
+        tails["rollout_workspace_bytes"] = tails["attribution_workspace_bytes"] = tails["input_grad_workspace_bytes"] = tails["workspace_bytes"]
         for n, tail in tails.items():
             f = getattr(lib, "uvc_vit_compact_" + n)
             f.argtypes, f.restype = head + tail, C.c_int64 if n.endswith("workspace_bytes") else C.c_int
@@ -509,13 +510,15 @@ class _CompactModule(nn.Module):
 
     def _workspace(self, B, training):
         """One workspace per mode (eval, training, "rollout": the eval forward that keeps qkv and lse per block, or "attribution": the
-        training set plus what the relevance walk adds), for the last batch size seen."""
+        training set plus what the relevance walk adds, or "input_grad": the training set plus what the walk down to the patch rows adds), for
+        the last batch size seen."""
         mode = training if isinstance(training, str) else bool(training)
         key = (B, mode)
         if key not in self._ws:
             from . import _lib as L
             entry = {False: "uvc_vit_compact_workspace_bytes", True: "uvc_vit_compact_train_workspace_bytes",
-                     "rollout": "uvc_vit_compact_rollout_workspace_bytes", "attribution": "uvc_vit_compact_attribution_workspace_bytes"}[mode]
+                     "rollout": "uvc_vit_compact_rollout_workspace_bytes", "attribution": "uvc_vit_compact_attribution_workspace_bytes",
+                     "input_grad": "uvc_vit_compact_input_grad_workspace_bytes"}[mode]
             n = self._lib_call(entry, B)
             if n < 0:
                 L.check(-1, entry)

@@ -8,6 +8,8 @@
 // reverse: plain GEMMs and the attention backward at a value width.  uvc_vit_compact_rollout is the eval forward with qkv and lse kept
 // per attention block, then one uvc_attention_rollout_step per such block, last block first.  uvc_vit_compact_attribution is the training forward,
 // a target pick, and the same backward walk without any parameter gradient, with one uvc_attention_relevance_step per attention block.
+// uvc_vit_compact_input_grad is that forward and target pick, the dgrad walk through every block, the masked row copy of token assembly's
+// backward and the patch-embedding dgrad: the gradient of the class logit at the input, as patch rows.
 #include "engine_host.h"
 
 namespace {
@@ -68,8 +70,9 @@ int check_train(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nbl
 // pair, no gp), and x1 / xo alternate between two residual-row buffers.  Rollout (CARVE_ROLLOUT): the eval set, but every block with heads
 // owns its qkv and lse (the reverse sweep reads them), and two [B, N] float vectors behind everything else.  Attribution (CARVE_ATTRIB): the
 // training set, and behind it the two [B, N] vectors, the one-hot logit gradients and 2 D floats the LayerNorm backward's parameter-gradient
-// pointers aim at (never reduced into: see ln_bwd).
-enum { CARVE_EVAL = 0, CARVE_TRAIN = 1, CARVE_ROLLOUT = 2, CARVE_ATTRIB = 3 };
+// pointers aim at (never reduced into: see ln_bwd).  Input gradient (CARVE_INPUT): the training set, the one-hot logit gradients and the 2 D
+// floats, the [K0, D] transposed patch-embedding weight (T) and the (N + 2) D floats that take the batch sums of uvc_assemble_tokens_bwd.
+enum { CARVE_EVAL = 0, CARVE_TRAIN = 1, CARVE_ROLLOUT = 2, CARVE_ATTRIB = 3, CARVE_INPUT = 4 };
 struct BlockBufs {
   void* h1; void* qkv; void* o; float* lse; float* mean1; float* rstd1; void* x1;
   void* h2; float* mean2; float* rstd2; void* gp; void* u; void* xo;
@@ -81,7 +84,8 @@ struct Work {
   void* g[2]; void* dA; void* dH; void* dO; void* dqkv; float* delta; float* ln_partial; int64_t ln_region; float* cs_partial;
   void* tn_ws; int64_t tn_ws_bytes; void* dhc; void* dpe;
   float* roll[2];      // rollout, attribution: the row vector ping-pongs between them
-  float* dl[2]; float* ln_scratch;      // attribution: d_logits (/ d_logits_dist) [B, NC], the unused dgamma | dbeta [2 D]
+  float* dl[2]; float* ln_scratch;      // attribution, input gradient: d_logits (/ d_logits_dist) [B, NC], the unused dgamma | dbeta [2 D]
+  void* wpt; float* asm_scratch;        // input gradient: W_patch^T [K0, D] (T), the unused dpos [N, D] | dcls [D] | ddist [D]
 };
 
 int64_t train_tn_ws(const CDims& d, const uvc_compact_block* blocks, int nblocks) {
@@ -96,7 +100,7 @@ int64_t train_tn_ws(const CDims& d, const uvc_compact_block* blocks, int nblocks
 }
 
 int64_t carve(const CDims& d, const uvc_compact_block* blocks, int nblocks, int mode, char* base, Work& w) {
-  const bool training = mode == CARVE_TRAIN || mode == CARVE_ATTRIB;
+  const bool training = mode == CARVE_TRAIN || mode == CARVE_ATTRIB || mode == CARVE_INPUT;
   Carver c{base, 0};
   const int64_t M = d.M, MD = M * d.D;
   memset(&w, 0, sizeof(w));
@@ -158,10 +162,14 @@ int64_t carve(const CDims& d, const uvc_compact_block* blocks, int nblocks, int 
   w.tn_ws = c.take(w.tn_ws_bytes);
   w.dhc = c.take((int64_t)d.B * d.ntok * d.D * d.tsz);
   w.dpe = c.take((int64_t)d.B * d.np * d.D * d.tsz);
-  if (mode == CARVE_ATTRIB) {
-    w.roll[0] = (float*)c.take(M * 4); w.roll[1] = (float*)c.take(M * 4);
+  if (mode == CARVE_ATTRIB) { w.roll[0] = (float*)c.take(M * 4); w.roll[1] = (float*)c.take(M * 4); }
+  if (mode == CARVE_ATTRIB || mode == CARVE_INPUT) {
     w.dl[0] = (float*)c.take((int64_t)d.B * d.NC * 4); w.dl[1] = (float*)c.take((int64_t)d.B * d.NC * 4);
     w.ln_scratch = (float*)c.take((int64_t)2 * d.D * 4);
+  }
+  if (mode == CARVE_INPUT) {
+    w.wpt = c.take((int64_t)d.K0 * d.D * d.tsz);
+    w.asm_scratch = (float*)c.take((int64_t)(d.N + 2) * d.D * 4);
   }
   return c.off;
 }
@@ -250,7 +258,7 @@ int setup_train(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block* blocks,
   TRY(check_train(cfg, blocks, nblocks));
   if (!io || !io->params || !io->shadow || !io->workspace || io->batch <= 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact training: null io member (params, shadow, workspace) or batch <= 0");
   if (io->accumulate != 0.f) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_vit_compact training: gradient accumulation (io.accumulate must be 0)");
-  if (!bind(c, cfg, blocks, nblocks, io, stream, mode)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact training: workspace too small (uvc_vit_compact_train_workspace_bytes; attribution: uvc_vit_compact_attribution_workspace_bytes)");
+  if (!bind(c, cfg, blocks, nblocks, io, stream, mode)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact training: workspace too small (uvc_vit_compact_train_workspace_bytes; attribution: uvc_vit_compact_attribution_workspace_bytes; input gradient: uvc_vit_compact_input_grad_workspace_bytes)");
   return UVC_OK;
 }
 
@@ -505,9 +513,11 @@ extern "C" int uvc_vit_compact_train_forward(const uvc_vit_cfg* cfg, const uvc_c
 // G != nullptr (training): every parameter gradient goes to G, the walk runs down to the patch embedding.  G == nullptr (attribution): the
 // dgrad chain alone -- no weight-gradient GEMM, no column sum, no zeroed slot, no LayerNorm reduction -- with one uvc_attention_relevance_step
 // per block with heads right behind the attn.proj dgrad (*rel: the row vector, which ping-pongs with *rel_other); the walk ends behind the
-// step of the lowest block with heads.
+// step of the lowest block with heads.  d_rows != nullptr (input gradient; G and rel are null): the dgrad chain alone through every block down to
+// block 0 -- a bias-only branch passes the stream through unchanged -- then token assembly's backward (its batch sums go to scratch) and the
+// patch-embedding dgrad d_rows [B np, K0] (float32) = dpe . W_patch, which reads the workspace's transposed weight copy.
 static int backward_walk(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nblocks, const float* dl, const float* dld, float* G,
-                         float** rel, float** rel_other) {
+                         float** rel, float** rel_other, float* d_rows = nullptr) {
   const uvc_vit_io* io = c.io;
   void* stream = c.st;
   const CDims& d = c.d;
@@ -523,7 +533,7 @@ static int backward_walk(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block
   auto gp = [&](int64_t off) -> float* { return G ? G + off : nullptr; };      // a gradient slot; nullptr without parameter gradients
   int low = nblocks;                                         // the lowest block with heads: where the attribution walk ends
   for (int k = nblocks - 1; k >= 0; --k) if (blocks[k].heads > 0) low = k;
-  if (!G && low == nblocks) return UVC_OK;                   // no block has heads: the start vector is the answer
+  if (!G && !d_rows && low == nblocks) return UVC_OK;        // no block has heads: the start vector is the answer
   // heads: dhc = dlogits . W, dW = dlogits^T . hc, db = colsum(dlogits)
   TRY(nt(c, dl, 1, wt(so.head_wt), w.dhc, 0, d.B, d.D, d.NC, UVC_EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, d.ntok * d.D));
   if (G) TRY(tn(c, dl, 1, w.hc, G + o.head_w, G + o.head_b, d.B, d.NC, d.D, 0, d.ntok * d.D));
@@ -584,6 +594,12 @@ static int backward_walk(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block
       TRY(uvc_colsum(w.g[cur], d.M, d.D, d.D, d.dtype, gf, w.cs_partial, G + q[5], 1.0f, nullptr, 0.f, nullptr, stream));
       TRY(zero_f32(c, G + q[0], q[5] - q[0]));
     }
+  }
+  if (d_rows) {
+    float* sc = w.asm_scratch;
+    TRY(uvc_assemble_tokens_bwd(w.g[cur], w.pe, io->patch_mask, w.dpe, sc, sc + (int64_t)d.N * d.D, d.ntok == 2 ? sc + (int64_t)(d.N + 1) * d.D : nullptr,
+                                nullptr, d.B, d.np, d.D, d.ntok, d.dtype, 0, d.dtype == UVC_BF16, 0.f, stream));
+    return nt(c, w.dpe, 0, w.wpt, d_rows, 1, d.B * d.np, d.K0, d.D, UVC_EPI_NONE);
   }
   if (!G) return UVC_OK;
   TRY(flush_ln(c));
@@ -668,4 +684,32 @@ extern "C" int uvc_vit_compact_attribution(const uvc_vit_cfg* cfg, const uvc_com
   TRY(backward_walk(c, cfg, blocks, nblocks, c.w.dl[0], c.w.dl[1], nullptr, &r, &other));
   const hipError_t e = hipMemcpyAsync(relevance, r, (size_t)d.M * 4, hipMemcpyDeviceToDevice, hs);
   return e == hipSuccess ? UVC_OK : uvc_set_error(e, __FILE__, __LINE__);
+}
+
+// ---- the gradient of a class logit at the input (saliency, gradient x input, integrated gradients) ---------------------------------------
+extern "C" int64_t uvc_vit_compact_input_grad_workspace_bytes(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int32_t batch) {
+  if (check_train(cfg, blocks, nblocks)) return -1;
+  if (batch <= 0) { uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_input_grad_workspace_bytes: batch <= 0"); return -1; }
+  Work w;
+  return carve(cdims_of(*cfg, blocks, nblocks, batch), blocks, nblocks, CARVE_INPUT, nullptr, w);
+}
+
+extern "C" int uvc_vit_compact_input_grad(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, const int32_t* target,
+                                          int32_t num_labels, float* d_rows, int32_t* target_out, void* stream) {
+  if (!d_rows) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_input_grad: null d_rows");
+  Ctx c;
+  TRY(setup_train(c, cfg, blocks, nblocks, io, stream, CARVE_INPUT));
+  if ((!io->x && !io->patches_in) || !io->logits || (cfg->ntok == 2 && !io->logits_dist))   // x is read by uvc_patchify alone, as in the eval forward
+    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_input_grad: null io member");
+  const CDims& d = c.d;
+  if (num_labels < 1 || num_labels > d.NC) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_input_grad: num_labels must lie in [1, num_classes]");
+  TRY(forward(c, cfg, blocks, nblocks, 1));
+  k_attrib_target<<<(unsigned)d.B, 256, 0, (hipStream_t)stream>>>(io->logits, d.ntok == 2 ? io->logits_dist : nullptr, target, num_labels, d.NC, c.w.dl[0], c.w.dl[1],
+                                                                 target_out);
+  UVC_CHECK_LAUNCH();
+  // W_patch^T in the operand type: the pinned shadow layouts hold no such copy, so it is made per call (K0 D elements beside the pass's GEMMs)
+  uvc_vit_offsets o;
+  TRY(uvc_vit_compact_layout(cfg, blocks, nblocks, &o, nullptr));
+  TRY(uvc_cast_transpose(io->params + o.patch_w, d.D, d.K0, nullptr, c.w.wpt, d.dtype, stream));
+  return backward_walk(c, cfg, blocks, nblocks, c.w.dl[0], c.w.dl[1], nullptr, nullptr, nullptr, d_rows);
 }

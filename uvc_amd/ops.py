@@ -691,6 +691,87 @@ def logits_target(logits, target, n_valid=None):
     return prob, hit
 
 
+def _row_dtype(t, what):
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise L.UvcHipError(f"{what}: rows must be float32 or bfloat16")
+    return UVC_F32 if t.dtype == torch.float32 else UVC_BF16
+
+
+def unpatchify(rows, C, S, P, out=None):
+    """float32 [B, C, S, S] from float32 patch rows [B * np, C * P * P]: the exact inverse of ``patchify`` (uvc_unpatchify)."""
+    _chk(rows, out)
+    C, S, P = int(C), int(S), int(P)
+    if P < 1 or S < 1 or S % P:
+        raise L.UvcHipError("unpatchify: S must be a positive multiple of P")
+    npatch = (S // P) ** 2
+    if rows.dim() != 2 or rows.dtype != torch.float32 or rows.shape[1] != C * P * P or rows.shape[0] % npatch or rows.shape[0] == 0:
+        raise L.UvcHipError("unpatchify: rows must be float32 [B * np, C * P * P]")
+    B = rows.shape[0] // npatch
+    if out is None:
+        out = torch.empty(B, C, S, S, dtype=torch.float32, device=rows.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, C, S, S):
+        raise L.UvcHipError("unpatchify: out must be float32 [B, C, S, S]")
+    L.check(L.lib().uvc_unpatchify(L.ptr(rows), L.ptr(out), B, C, S, P, L.cur_stream()), "uvc_unpatchify")
+    return out
+
+
+def ig_rows(x, x0, first_step, count, steps, out=None):
+    """[count * R, width] in ``x``'s type: the interpolated inputs ``x0 + alpha_s (x - x0)``, ``alpha_s = (first_step + s + 1/2) / steps``,
+    s < count, of the patch rows ``x`` [R, width] (float32 or bfloat16) and the baseline rows ``x0`` (same shape and type, or None for
+    zeros), float32 arithmetic rounded once (uvc_ig_rows)."""
+    _chk(x, x0, out)
+    dt = _row_dtype(x, "ig_rows")
+    if x.dim() != 2 or (x0 is not None and (x0.dtype != x.dtype or x0.shape != x.shape)):
+        raise L.UvcHipError("ig_rows: x must be [R, width] and x0 None or of x's shape and type")
+    R, width = x.shape
+    count = int(count)
+    if out is None:
+        out = torch.empty(max(count, 0) * R, width, dtype=x.dtype, device=x.device)
+    elif out.dtype != x.dtype or tuple(out.shape) != (count * R, width):
+        raise L.UvcHipError("ig_rows: out must be [count * R, width] in x's type")
+    L.check(L.lib().uvc_ig_rows(L.ptr(x), L.ptr(x0), L.ptr(out), R, width, int(first_step), count, int(steps), dt, L.cur_stream()), "uvc_ig_rows")
+    return out
+
+
+def ig_accumulate(d_rows, acc, first):
+    """``acc`` float32 [R, width] = (0 if ``first`` else acc) + the sum over s, ascending, of ``d_rows`` float32 [count * R, width]
+    (uvc_ig_accumulate)."""
+    _chk(d_rows, acc)
+    if d_rows.dtype != torch.float32 or acc.dtype != torch.float32 or acc.numel() == 0 or d_rows.numel() == 0 or d_rows.numel() % acc.numel():
+        raise L.UvcHipError("ig_accumulate: float32 d_rows [count * R, width] and acc [R, width]")
+    L.check(L.lib().uvc_ig_accumulate(L.ptr(d_rows), L.ptr(acc), acc.numel(), d_rows.numel() // acc.numel(), int(bool(first)), L.cur_stream()),
+            "uvc_ig_accumulate")
+    return acc
+
+
+def pixel_maps(a, C, S, P, x=None, x0=None, scale=1.0):
+    """``(pixel float32 [B, S, S], patch float32 [B, np], total float32 [B])`` of float32 gradient rows ``a`` [B * np, C * P * P]: per element
+    ``e = a * scale``, or ``a * (x - x0) * scale`` with the patch rows ``x`` (and ``x0``; float32 or bfloat16) given; sum_c |e| per pixel,
+    the sum of |e| per patch, the signed sum of e per image (uvc_pixel_maps)."""
+    _chk(a, x, x0)
+    C, S, P = int(C), int(S), int(P)
+    if P < 1 or S < 1 or S % P:
+        raise L.UvcHipError("pixel_maps: S must be a positive multiple of P")
+    npatch = (S // P) ** 2
+    if a.dim() != 2 or a.dtype != torch.float32 or a.shape[1] != C * P * P or a.shape[0] % npatch or a.shape[0] == 0:
+        raise L.UvcHipError("pixel_maps: a must be float32 [B * np, C * P * P]")
+    dt = UVC_F32
+    if x is not None:
+        dt = _row_dtype(x, "pixel_maps")
+        if x.shape != a.shape or (x0 is not None and (x0.shape != a.shape or x0.dtype != x.dtype)):
+            raise L.UvcHipError("pixel_maps: x (and x0) must have a's shape, x0 x's type")
+    elif x0 is not None:
+        raise L.UvcHipError("pixel_maps: a baseline goes with x")
+    B, dev = a.shape[0] // npatch, a.device
+    pixel = torch.empty(B, S, S, dtype=torch.float32, device=dev)
+    patch = torch.empty(B, npatch, dtype=torch.float32, device=dev)
+    total = torch.empty(B, dtype=torch.float32, device=dev)
+    partial = torch.empty(B * npatch, dtype=torch.float32, device=dev)
+    L.check(L.lib().uvc_pixel_maps(L.ptr(a), L.ptr(x), L.ptr(x0), float(scale), B, C, S, P, dt, L.ptr(pixel), L.ptr(patch), L.ptr(total),
+                                   L.ptr(partial), L.cur_stream()), "uvc_pixel_maps")
+    return pixel, patch, total
+
+
 def image_crop_desc_dtype():
     """numpy dtype with the layout of uvc_image_crop_desc: a crop window inside an image of a resident store."""
     import numpy as np
