@@ -429,6 +429,41 @@ int uvc_ig_accumulate(const float* d_rows, float* acc, int64_t n, int32_t count,
 int uvc_pixel_maps(const float* a, const void* x, const void* x0, float scale, int32_t B, int32_t C, int32_t S, int32_t P, int32_t dtype,
                    float* pixel, float* patch, float* total, float* partial, void* stream);
 
+/* Nearest neighbours in a feature bank and the weighted k-NN vote (python -m uvc_amd.compact_transfer; Wu et al. 2018, DINO's
+ * knn_classifier).  Each call returns UVC_OK or refuses before anything is launched (outputs untouched); no atomics, every output
+ * element has one writer, the same bits on a repeat.
+ *
+ * uvc_knn_topk: queries [nq, D] (row stride ldq) and bank [n, D] (row stride ldb), both UVC_BF16 or both UVC_F32 (q_dtype / bank_dtype;
+ * a mix: UVC_ERR_UNSUPPORTED), row-major, pointers and row strides 16-byte aligned, strides >= D (UVC_ERR_ARG).  D a multiple of 8 in
+ * [8, 1024] (UVC_ERR_UNSUPPORTED), 1 <= k <= 64, nq >= 1, n >= 1 (UVC_ERR_ARG); n is an int32, every byte offset is 64-bit.
+ * s(q, x) = sum_d q_d x_d in float32, d ascending: exact products and float32 sums of v_mfma_f32_16x16x32_bf16 per 32 dims, or the fmaf
+ * chain of v_mfma_f32_16x16x4_f32; nothing is normalised.  The value of a (query, bank row) pair does not depend on nq, n, the row's place
+ * in the bank or the split count.  sims float32 [nq, k] and idx int32 [nq, k]: the k largest similarities of every query in descending
+ * order, equal values by ascending bank row.  Lists start as (-inf, -1), the bank is visited in ascending row order and a similarity
+ * enters a list only when it is strictly greater than the list's last entry: a NaN or -inf similarity never enters, +inf ranks first,
+ * and with n < k the remaining slots stay (-inf, -1).  Bank rows past n are never read and masked to -inf; query rows past nq are never
+ * stored.  One workgroup per 64 queries; splits > 1 divides the bank into that many contiguous row ranges over a second grid dimension
+ * (partial lists in `workspace`, merged under the same order), splits = 0 chooses from the shapes and the device's CU count (split when
+ * the query tiles are fewer than twice the CUs).  A request is clamped to [1, min(512, ceil(n / 64))]; every split count gives the same
+ * bits.  uvc_knn_workspace_bytes: the bytes `workspace` needs for (nq, n, k, splits) -- 0 without a split -- and the split count used. */
+typedef struct uvc_knn_args {
+  const void* queries; const void* bank;
+  float* sims; int32_t* idx;
+  void* workspace; int64_t workspace_bytes;
+  int64_t ldq, ldb;
+  int32_t nq, n, D, k, q_dtype, bank_dtype, splits, reserved;
+} uvc_knn_args;
+int uvc_knn_workspace_bytes(int32_t nq, int32_t n, int32_t k, int32_t splits, int64_t* bytes, int32_t* splits_used);
+int uvc_knn_topk(const uvc_knn_args* args, void* stream);
+/* uvc_knn_vote: sims / idx [nq, k] as uvc_knn_topk leaves them, labels [n] (int32, or int64 with labels_i64), 1 <= num_classes <= 65536,
+ * 1 <= k <= 64.  w_j = exp((s_j - s_0) / T) in float64 with s_0 the row's first (largest) similarity (w_j = 1 where s_j == s_0, and for every
+ * j with T <= 0: a plain majority); score[c] = sum_j w_j [label(idx_j) == c], j ascending in float64 by one thread per class, rounded once
+ * to float32.  Slots with an index outside [0, n) and labels outside [0, num_classes) count for nothing.  scores float32 [nq, num_classes]
+ * or NULL; pred int32 [nq]: the first maximum of the row's scores (the lowest class), -1 for a row with no valid neighbour.  One workgroup
+ * per query, fixed trees. */
+int uvc_knn_vote(const float* sims, const int32_t* idx, const void* labels, int32_t labels_i64, int32_t nq, int32_t n, int32_t k,
+                 int32_t num_classes, float temperature, float* scores, int32_t* pred, void* stream);
+
 /* clip_grad_norm_(max_norm) + AdamW over flat float32 buffers (joint_train.py:428-429;
  * torch.optim.AdamW(lr, betas, eps, weight_decay) semantics, decoupled decay).
  * uvc_grad_sqnorm accumulates sum(g^2) of a segment into sq[0] (accumulate = 0 for the first segment) and leaves sqrt(sq[0]) -- the

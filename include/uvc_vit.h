@@ -188,6 +188,14 @@ int uvc_vit_compact_forward(const uvc_vit_cfg* cfg, const uvc_compact_block* blo
 int64_t uvc_vit_compact_rollout_workspace_bytes(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int32_t batch);
 int uvc_vit_compact_rollout(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, float* rollout,
                             int32_t method, void* stream);
+/* Features (python -m uvc_amd.compact_transfer): uvc_vit_compact_forward -- the same workspace (uvc_vit_compact_workspace_bytes) and io,
+ * patches_in included, and logits / logits_dist are its bits -- then one small kernel over the final-norm readout rows [B, ntok, D] the
+ * heads read: feats [B, D] = their float32 mean over the ntok rows (the class row; (cls + dist) / 2 with the distillation token, whose eval
+ * logits average the two heads), divided by max(||.||_2, 1e-12) with `normalize` (F.normalize).  feats_dtype UVC_F32, or UVC_BF16: the
+ * float32 result rounded once.  One wave per row, a lane's dims in ascending order and the wave butterfly: deterministic, and a row does
+ * not depend on the batch.  Any N the eval forward takes. */
+int uvc_vit_compact_features(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* feats,
+                             int32_t normalize, int32_t feats_dtype, void* stream);
 
 /* ---- fine-tuning a compact model at its kept widths (uvc_amd/compact_train.py) ----
  * One flat float32 parameter buffer serves eval and training, and a gradient buffer congruent with it: `off` is uvc_vit_compact_layout's.

@@ -126,6 +126,12 @@ class uvc_adamw_args(C.Structure):
                [("step", C.c_int32), ("flags", C.c_void_p)]
 
 
+class uvc_knn_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("queries", "bank", "sims", "idx", "workspace")] + \
+               [(n, C.c_int64) for n in ("workspace_bytes", "ldq", "ldb")] + \
+               [(n, C.c_int32) for n in ("nq", "n", "D", "k", "q_dtype", "bank_dtype", "splits", "reserved")]
+
+
 class uvc_unfold_args(C.Structure):          # include/uvc_t2t.h
     _fields_ = [("src", C.c_void_p)] + [(n, C.c_int64) for n in ("sb", "sc", "sh", "sw")] + \
                [(n, C.c_int32) for n in ("B", "C", "H", "W", "k", "s", "p", "ldo", "out_is_f32", "dtype")] + \
@@ -231,6 +237,9 @@ _SIGNATURES = {
     "uvc_ig_rows": [VP, VP, VP, I64, I32, I32, I32, I32, I32, VP],
     "uvc_ig_accumulate": [VP, VP, I64, I32, I32, VP],
     "uvc_pixel_maps": [VP, VP, VP, F32, I32, I32, I32, I32, I32, VP, VP, VP, VP, VP],
+    "uvc_knn_workspace_bytes": [I32, I32, I32, I32, C.POINTER(I64), C.POINTER(I32)],
+    "uvc_knn_topk": [C.POINTER(uvc_knn_args), VP],
+    "uvc_knn_vote": [VP, VP, VP, I32, I32, I32, I32, I32, F32, VP, VP, VP],
     "uvc_grad_sqnorm": [VP, I64, VP, VP, I32, VP],
     "uvc_adamw_step": [C.POINTER(uvc_adamw_args), VP],
     "uvc_scale_by_clip": [VP, I64, VP, F32, VP],
@@ -287,7 +296,8 @@ VIT_SYMBOLS = ["uvc_vit_layout", "uvc_vit_workspace_bytes", "uvc_vit_ws_offsets"
                "uvc_vit_compact_frozen_ranges", "uvc_vit_compact_train_forward", "uvc_vit_compact_backward",   # (uvc_amd/compact_train.py)
                "uvc_vit_compact_rollout_workspace_bytes", "uvc_vit_compact_rollout",   # (attention rollout maps: uvc_amd/compact.py)
                "uvc_vit_compact_attribution_workspace_bytes", "uvc_vit_compact_attribution",   # (uvc_amd/compact_attribution.py)
-               "uvc_vit_compact_input_grad_workspace_bytes", "uvc_vit_compact_input_grad"]   # (input gradients: uvc_amd/compact_pixel.py)
+               "uvc_vit_compact_input_grad_workspace_bytes", "uvc_vit_compact_input_grad",   # (input gradients: uvc_amd/compact_pixel.py)
+               "uvc_vit_compact_features"]   # (features for k-NN and re-heading: uvc_amd/compact_transfer.py)
 
 
 def side_stream(device, priority_class=None):

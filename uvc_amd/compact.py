@@ -28,6 +28,8 @@ apart: the function ``compact_train.CompactTrainer`` fine-tunes (a fine-tuned fi
 (``uvc_vit_compact_rollout``; ``reference_rollout`` is its written spec).  ``attribute`` maps the patches that speak for ONE label, the
 gradient-weighted rollout (``uvc_vit_compact_attribution`` through ``compact_attribution.CompactAttributionViT``; ``reference_attribution``).
 Whether such a map is faithful -- the perturbation test, deletion curves and their areas -- is ``python -m uvc_amd.compact_perturb``.
+Another label set -- the model's features for a dataset (``CompactVisionTransformer.features``), their k-NN top-1 and a new head that
+``finetune`` trains -- is ``python -m uvc_amd.compact_transfer``.
 """
 from __future__ import annotations
 
@@ -259,10 +261,11 @@ def reference_attribution(export: dict, x: torch.Tensor, target=None, num_labels
     return r, t.clone()
 
 
-def _reference_walk(export: dict, x: torch.Tensor, keep_attention: bool = False, keep_heads: bool = False):
+def _reference_walk(export: dict, x: torch.Tensor, keep_attention: bool = False, keep_heads: bool = False, keep_readout: bool = False):
     """The block loop behind ``reference_logits``, ``reference_rollout`` and ``reference_attribution``: ``(logits, logits_dist, atts)``;
     with ``keep_attention`` ``atts`` lists the head-mean softmax ``[B, N, N]`` of every block that has heads, in block order, with
-    ``keep_heads`` the per-head softmax ``[B, H_l, N, N]`` itself, the very tensor the block goes on with (else it is empty)."""
+    ``keep_heads`` the per-head softmax ``[B, H_l, N, N]`` itself, the very tensor the block goes on with (else it is empty).
+    ``keep_readout`` appends a fourth item, the final-norm readout rows ``[B, ntok, D]`` the heads read (``compact_transfer``)."""
     check_export(export)
     cfg = export["cfg"]
     P = {k: v.to(device=x.device, dtype=x.dtype) for k, v in export["state_dict"].items()}
@@ -307,6 +310,8 @@ def _reference_walk(export: dict, x: torch.Tensor, keep_attention: bool = False,
     h = F.layer_norm(h, (D,), P["norm.weight"], P["norm.bias"], eps)
     o = F.linear(h[:, 0], P["head.weight"], P["head.bias"])
     od = F.linear(h[:, 1], P["head_dist.weight"], P["head_dist.bias"]) if cfg["enable_dist"] else o
+    if keep_readout:
+        return o, od, atts, h[:, :2 if cfg["enable_dist"] else 1]
     return o, od, atts
 
 
@@ -414,6 +419,7 @@ def _bind():
         for n in ("layout", "workspace_bytes", "update_shadows"):
             tails["train_" + n] = tails[n]
         tails["input_grad"] = tails["attribution"]
+        tails["features"] = [C.POINTER(uvc_vit_io), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         tails["rollout_workspace_bytes"] = tails["attribution_workspace_bytes"] = tails["input_grad_workspace_bytes"] = tails["workspace_bytes"]
         for n, tail in tails.items():
             f = getattr(lib, "uvc_vit_compact_" + n)
@@ -544,7 +550,7 @@ class _CompactModule(nn.Module):
         io.x, io.patch_mask, io.batch, io.training = L.ptr(x), L.ptr(mask), B, int(training is True)
         return io, mask
 
-    def _forward(self, x, training=False, patches=None, rollout=None):
+    def _forward(self, x, training=False, patches=None, rollout=None, features=None):
         """``(logits, logits_dist or None, what a backward needs of the pass)`` through the eval or the training forward.  ``patches``
         (eval only, in place of ``x``): the batch's patch rows, which the forward then does not make itself.  ``rollout`` (eval only;
         0 = rollout, 1 = last): the pass goes through ``uvc_vit_compact_rollout`` and its maps, float32 [B, N], come back as ``"maps"``."""
@@ -570,7 +576,15 @@ class _CompactModule(nn.Module):
             maps = torch.empty(B, _seq(self._export["cfg"]), device=dev)
             L.check(self._lib_call("uvc_vit_compact_rollout", C.byref(io), L.ptr(maps), int(rollout), L.cur_stream()), "uvc_vit_compact_rollout")
             return logits, logits_dist, dict(x=x, B=B, mask=mask, maps=maps)
-        entry = "uvc_vit_compact_train_forward" if training else "uvc_vit_compact_forward"
+        if features is not None:      # (eval only; (normalize, dtype)): uvc_vit_compact_features, the forward plus the readout kernel
+            if training:
+                raise ValueError("features come from the eval forward")
+            from . import ops
+            feats = torch.empty(B, self._export["cfg"]["embed_dim"], dtype=features[1], device=dev)
+            L.check(self._lib_call("uvc_vit_compact_features", C.byref(io), L.ptr(feats), int(features[0]),
+                                   ops.UVC_F32 if features[1] == torch.float32 else ops.UVC_BF16, L.cur_stream()), "uvc_vit_compact_features")
+            return logits, logits_dist, dict(x=x, B=B, mask=mask, feats=feats)
+        entry ="uvc_vit_compact_train_forward" if training else "uvc_vit_compact_forward"
         L.check(self._lib_call(entry, C.byref(io), L.cur_stream()), entry)
         return logits, logits_dist, dict(x=x, B=B, mask=mask)
 
@@ -610,6 +624,17 @@ class CompactVisionTransformer(_CompactModule):
             raise ValueError(f"method must be one of {METHODS}, not {method!r}")
         o, od, kept = self._forward(x, patches=patches, rollout=METHODS.index(method))
         return (o if od is None else (o + od) / 2), kept["maps"]
+
+    @torch.no_grad()
+    def features(self, x=None, *, patches=None, normalize=True, dtype=torch.float32):
+        """``(eval logits, feats [B, D])``: the logits are ``forward``'s bit for bit; ``feats`` is the float32 mean of the final-norm
+        readout rows the heads read (the class row; ``(cls + dist) / 2`` with the distillation token), divided by ``max(norm, 1e-12)``
+        with ``normalize`` (``F.normalize``) -- ``compact_transfer.reference_features`` is the spec.  ``dtype`` torch.float32, or
+        torch.bfloat16: the float32 result rounded once.  Inputs as ``forward`` takes them."""
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"dtype must be torch.float32 or torch.bfloat16, not {dtype!r}")
+        o, od, kept = self._forward(x, patches=patches, features=(bool(normalize), dtype))
+        return (o if od is None else (o + od) / 2), kept["feats"]
 
 
 # ---- classify image files -------------------------------------------------------------------------------------------------------

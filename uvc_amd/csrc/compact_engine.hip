@@ -467,6 +467,44 @@ extern "C" int uvc_vit_compact_forward(const uvc_vit_cfg* cfg, const uvc_compact
   return forward(c, cfg, blocks, nblocks, 0);
 }
 
+// feats[b, :] = the mean of row b's ntok readout rows (/ max(its 2-norm, 1e-12)): one wave per row, a lane's dims in ascending order, the wave butterfly
+template <typename T, typename O>
+static __global__ __launch_bounds__(256) void k_readout_features(const T* __restrict__ hc, int B, int ntok, int D, int normalize, O* __restrict__ feats) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+  if (row >= B) return;
+  const T* h = hc + (size_t)row * ntok * D;
+  auto mean_at = [&](int d) { return ntok == 2 ? (ElemIO<T>::load(h + d) + ElemIO<T>::load(h + D + d)) * 0.5f : ElemIO<T>::load(h + d); };
+  float scale = 1.f;
+  if (normalize) {
+    float ss = 0.f;
+    for (int d = l; d < D; d += 64) { const float m = mean_at(d); ss = fmaf(m, m, ss); }
+    scale = fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
+  }
+  for (int d = l; d < D; d += 64) ElemIO<O>::store(feats + (size_t)row * D + d, normalize ? __fdiv_rn(mean_at(d), scale) : mean_at(d));
+}
+
+extern "C" int uvc_vit_compact_features(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, void* feats,
+                                        int32_t normalize, int32_t feats_dtype, void* stream) {
+  if (!feats) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_features: null feats");
+  if (feats_dtype != UVC_F32 && feats_dtype != UVC_BF16) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_features: feats_dtype must be UVC_F32 or UVC_BF16");
+  Ctx c;
+  TRY(setup_eval(c, cfg, blocks, nblocks, io, stream, CARVE_EVAL));
+  TRY(forward(c, cfg, blocks, nblocks, 0));
+  const CDims& d = c.d;
+  const unsigned grid = (unsigned)((d.B + 3) / 4);
+  hipStream_t st = (hipStream_t)stream;
+  const int nz = normalize != 0;
+  if (d.dtype == UVC_F32) {
+    if (feats_dtype == UVC_F32) k_readout_features<float, float><<<grid, 256, 0, st>>>((const float*)c.w.hc, d.B, d.ntok, d.D, nz, (float*)feats);
+    else k_readout_features<float, bf16_t><<<grid, 256, 0, st>>>((const float*)c.w.hc, d.B, d.ntok, d.D, nz, (bf16_t*)feats);
+  } else {
+    if (feats_dtype == UVC_F32) k_readout_features<bf16_t, float><<<grid, 256, 0, st>>>((const bf16_t*)c.w.hc, d.B, d.ntok, d.D, nz, (float*)feats);
+    else k_readout_features<bf16_t, bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)c.w.hc, d.B, d.ntok, d.D, nz, (bf16_t*)feats);
+  }
+  UVC_CHECK_LAUNCH();
+  return UVC_OK;
+}
+
 extern "C" int64_t uvc_vit_compact_rollout_workspace_bytes(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int32_t batch) {
   if (check_blocks(cfg, blocks, nblocks)) return -1;
   if (batch <= 0) { uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_rollout_workspace_bytes: batch <= 0"); return -1; }

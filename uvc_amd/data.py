@@ -605,6 +605,49 @@ def build_loaders(args, rank=0, world=1, splits=("train", "test")):
     return train, test
 
 
+def build_eval_loader(args, split, dataset=None):
+    """(loader, data_classes): ONE split of --dataset ("train" or "test") under the EVAL transform, every sample in dataset order and the
+    short last batch included -- what feature extraction reads (python -m uvc_amd.compact_transfer); build_loaders gives the train split
+    with augmentation only.  Reads build_loaders' attributes (dataset, data_dir, img_size, eval_batch_size, num_workers, packed_dir,
+    resident, interpolation, crop_pct); CIFAR: the square resize with 0.5 / 0.5, ImageNet: resize + centre crop with its mean / std.
+    ``dataset``: a ready dataset (``load(i)`` / ``targets``) in place of the files, labelled by args.dataset's transform."""
+    if split not in ("train", "test"):
+        raise ValueError(f"split must be 'train' or 'test', not {split!r}")
+    if args.dataset not in ("cifar10", "cifar100", "imagenet"):
+        raise ValueError(args.dataset)
+    S = args.img_size
+    packed_dir = getattr(args, "packed_dir", None)
+    resident = bool(int(getattr(args, "resident", 0) or 0))
+    interpolation = getattr(args, "interpolation", None) or "bilinear"
+    crop_pct = getattr(args, "crop_pct", None)
+    _pil_filter(interpolation)
+    eval_resize_side(S, crop_pct)
+    Loader = DeviceLoader
+    if resident:
+        from .packed import ResidentLoader as Loader
+    cifar = args.dataset in ("cifar10", "cifar100")
+    if dataset is not None:
+        ds = dataset
+    elif packed_dir:
+        from .packed import EXTENSION, PackedDataset
+        ds = PackedDataset(os.path.join(packed_dir, ("train" if split == "train" else "val") + EXTENSION))
+    elif cifar:
+        ds = read_cifar(args.data_dir, args.dataset, split == "train")
+    else:
+        if resident:
+            raise ValueError("--resident 1 keeps decoded pixels on the device and image folders are not decoded: pack first and pass --packed_dir")
+        ds = ImageFolder(os.path.join(args.data_dir, "train" if split == "train" else "val"))
+    if cifar:
+        classes = 10 if args.dataset == "cifar10" else 100
+        kw = dict(mean=CIFAR_MEAN, std=CIFAR_STD, eval="square")
+    else:
+        names = getattr(ds, "classes", None)
+        classes = len(names) if names is not None else (ds.num_classes() if hasattr(ds, "num_classes") else int(max(ds.targets)) + 1)
+        kw = dict(mean=IMAGENET_MEAN, std=IMAGENET_STD, eval="center", crop_pct=crop_pct)
+    loader = Loader(ds, args.eval_batch_size, S, train=False, num_workers=getattr(args, "num_workers", 4), interpolation=interpolation, **kw)
+    return loader, classes
+
+
 def add_image_args(p):
     """--interpolation / --crop_pct on a driver's parser (build_loaders reads them)."""
     p.add_argument("--interpolation", choices=list(INTERPOLATIONS), default="bilinear",

@@ -637,6 +637,72 @@ def logits_topk(logits, k, n_valid=None):
     return probs, index
 
 
+def _knn_dtype(t, what):
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise L.UvcHipError(f"knn_topk: {what} must be float32 or bfloat16, not {t.dtype}")
+    return UVC_F32 if t.dtype == torch.float32 else UVC_BF16
+
+
+def knn_splits(nq, n, k, splits=0):
+    """(workspace bytes, split count used) of ``knn_topk`` for these shapes (uvc_knn_workspace_bytes; ``splits=0``: the host's choice)."""
+    nbytes, used = C.c_int64(0), C.c_int32(0)
+    L.check(L.lib().uvc_knn_workspace_bytes(int(nq), int(n), int(k), int(splits), C.byref(nbytes), C.byref(used)), "uvc_knn_workspace_bytes")
+    return nbytes.value, used.value
+
+
+def knn_topk(queries, bank, k, splits=0, sims=None, idx=None):
+    """(sims float32 [nq, k], idx int32 [nq, k]): the k bank rows most similar to every query by the float32 dot product, descending, equal
+    values by ascending bank row; (-inf, -1) in the slots a bank of fewer than k rows leaves (uvc_knn_topk).  ``queries`` [nq, D] and
+    ``bank`` [n, D]: both bfloat16 or both float32, rows with unit element stride (a row stride above D is taken as the leading dimension).
+    ``splits``: ranges the bank is divided into (0: chosen from the shapes); every value gives the same bits.  ``sims`` / ``idx``:
+    contiguous outputs to write into."""
+    L.require_cuda(queries, bank, sims, idx)
+    if queries.dim() != 2 or bank.dim() != 2 or queries.shape[1] != bank.shape[1]:
+        raise L.UvcHipError("knn_topk: queries [nq, D] and bank [n, D] must share D")
+    for t in (queries, bank):
+        if t.shape[1] > 1 and t.stride(1) != 1:
+            raise L.UvcHipError("knn_topk: rows must have unit element stride")
+    nq, D = queries.shape
+    n, k = bank.shape[0], int(k)
+    dev = queries.device
+    sims = torch.empty(nq, max(k, 0), dtype=torch.float32, device=dev) if sims is None else sims
+    idx = torch.empty(nq, max(k, 0), dtype=torch.int32, device=dev) if idx is None else idx
+    _chk(sims, idx)
+    if sims.dtype != torch.float32 or idx.dtype != torch.int32 or sims.numel() < nq * k or idx.numel() < nq * k:
+        raise L.UvcHipError("knn_topk: sims float32 and idx int32 of at least nq * k elements")
+    a = L.uvc_knn_args()
+    a.queries, a.bank, a.sims, a.idx = L.ptr(queries), L.ptr(bank), L.ptr(sims), L.ptr(idx)
+    a.ldq, a.ldb = (queries.stride(0) if nq > 1 else D), (bank.stride(0) if n > 1 else D)
+    a.nq, a.n, a.D, a.k, a.splits = nq, n, D, k, int(splits)
+    a.q_dtype, a.bank_dtype = _knn_dtype(queries, "queries"), _knn_dtype(bank, "bank")
+    ws = None
+    if 1 <= k <= 64 and nq >= 1 and n >= 1:            # (the call itself refuses the rest, by name)
+        nbytes, _ = knn_splits(nq, n, k, splits)
+        if nbytes:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            a.workspace, a.workspace_bytes = L.ptr(ws), nbytes
+    L.check(L.lib().uvc_knn_topk(C.byref(a), L.cur_stream()), "uvc_knn_topk")
+    return sims, idx
+
+
+def knn_vote(sims, idx, labels, num_classes, temperature=0.07, scores=True):
+    """(scores float32 [nq, num_classes] or None, pred int32 [nq]): the weighted k-NN vote over ``knn_topk``'s lists -- weights
+    exp((s_j - s_0) / temperature), 1 with ``temperature <= 0``; ``labels`` int32 or int64 [n]; the first maximum wins, -1 for a row
+    without a valid neighbour (uvc_knn_vote)."""
+    _chk(sims, idx, labels)
+    if sims.dim() != 2 or sims.shape != idx.shape or sims.dtype != torch.float32 or idx.dtype != torch.int32:
+        raise L.UvcHipError("knn_vote: sims float32 [nq, k] and idx int32 [nq, k]")
+    if labels.dim() != 1 or labels.dtype not in (torch.int32, torch.int64):
+        raise L.UvcHipError("knn_vote: labels must be int32 or int64 [n]")
+    nq, k = sims.shape
+    C_ = int(num_classes)
+    out = torch.empty(nq, max(C_, 0), dtype=torch.float32, device=sims.device) if scores else None
+    pred = torch.empty(nq, dtype=torch.int32, device=sims.device)
+    L.check(L.lib().uvc_knn_vote(L.ptr(sims), L.ptr(idx), L.ptr(labels), int(labels.dtype == torch.int64), nq, labels.shape[0], k, C_,
+                                 float(temperature), L.ptr(out), L.ptr(pred), L.cur_stream()), "uvc_knn_vote")
+    return out, pred
+
+
 def patch_rank(scores, offset=0, descending=True, np=None):
     """int32 [B, np]: the removal order of every image's patches from float32 ``scores`` [B, ld], the patches being columns
     [offset, offset + np) (default np: the rest of the row) -- rank[b, p] patches come before p; larger score first with ``descending``,
