@@ -1,6 +1,6 @@
 """CPU: which kernel uvc_gemm_nt / uvc_gemm_tn select, on both sides of every bound of the rules (no GPU call).
 
-uvc_gemm_nt_route / uvc_gemm_tn_route are the functions the entry points themselves call before they launch (gemm.hip: nt_route, tn_route).  They never
+uvc_gemm_nt_route / uvc_gemm_tn_route are the functions the entry points themselves call before they launch (nt_route in gemm.hip, tn_route in gemm_tn.hip).  They never
 dereference a pointer, so the operands here are fake addresses: non-null, distinct, 16-byte aligned.  Every expectation below is read from the rule
 as DESIGN.md ("GEMM routing") and include/uvc_kernels.h state it, not from a run of the code; tests/golden/gemm_route_pins.json is what the commit
 before the route functions launched on an MI355X (tools/gemm_route_pins.py under rocprofv3 --kernel-trace)."""
@@ -386,18 +386,29 @@ def test_tn_workspace_is_the_larger_of_generic_and_shape_cfg(tn, ops):
 
 # ---------------------------------------------------------------------------------------------------- every route
 def test_route_kernel_names_are_kernel_templates_of_one_gemm_family_file(ops):
-    """Every kernel template is defined in exactly one gemm*.hip (a kernel must not end up in two objects); the families that have a file of their
-    own are not in gemm.hip."""
+    """Every kernel template is defined in exactly one gemm*.hip (a kernel must not end up in two objects), in the file of its family; gemm.hip,
+    the routing, defines no kernel at all."""
     import glob
     from uvc_amd import _lib as L
     defined = {}                                              # kernel template name -> the files that define it
     files = sorted(glob.glob(os.path.join(ROOT, "uvc_amd", "csrc", "gemm*.hip")))
     for path in files:
-        for k in re.findall(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", open(path).read()):
+        text = open(path).read()
+        if os.path.basename(path) == "gemm.hip":
+            assert not re.search(r"__global__\s", text), "gemm.hip defines no __global__ function"
+        for k in re.findall(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", text):
             defined.setdefault(k, []).append(os.path.basename(path))
     assert "gemm.hip" in [os.path.basename(p) for p in files] and len(files) > 1
     assert defined["k_gemm_nt"] == defined["k_gemm_nt_rows"] == ["gemm_nt_tiled.hip"] and defined["k_gemm_ws"] == ["gemm_nt_ws.hip"]
     assert not {k: fs for k, fs in defined.items() if len(fs) != 1}, "a kernel template is defined in exactly one file"
+    assert {k: fs[0] for k, fs in defined.items()} == {
+        "k_gemm_nt": "gemm_nt_tiled.hip", "k_gemm_nt_rows": "gemm_nt_tiled.hip",
+        "k_gemm_ws": "gemm_nt_ws.hip",
+        "k_gemm_wsn": "gemm_nt_wsn.hip", "k_gemm_wsn16": "gemm_nt_wsn.hip", "k_gemm_wsn16_dma": "gemm_nt_wsn.hip",
+        "k_gemm_wsn_lnbwd": "gemm_nt_lnbwd.hip", "k_gemm_wsn_lnbwd_dma": "gemm_nt_lnbwd.hip",
+        "k_gemm_nt256": "gemm_nt_wide.hip", "k_gemm_row384_lnbwd": "gemm_nt_wide.hip", "k_gemm_nt8p": "gemm_nt_wide.hip",
+        "k_gemm_tn": "gemm_tn.hip", "k_gemm_tn_big": "gemm_tn.hip", "k_gemm_tn_dma": "gemm_tn.hip", "k_gemm_tn8p": "gemm_tn.hip", "k_tn_reduce": "gemm_tn.hip",
+    }, "the whole kernel -> file map (the table at the top of gemm_common.h)"
     kernels = set(defined)
     assert len(L.ROUTE_FAMILIES) == 14
     for fam in range(len(L.ROUTE_FAMILIES)):

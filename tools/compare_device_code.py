@@ -1,12 +1,14 @@
 """Compare the gfx950 device code of two builds, kernel by kernel (run by hand after a change that must not touch kernels).
 
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-slp-vectorize -Iinclude --cuda-device-only -c uvc_amd/csrc/gemm.hip -o new.o   (and parent.o)
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-slp-vectorize -Iinclude --cuda-device-only -c uvc_amd/csrc/gemm_tn.hip -o new.o   (and parent.o)
     python tools/compare_device_code.py parent.o new.o > profiles/<name>.txt
 
 Either side may be several objects, the two sides separated by `--` (a file split into several, or the reverse):
 
     for f in uvc_amd/csrc/gemm*.hip; do hipcc <the same flags> --cuda-device-only -c $f -o new_$(basename $f .hip).o; done
-    python tools/compare_device_code.py parent.o -- new_gemm*.o > profiles/<name>.txt
+    python tools/compare_device_code.py parent_*.o -- new_gemm*.o > profiles/<name>.txt
+
+(gemm.hip defines no kernel; its device-only object unbundles to an empty code object and adds nothing to its side.)
 
 A side is the union of its objects' kernels by mangled name; a name that two objects of one side define is an error (a kernel must not end up in
 two objects).  Unbundles the objects, reads the kernel metadata (llvm-readelf --notes) and the symbol table (llvm-readelf -s), and compares for every kernel:

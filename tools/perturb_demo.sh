@@ -2,7 +2,7 @@
 # Shows once that tests/test_streaming_batch_gpu.py (r3) and tests/test_wide_models_gpu.py (r4) go red when a production kernel is wrong.
 #   here (build container):  tools/perturb_demo.sh build     -> tools/perturb/libuvc_hip_{ws,lnbwd,wide,row384,tn8p,row384fwd}.so (git-ignored; they travel with gpurun)
 #   on the GPU box:          tools/perturb_demo.sh run       -> gpurun_out/perturb_demo.txt
-# The perturbed libraries are built from sed-edited COPIES of the file that holds the kernel (gemm_nt_ws.hip for k_gemm_ws, gemm.hip for the others) under /tmp:
+# The perturbed libraries are built from sed-edited COPIES of the file that holds the kernel (gemm_nt_ws.hip for k_gemm_ws, gemm_nt_lnbwd.hip for lnbwd, gemm_nt_wide.hip for wide / row384 / row384fwd, gemm_tn.hip for tn8p) under /tmp:
 # the product source carries no test switch.
 set -u
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -13,13 +13,13 @@ if [ "${1:-}" = build ]; then
   # 1. k_gemm_ws: every output tile of the K <= 192 streaming GEMM (qkv, fc1, dfc2, dproj) scaled by 1.02
   sed 's|\*reinterpret_cast<f32x4\*>(stg + li \* EPW + j \* 16 + gq \* 4) = c;|*reinterpret_cast<f32x4*>(stg + li * EPW + j * 16 + gq * 4) = c * 1.02f;|' "$R/uvc_amd/csrc/gemm_nt_ws.hip" > /tmp/perturb/gemm_ws.hip
   # 2. k_gemm_wsn_lnbwd_dma: dx of the fused dgrad + LayerNorm backward scaled by 1.02
-  sed 's|o\[e\] = rstd \* (c0\[e\] - c1 - xh \* c2);   |o[e] = 1.02f * rstd * (c0[e] - c1 - xh * c2);   |' "$R/uvc_amd/csrc/gemm.hip" > /tmp/perturb/gemm_lnbwd.hip
+  sed 's|o\[e\] = rstd \* (c0\[e\] - c1 - xh \* c2);   |o[e] = 1.02f * rstd * (c0[e] - c1 - xh * c2);   |' "$R/uvc_amd/csrc/gemm_nt_lnbwd.hip" > /tmp/perturb/gemm_lnbwd.hip
   # 3. (r4) the wide-tile NT kernels of DeiT-Small / Base (k_gemm_nt256 and k_gemm_nt8p share NT_EPILOGUE_TILE): staged accumulator x 1.02
-  sed 's|(stg_at<true>(stg, lane \& 15, j \* 4 + (lane >> 4))) = acc\[h\]\[j\];  |(stg_at<true>(stg, lane \& 15, j * 4 + (lane >> 4))) = acc[h][j] * 1.02f;|' "$R/uvc_amd/csrc/gemm.hip" > /tmp/perturb/gemm_wide.hip
+  sed 's|(stg_at<true>(stg, lane \& 15, j \* 4 + (lane >> 4))) = acc\[h\]\[j\];  |(stg_at<true>(stg, lane \& 15, j * 4 + (lane >> 4))) = acc[h][j] * 1.02f;|' "$R/uvc_amd/csrc/gemm_nt_wide.hip" > /tmp/perturb/gemm_wide.hip
   # 4. (r4) k_gemm_row384_lnbwd (D = 384 dgrad + LayerNorm backward on a row tile): dx x 1.02
-  sed 's|o\[e\] = R.rstd \* (gy\[i\]\[e\] - c1 - ((xv\[i\]\[e\] - R.mean) \* R.rstd) \* c2);|o[e] = 1.02f * R.rstd * (gy[i][e] - c1 - ((xv[i][e] - R.mean) * R.rstd) * c2);|' "$R/uvc_amd/csrc/gemm.hip" > /tmp/perturb/gemm_row384.hip
+  sed 's|o\[e\] = R.rstd \* (gy\[i\]\[e\] - c1 - ((xv\[i\]\[e\] - R.mean) \* R.rstd) \* c2);|o[e] = 1.02f * R.rstd * (gy[i][e] - c1 - ((xv[i][e] - R.mean) * R.rstd) * c2);|' "$R/uvc_amd/csrc/gemm_nt_wide.hip" > /tmp/perturb/gemm_row384.hip
   # 5. (r4) k_gemm_tn8p (256 x 256 weight-gradient tiles of DeiT-Base): partial tile x 1.03
-  python3 - "$R/uvc_amd/csrc/gemm.hip" /tmp/perturb/gemm_tn8p.hip <<'PY'
+  python3 - "$R/uvc_amd/csrc/gemm_tn.hip" /tmp/perturb/gemm_tn8p.hip <<'PY'
 import sys
 s = open(sys.argv[1]).read()
 i = s.index("void k_gemm_tn8p(TnArgs g)")
@@ -28,9 +28,11 @@ s = s[:j] + "*reinterpret_cast<f32x4*>(P + (size_t)n1 * g.N2 + n2) = acc[i][j] *
 open(sys.argv[2], "w").write(s)
 PY
   # 6. (r4) k_gemm_row384_lnbwd<.., 1> (D = 384: fc2 / attn.proj + residual + the next LayerNorm in one launch): the GEMM result x 1.02 before bias / residual
-  sed 's|float t = epi_scale_bias(v\[i\]\[e\], 1.0f, bv\[e\]);|float t = epi_scale_bias(v[i][e] * 1.02f, 1.0f, bv[e]);|' "$R/uvc_amd/csrc/gemm.hip" > /tmp/perturb/gemm_row384fwd.hip
+  sed 's|float t = epi_scale_bias(v\[i\]\[e\], 1.0f, bv\[e\]);|float t = epi_scale_bias(v[i][e] * 1.02f, 1.0f, bv[e]);|' "$R/uvc_amd/csrc/gemm_nt_wide.hip" > /tmp/perturb/gemm_row384fwd.hip
   for v in ws lnbwd wide row384 tn8p row384fwd; do
-    src=gemm; [ $v = ws ] && src=gemm_nt_ws      # the file the variant is a copy of: its object is the one the perturbed object replaces
+    case $v in      # the file the variant is a copy of: its object is the one the perturbed object replaces
+      ws) src=gemm_nt_ws ;; lnbwd) src=gemm_nt_lnbwd ;; tn8p) src=gemm_tn ;; *) src=gemm_nt_wide ;;
+    esac
     cmp -s /tmp/perturb/gemm_$v.hip "$R/uvc_amd/csrc/$src.hip" && { echo "perturbation $v did not apply"; exit 1; }
     sed -i 's|#include "gemm_common.h"|#include "'"$R"'/uvc_amd/csrc/gemm_common.h"|' /tmp/perturb/gemm_$v.hip
     /opt/rocm/bin/hipcc $FLAGS -c /tmp/perturb/gemm_$v.hip -o /tmp/perturb/gemm_$v.o || exit 1

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Reads the s_memtime stamps of the instrumented k_gemm_nt8p copy (tools/perturb/libuvc_hip_stamp.so, built from a patched COPY of gemm.hip;
+"""Reads the s_memtime stamps of the instrumented k_gemm_nt8p copy (tools/perturb/libuvc_hip_stamp.so, built from a patched COPY of gemm_nt_wide.hip;
 the product source carries no probe code): per phase [a = before the requests, b = requests issued, c = counted wait done, d = behind the first
 barrier, e = fragments there, f = MFMA block issued]; the next phase's a = behind the second barrier.  Last k-step of workgroup 0, waves 0 and 4.
     UVC_LIB=tools/perturb/libuvc_hip_stamp.so python tools/with_lib.py tools/probe/nt8p_stamps.py [ri]"""

@@ -1,6 +1,6 @@
 #!/bin/bash
 # What bounds the split-M weight-gradient GEMM k_gemm_tn_dma on 128 workgroups (r6): the library built with -DUVC_TN_PROBE=1 (operand ring only), 2 (compute only),
-# 3 (no partial-tile store) from the product source (the switch is a compile-time constant, 0 in the product).  Wrong results on purpose, timing only.
+# 3 (no partial-tile store) from the product source gemm_tn.hip (the switch is a compile-time constant, 0 in the product).  Wrong results on purpose, timing only.
 #   here:            tools/tn_probes.sh build   -> tools/perturb/libuvc_hip_tnprobe{1,2,3}.so
 #   on the GPU box:  tools/tn_probes.sh run     -> gpurun_out/tn_probes.txt
 set -u
@@ -10,8 +10,8 @@ if [ "${1:-}" = build ]; then
   python -m uvc_amd.build > /dev/null || exit 1
   mkdir -p /tmp/perturb "$R/tools/perturb"
   for v in 1 2 3; do
-    /opt/rocm/bin/hipcc $FLAGS -DUVC_TN_PROBE=$v -c "$R/uvc_amd/csrc/gemm.hip" -o /tmp/perturb/gemm_tnprobe$v.o || exit 1
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$R/tools/perturb/libuvc_hip_tnprobe$v.so" $(ls "$R"/uvc_amd/csrc/build/*.o | grep -v '/gemm.o$') /tmp/perturb/gemm_tnprobe$v.o || exit 1
+    /opt/rocm/bin/hipcc $FLAGS -DUVC_TN_PROBE=$v -c "$R/uvc_amd/csrc/gemm_tn.hip" -o /tmp/perturb/gemm_tnprobe$v.o || exit 1
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$R/tools/perturb/libuvc_hip_tnprobe$v.so" $(ls "$R"/uvc_amd/csrc/build/*.o | grep -v '/gemm_tn.o$') /tmp/perturb/gemm_tnprobe$v.o || exit 1
   done
   ls "$R/tools/perturb" | grep tnprobe
   exit 0

@@ -1,9 +1,15 @@
-// What the NT GEMM kernels share across files: MFMA and operand-load traits, the NT kernels' argument block and staged epilogue, the launch macros,
-// and the launchers through which uvc_gemm_nt (gemm.hip) reaches the families that have a file of their own.  No kernel is defined here: a kernel
-// template lives in exactly one gemm*.hip and is instantiated there only.
-//   gemm_nt_tiled.hip   k_gemm_nt, k_gemm_nt_rows    UVC_ROUTE_NT, NT_ROWS
-//   gemm_nt_ws.hip      k_gemm_ws                    UVC_ROUTE_WS, WS384
-//   gemm.hip            every other family, the routing of uvc_gemm_nt, uvc_gemm_tn
+// What the GEMM kernels share across files: MFMA and operand-load traits, the NT kernels' argument block and staged epilogue, the inline-assembly LDS
+// accesses and counted waits of the LDS-DMA kernels, the LayerNorm-backward argument block, the tile sizes the routing reads, the launch macros, and
+// the launchers through which uvc_gemm_nt (gemm.hip) reaches the kernel families.  No kernel is defined here: a kernel template lives in exactly one
+// gemm*.hip and is instantiated there only.  One header, not one per topic: every gemm*.hip includes this one already, and what is shared is a page;
+// a definition is here only when more than one file uses it.
+//   gemm_nt_tiled.hip   k_gemm_nt, k_gemm_nt_rows                           UVC_ROUTE_NT, NT_ROWS
+//   gemm_nt_ws.hip      k_gemm_ws                                           UVC_ROUTE_WS, WS384
+//   gemm_nt_wsn.hip     k_gemm_wsn, k_gemm_wsn16, k_gemm_wsn16_dma          UVC_ROUTE_WSN, WSN16, WSN16_DMA
+//   gemm_nt_lnbwd.hip   k_gemm_wsn_lnbwd, k_gemm_wsn_lnbwd_dma              uvc_gemm_nt_lnbwd at D = 192
+//   gemm_nt_wide.hip    k_gemm_nt256, k_gemm_row384_lnbwd, k_gemm_nt8p      UVC_ROUTE_NT256, ROW384, NT8P; uvc_gemm_nt_lnbwd at D = 384
+//   gemm_tn.hip         k_gemm_tn, _tn_big, _tn_dma, _tn8p, k_tn_reduce     uvc_gemm_tn and its routing
+//   gemm.hip            no kernel: the routing of uvc_gemm_nt, its entry point, the route -> kernel name table
 #pragma once
 #include <type_traits>
 #include "common.h"
@@ -278,8 +284,34 @@ __device__ __forceinline__ void nt_epilogue_rows(const NtArgs& g, float* stg, in
   }
 }
 
+// ---- LDS accesses and waits of the LDS-DMA kernels (the rings of gemm_nt_wsn.hip / gemm_nt_lnbwd.hip, the wide tiles of gemm_nt_wide.hip, gemm_tn.hip).
+//      Inline assembly: for an LDS read it can see, hipcc drains s_waitcnt vmcnt(0) behind an LDS-DMA, which would serialise the stages in flight; the
+//      waits are spelled out by the kernels (k_gemm_wsn_lnbwd_dma's comment has the whole argument).
+__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(LDS_PTR(char))(char*)p; }
+template <int OFF> __device__ __forceinline__ u32x4 ds_read128(unsigned addr) {
+  u32x4 v;
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
+  return v;
+}
+__device__ __forceinline__ void ds_write64_a(unsigned addr, f32x2 v) { asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
+template <int N> __device__ __forceinline__ void wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
+template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+// ---- arguments of the dgrad kernels that end in the LayerNorm backward (uvc_gemm_nt_lnbwd): k_gemm_wsn_lnbwd / _dma (gemm_nt_lnbwd.hip, D = 192) and
+//      k_gemm_row384_lnbwd (gemm_nt_wide.hip, D = 384; its forward MODE reads A, W, M, K only)
+struct LnbArgs {
+  const void* A; const void* W; const void* x; const float* mean; const float* rstd; const float* gamma;
+  const void* add1; const float* a1; const void* add2; const float* a2; void* dx; float* partial;
+  int M, K, want_dots;
+};
+
+// ---- tile sizes the routing of uvc_gemm_nt (gemm.hip) reads, each with the file that owns the kernel
 // the row-panel kernel's largest problem (gemm_nt_tiled.hip), read by uvc_gemm_nt_rows_supported (gemm.hip)
 constexpr int RP_MAX_M = 1024, RP_MAX_K = 1024;
+// k_gemm_nt256's tile (gemm_nt_wide.hip), read by nt256_ok
+constexpr int G2_BM = 256, G2_BN = 256, G2_BK = 64;
+// k_gemm_row384_lnbwd's tile (gemm_nt_wide.hip): R3_BN is the one width it is built for, read by row384_fwd_ok
+constexpr int R3_BM = 128, R3_BN = 384, R3_BK = 64;
 
 // ---- launchers: grid, LDS bytes, launch.  NT_LAUNCH(epi, cases): the launch of the case that is `epi` (nt_route has checked that the family takes it)
 #define NT_LAUNCH(epi, ...) \
@@ -293,11 +325,18 @@ constexpr int RP_MAX_M = 1024, RP_MAX_K = 1024;
 #define NT_BY_TA_TC(F, ...) (r.a_f32 ? (r.c_f32 ? F<float, float>(__VA_ARGS__) : F<float, bf16_t>(__VA_ARGS__)) \
                                      : (r.c_f32 ? F<bf16_t, float>(__VA_ARGS__) : F<bf16_t, bf16_t>(__VA_ARGS__)))
 
-// ---- the launchers of the families that have a file of their own, defined next to their kernels: each picks the instance of the route's operand
-//      types, computes grid and LDS bytes, launches.  Internal to the library (hidden); uvc_gemm_nt (gemm.hip) is their only caller.
+// ---- the launchers of the kernel families, defined next to their kernels: each picks the instance of the route's operand types, computes grid and
+//      LDS bytes, launches.  Internal to the library (hidden); uvc_gemm_nt (gemm.hip) is their only caller, but for launch_row384_lnbwd, which
+//      uvc_gemm_nt_lnbwd (gemm_nt_lnbwd.hip) calls at D = 384.
 namespace uvc_gemm __attribute__((visibility("hidden"))) {
 int launch_nt(const uvc_gemm_route& r, const NtArgs& a, hipStream_t st);            // gemm_nt_tiled.hip
 int launch_nt_rows(const uvc_gemm_route& r, const NtArgs& a, hipStream_t st);
 int launch_ws(const uvc_gemm_route& r, const NtArgs& a, hipStream_t st);            // gemm_nt_ws.hip
 int launch_ws384(const uvc_gemm_route& r, const NtArgs& a, hipStream_t st);
+int launch_wsn(const uvc_gemm_route& r, const NtArgs& a, hipStream_t st);           // gemm_nt_wsn.hip
+int launch_ring(const uvc_gemm_route& r, const NtArgs& a, hipStream_t st);
+int launch_row384_fwd(const NtArgs& a, int epi, hipStream_t st);                    // gemm_nt_wide.hip
+int launch_row384_lnbwd(const LnbArgs& a, int x_lowp, hipStream_t st);
+int launch_nt256(const uvc_gemm_route& r, const NtArgs& a, hipStream_t st);
+int launch_nt8p(const uvc_gemm_route& r, const NtArgs& a, hipStream_t st);
 }  // namespace uvc_gemm
