@@ -464,6 +464,47 @@ int uvc_knn_topk(const uvc_knn_args* args, void* stream);
 int uvc_knn_vote(const float* sims, const int32_t* idx, const void* labels, int32_t labels_i64, int32_t nq, int32_t n, int32_t k,
                  int32_t num_classes, float temperature, float* scores, int32_t* pred, void* stream);
 
+/* Linear probe on a feature bank (python -m uvc_amd.compact_probe): the L2-regularised multinomial logistic objective and its gradient,
+ * what L-BFGS evaluates a few hundred times per fit.  Each call returns UVC_OK or refuses before anything is launched (outputs
+ * untouched); no atomics, one writer per output element in every launch, the same bits on a repeat with the same chunk_rows; every
+ * row offset is 64-bit.
+ *
+ * uvc_softmax_xent_grad: logits float32 [rows, ld] of which columns [0, C) are valid, labels [rows] (int32, or int64 with labels_i64).
+ * Per row, in float32: the maximum of the valid columns, e_c = exp(z_c - max) with the difference carried as an exact two-term sum, their
+ * sum in a fixed tree (a lane's columns ascending, then the xor butterfly), p_c = e_c / sum.  G [rows, ldg] of g_dtype (UVC_BF16: rounded
+ * once; UVC_F32), ldg >= ld: p - 1 at the label (from p = 1/2 up taken as minus the other columns' share of the sum: no cancellation near p = 1) and p
+ * elsewhere, +0 on columns [C, ld) and on every column of a row whose label lies outside [0, C) (an uncounted row: it adds nothing to
+ * loss or hits either); columns [ld, ldg) are not written.  The row's loss term is log1p(sum without the first maximum's 1) - (z_y - max)
+ * and its hit flag 1 when the label is the FIRST maximum of the valid columns.  loss_part float32 / hit_part int32
+ * [uvc_softmax_xent_grad_blocks(rows, ld)]: the sums over the rows of each workgroup in a fixed order.  A row's results depend on that
+ * row alone.  Up to 2048 columns a group of 1 .. 64 lanes holds a row in registers, beyond one workgroup takes a row; 16-byte accesses
+ * when ld % 8 == 0, logits and G are 16-byte aligned and ldg rows are too, element by element otherwise.  1 <= C <= 65536,
+ * C <= ld <= ldg, 1 <= rows < 2^31 (UVC_ERR_ARG).
+ *
+ * uvc_probe_eval: with z = X W^T + b over the m rows whose label lies in [0, C),
+ *   F = (1/m) sum_i (lse(z_i) - z_{i, y_i}) + (l2 / 2) |W|^2,   dW = (1/m) G^T X + l2 W,   db = (1/m) colsum G,   hits = the rows whose label is the
+ * first maximum.  X [n, D] (row stride ldx elements) of dtype (UVC_BF16 or UVC_F32), 16-byte aligned rows; W float32 [Cp, D] and b
+ * float32 [Cp] with Cp = C rounded up to 8 -- the padding rows take no part and get exactly zero gradients, the bias is not regularised;
+ * b and db may both be NULL (no bias).  dW float32 [Cp, D], db float32 [Cp], F float64 [1], counts int64 [2] = (hits, m); m = 0 gives the
+ * l2 terms alone.  W is rounded to dtype once per call; the rows go through in chunks of chunk_rows (clamped to n): uvc_gemm_nt into a
+ * float32 logits buffer, uvc_softmax_xent_grad, uvc_gemm_tn with beta = 1 and the device scalar 1 / m onto dW = l2 W and db = 0; one
+ * workgroup then sums the loss, hit and |W|^2 partials in ascending order in float64.  Different chunk_rows differ by float32 summation
+ * order only.  D a multiple of 8 (UVC_ERR_ARG) up to 1024 (UVC_ERR_UNSUPPORTED), 1 <= C <= 65536, 1 <= n < 2^31, chunk_rows >= 1,
+ * l2 >= 0, workspace >= uvc_probe_workspace_bytes() and 16-byte aligned like X, W and dW (UVC_ERR_ARG). */
+typedef struct uvc_probe_args {
+  const void* X; const void* labels; const float* W; const float* b;
+  float* dW; float* db; double* F; int64_t* counts;
+  void* workspace; int64_t workspace_bytes;
+  int64_t n, ldx;
+  float l2;
+  int32_t D, C, dtype, labels_i64, chunk_rows;
+} uvc_probe_args;
+int uvc_softmax_xent_grad_blocks(int64_t rows, int32_t ld, int64_t* blocks);
+int uvc_softmax_xent_grad(const float* logits, const void* labels, int32_t labels_i64, int64_t rows, int32_t C, int32_t ld, void* G,
+                          int32_t ldg, int32_t g_dtype, float* loss_part, int32_t* hit_part, void* stream);
+int uvc_probe_workspace_bytes(int64_t n, int32_t D, int32_t C, int32_t dtype, int32_t chunk_rows, int64_t* bytes);
+int uvc_probe_eval(const uvc_probe_args* args, void* stream);
+
 /* clip_grad_norm_(max_norm) + AdamW over flat float32 buffers (joint_train.py:428-429;
  * torch.optim.AdamW(lr, betas, eps, weight_decay) semantics, decoupled decay).
  * uvc_grad_sqnorm accumulates sum(g^2) of a segment into sq[0] (accumulate = 0 for the first segment) and leaves sqrt(sq[0]) -- the

@@ -126,6 +126,12 @@ class uvc_adamw_args(C.Structure):
                [("step", C.c_int32), ("flags", C.c_void_p)]
 
 
+class uvc_probe_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("X", "labels", "W", "b", "dW", "db", "F", "counts", "workspace")] + \
+               [(n, C.c_int64) for n in ("workspace_bytes", "n", "ldx")] + [("l2", C.c_float)] + \
+               [(n, C.c_int32) for n in ("D", "C", "dtype", "labels_i64", "chunk_rows")]
+
+
 class uvc_knn_args(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("queries", "bank", "sims", "idx", "workspace")] + \
                [(n, C.c_int64) for n in ("workspace_bytes", "ldq", "ldb")] + \
@@ -240,6 +246,10 @@ _SIGNATURES = {
     "uvc_knn_workspace_bytes": [I32, I32, I32, I32, C.POINTER(I64), C.POINTER(I32)],
     "uvc_knn_topk": [C.POINTER(uvc_knn_args), VP],
     "uvc_knn_vote": [VP, VP, VP, I32, I32, I32, I32, I32, F32, VP, VP, VP],
+    "uvc_softmax_xent_grad_blocks": [I64, I32, C.POINTER(I64)],
+    "uvc_softmax_xent_grad": [VP, VP, I32, I64, I32, I32, VP, I32, I32, VP, VP, VP],
+    "uvc_probe_workspace_bytes": [I64, I32, I32, I32, I32, C.POINTER(I64)],
+    "uvc_probe_eval": [C.POINTER(uvc_probe_args), VP],
     "uvc_grad_sqnorm": [VP, I64, VP, VP, I32, VP],
     "uvc_adamw_step": [C.POINTER(uvc_adamw_args), VP],
     "uvc_scale_by_clip": [VP, I64, VP, F32, VP],

@@ -703,6 +703,99 @@ def knn_vote(sims, idx, labels, num_classes, temperature=0.07, scores=True):
     return out, pred
 
 
+def softmax_xent_grad_blocks(rows, ld) -> int:
+    """The workgroups (loss / hit partials) ``softmax_xent_grad`` uses for ``rows`` rows of ``ld`` columns."""
+    nb = C.c_int64(0)
+    L.check(L.lib().uvc_softmax_xent_grad_blocks(int(rows), int(ld), C.byref(nb)), "uvc_softmax_xent_grad_blocks")
+    return int(nb.value)
+
+
+def softmax_xent_grad(logits, labels, num_classes, G=None, g_dtype=torch.float32, rows=None):
+    """(G [rows, ld] of ``g_dtype``, loss_part float32 [blocks], hit_part int32 [blocks]) of float32 ``logits`` [rows, ld] whose columns
+    [0, num_classes) are valid and int32 / int64 ``labels``: G = softmax - onehot, +0 on the padding columns and on rows whose label lies
+    outside [0, num_classes); the row losses and first-maximum hits summed per workgroup in a fixed order (uvc_softmax_xent_grad).
+    ``G``: an output to write into, rows with unit element stride (its row stride is the leading dimension)."""
+    L.require_cuda(logits, labels, G)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise L.UvcHipError("softmax_xent_grad: logits must be float32 [rows, ld] with unit element stride")
+    if labels.dim() != 1 or labels.dtype not in (torch.int32, torch.int64) or not labels.is_contiguous():
+        raise L.UvcHipError("softmax_xent_grad: labels must be contiguous int32 or int64 [rows]")
+    rows = logits.shape[0] if rows is None else int(rows)
+    ld = logits.stride(0) if logits.shape[0] > 1 else logits.shape[1]
+    if labels.shape[0] < rows or logits.shape[0] < rows:
+        raise L.UvcHipError("softmax_xent_grad: fewer labels or logit rows than rows")
+    if G is None:
+        G = torch.empty(max(rows, 0), ld, dtype=g_dtype, device=logits.device)
+    if G.dim() != 2 or G.dtype not in (torch.float32, torch.bfloat16) or G.shape[0] < rows or G.shape[1] < ld or (G.shape[1] > 1 and G.stride(1) != 1):
+        raise L.UvcHipError("softmax_xent_grad: G must be float32 or bfloat16 [rows, >= ld] with unit element stride")
+    ldg = G.stride(0) if G.shape[0] > 1 else G.shape[1]
+    nb = softmax_xent_grad_blocks(rows, ld) if rows >= 1 and ld >= 1 else 1
+    loss_part = torch.empty(nb, dtype=torch.float32, device=logits.device)
+    hit_part = torch.empty(nb, dtype=torch.int32, device=logits.device)
+    L.check(L.lib().uvc_softmax_xent_grad(L.ptr(logits), L.ptr(labels), int(labels.dtype == torch.int64), rows, int(num_classes), ld, L.ptr(G), ldg,
+                                          UVC_F32 if G.dtype == torch.float32 else UVC_BF16, L.ptr(loss_part), L.ptr(hit_part), L.cur_stream()),
+            "uvc_softmax_xent_grad")
+    return G, loss_part, hit_part
+
+
+PROBE_CHUNK_ROWS = 262144                           # tools/probe_time.py: the fastest of 16 384 / 65 536 / 262 144 / n at both ImageNet shapes
+PROBE_CHUNK_BYTES = 2 << 30                         # and, for wide heads, at most 2 GiB of float32 logits plus G
+
+
+def probe_chunk_rows(n, num_classes, dtype) -> int:
+    """The default ``chunk_rows`` of ``probe_eval``: 262 144 rows, fewer where the chunk's float32 logits plus G would pass 2 GiB (a multiple
+    of 64, at least 64), or n when that is smaller.  Measured, not derived: a chunk sized for the 256 MiB Infinity Cache (11 136 rows at
+    1000 classes) ran 2.0 x slower than this one, its 115 chunks bound by their launches (README "Linear probe")."""
+    Cp = -(-int(num_classes) // 8) * 8
+    rows = min(PROBE_CHUNK_ROWS, PROBE_CHUNK_BYTES // (Cp * (4 + (4 if dtype == UVC_F32 else 2))) // 64 * 64)
+    return max(1, min(int(n), max(rows, 64)))
+
+
+def probe_workspace_bytes(n, D, num_classes, dtype, chunk_rows) -> int:
+    nb = C.c_int64(0)
+    L.check(L.lib().uvc_probe_workspace_bytes(int(n), int(D), int(num_classes), int(dtype), int(chunk_rows), C.byref(nb)), "uvc_probe_workspace_bytes")
+    return int(nb.value)
+
+
+def probe_eval(X, labels, W, b, num_classes, l2, *, chunk_rows=None, dW=None, db=None, F=None, counts=None, workspace=None):
+    """(dW float32 [Cp, D], db float32 [Cp] or None, F float64 [1], counts int64 [2] = (hits, m)), all on the device: the L2-regularised
+    multinomial logistic objective of the head (W, b) on the features ``X`` [n, D] (bfloat16 or float32, unit element stride) and its
+    gradient (uvc_probe_eval).  W float32 [Cp, D] and b float32 [Cp] or None, Cp = num_classes rounded up to 8.  Nothing is synchronised."""
+    L.require_cuda(X, labels, W, b, dW, db, F, counts, workspace)
+    if X.dim() != 2 or X.dtype not in (torch.float32, torch.bfloat16) or (X.shape[1] > 1 and X.stride(1) != 1):
+        raise L.UvcHipError("probe_eval: X must be float32 or bfloat16 [n, D] with unit element stride")
+    if labels.dim() != 1 or labels.dtype not in (torch.int32, torch.int64) or labels.shape[0] != X.shape[0] or not labels.is_contiguous():
+        raise L.UvcHipError("probe_eval: labels must be contiguous int32 or int64 [n]")
+    n, D = X.shape
+    Cc = int(num_classes)
+    Cp = -(-Cc // 8) * 8
+    dtype = UVC_F32 if X.dtype == torch.float32 else UVC_BF16
+    if W.dtype != torch.float32 or tuple(W.shape) != (Cp, D) or not W.is_contiguous():
+        raise L.UvcHipError(f"probe_eval: W must be contiguous float32 [{Cp}, {D}]")
+    if b is not None and (b.dtype != torch.float32 or tuple(b.shape) != (Cp,) or not b.is_contiguous()):
+        raise L.UvcHipError(f"probe_eval: b must be contiguous float32 [{Cp}]")
+    dev = X.device
+    dW = torch.empty(Cp, D, dtype=torch.float32, device=dev) if dW is None else dW
+    db = (torch.empty(Cp, dtype=torch.float32, device=dev) if db is None else db) if b is not None else None
+    F = torch.empty(1, dtype=torch.float64, device=dev) if F is None else F
+    counts = torch.empty(2, dtype=torch.int64, device=dev) if counts is None else counts
+    _chk(dW, db, F, counts)
+    if dW.dtype != torch.float32 or dW.numel() != Cp * D or (db is not None and (db.dtype != torch.float32 or db.numel() != Cp)) or \
+            F.dtype != torch.float64 or F.numel() < 1 or counts.dtype != torch.int64 or counts.numel() < 2:
+        raise L.UvcHipError("probe_eval: dW float32 [Cp, D], db float32 [Cp], F float64 [1], counts int64 [2]")
+    chunk_rows = probe_chunk_rows(n, max(Cc, 1), dtype) if chunk_rows is None else int(chunk_rows)
+    a = L.uvc_probe_args()
+    a.X, a.labels, a.W, a.b, a.dW, a.db, a.F, a.counts = L.ptr(X), L.ptr(labels), L.ptr(W), L.ptr(b), L.ptr(dW), L.ptr(db), L.ptr(F), L.ptr(counts)
+    a.n, a.ldx, a.l2 = n, (X.stride(0) if n > 1 else D), float(l2)
+    a.D, a.C, a.dtype, a.labels_i64, a.chunk_rows = D, Cc, dtype, int(labels.dtype == torch.int64), chunk_rows
+    if workspace is None and n >= 1 and 1 <= Cc <= 65536 and 8 <= D <= 1024 and D % 8 == 0 and chunk_rows >= 1:      # (the call itself refuses the rest, by name)
+        workspace = torch.empty(probe_workspace_bytes(n, D, Cc, dtype, chunk_rows), dtype=torch.uint8, device=dev)
+    if workspace is not None:
+        a.workspace, a.workspace_bytes = L.ptr(workspace), workspace.numel() * workspace.element_size()
+    L.check(L.lib().uvc_probe_eval(C.byref(a), L.cur_stream()), "uvc_probe_eval")
+    return dW, db, F, counts
+
+
 def patch_rank(scores, offset=0, descending=True, np=None):
     """int32 [B, np]: the removal order of every image's patches from float32 ``scores`` [B, ld], the patches being columns
     [offset, offset + np) (default np: the rest of the row) -- rank[b, p] patches come before p; larger score first with ``descending``,
