@@ -505,6 +505,40 @@ int uvc_softmax_xent_grad(const float* logits, const void* labels, int32_t label
 int uvc_probe_workspace_bytes(int64_t n, int32_t D, int32_t C, int32_t dtype, int32_t chunk_rows, int64_t* bytes);
 int uvc_probe_eval(const uvc_probe_args* args, void* stream);
 
+/* Calibration of a logits bank (python -m uvc_amd.compact_calibrate): temperature and vector scaling are the affine map
+ * z'_c = scale_c z_c + shift_c of the logits (scale_len = 1: one scale for every class, s = 1/T; scale_len = C: one per class; shift
+ * float32 [C] or NULL).  logits float32 [n, ld] of which columns [0, C) are valid (the rest is never read into a result), labels [n]
+ * (int32, or int64 with labels_i64); only the m rows whose label lies in [0, C) count.  With p = softmax(z') over the valid columns and
+ * g_ic = p_ic - [c = y_i]:
+ *
+ * uvc_calib_eval:  F float64 [1] = (1/m) sum_i (lse(z'_i) - z'_{i, y_i});  dscale float32 [scale_len]: (1/m) sum_i g_ic z_ic (scale_len = 1:
+ * its sum over c);  dshift float32 [C] = (1/m) sum_i g_ic, not touched when shift is NULL (and required with a shift);  counts int64 [2] =
+ * (the rows whose label is the FIRST maximum of z', m).  m = 0 gives zeros.
+ * uvc_calib_stats: per counted row conf = max_c p_c, pred = the first maximum, bin = clamp(ceil(conf bins) - 1, 0, bins - 1) (the intervals
+ * ((j - 1) / bins, j / bins]); bin_count int64 / bin_conf float64 (the sum of conf) / bin_hit int64 (pred = label), each [bins];
+ * sums float64 [2] = (sum_i -log p_{i, y_i}, sum_i (sum_c p_ic^2 - 2 p_{i, y_i} + 1)); counts int64 [2] = (hits, m).  1 <= bins <= 64.
+ *
+ * One pass over the logits, nothing of size [n, C] is written: workgroup w owns the rows [w R, (w + 1) R), R and the workgroup count
+ * uvc_calib_blocks(n, ld) functions of (n, ld) alone -- not of the device --, and leaves one partial; a second launch adds the partials in
+ * ascending workgroup order in float64 and divides by m.  z' is one float64 fma of the float32 inputs and z' - max is rounded to float32
+ * once; the rest of a row is float32 in fixed trees (calib.hip).  A row's contribution does not depend on the rows beside it.  No atomics,
+ * one writer per element in every launch, the same bits on a repeat; 64-bit row offsets; 16-byte loads when ld % 4 == 0 and logits is
+ * 16-byte aligned, element by element otherwise; up to 2048 classes a row is read once, beyond it is read three times (twice from cache).
+ * 1 <= n < 2^31, 1 <= C <= ld < 2^31, scale_len 1 or C, workspace >= uvc_calib_workspace_bytes(n, ld, C, bins; bins = 0: uvc_calib_eval) and
+ * 16-byte aligned (UVC_ERR_ARG); C <= 65536 (UVC_ERR_UNSUPPORTED).  Every refusal happens before anything is launched. */
+typedef struct uvc_calib_args {
+  const float* logits; const void* labels; const float* scale; const float* shift;
+  double* F; float* dscale; float* dshift; int64_t* counts;
+  int64_t* bin_count; double* bin_conf; int64_t* bin_hit; double* sums;
+  void* workspace; int64_t workspace_bytes;
+  int64_t n, ld;
+  int32_t C, scale_len, labels_i64, bins;
+} uvc_calib_args;
+int uvc_calib_blocks(int64_t n, int32_t ld, int64_t* blocks);
+int uvc_calib_workspace_bytes(int64_t n, int32_t ld, int32_t C, int32_t bins, int64_t* bytes);
+int uvc_calib_eval(const uvc_calib_args* args, void* stream);
+int uvc_calib_stats(const uvc_calib_args* args, void* stream);
+
 /* clip_grad_norm_(max_norm) + AdamW over flat float32 buffers (joint_train.py:428-429;
  * torch.optim.AdamW(lr, betas, eps, weight_decay) semantics, decoupled decay).
  * uvc_grad_sqnorm accumulates sum(g^2) of a segment into sq[0] (accumulate = 0 for the first segment) and leaves sqrt(sq[0]) -- the

@@ -132,6 +132,12 @@ class uvc_probe_args(C.Structure):
                [(n, C.c_int32) for n in ("D", "C", "dtype", "labels_i64", "chunk_rows")]
 
 
+class uvc_calib_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("logits", "labels", "scale", "shift", "F", "dscale", "dshift", "counts", "bin_count", "bin_conf", "bin_hit",
+                                          "sums", "workspace")] + \
+               [(n, C.c_int64) for n in ("workspace_bytes", "n", "ld")] + [(n, C.c_int32) for n in ("C", "scale_len", "labels_i64", "bins")]
+
+
 class uvc_knn_args(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("queries", "bank", "sims", "idx", "workspace")] + \
                [(n, C.c_int64) for n in ("workspace_bytes", "ldq", "ldb")] + \
@@ -250,6 +256,10 @@ _SIGNATURES = {
     "uvc_softmax_xent_grad": [VP, VP, I32, I64, I32, I32, VP, I32, I32, VP, VP, VP],
     "uvc_probe_workspace_bytes": [I64, I32, I32, I32, I32, C.POINTER(I64)],
     "uvc_probe_eval": [C.POINTER(uvc_probe_args), VP],
+    "uvc_calib_blocks": [I64, I32, C.POINTER(I64)],
+    "uvc_calib_workspace_bytes": [I64, I32, I32, I32, C.POINTER(I64)],
+    "uvc_calib_eval": [C.POINTER(uvc_calib_args), VP],
+    "uvc_calib_stats": [C.POINTER(uvc_calib_args), VP],
     "uvc_grad_sqnorm": [VP, I64, VP, VP, I32, VP],
     "uvc_adamw_step": [C.POINTER(uvc_adamw_args), VP],
     "uvc_scale_by_clip": [VP, I64, VP, F32, VP],

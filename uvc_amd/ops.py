@@ -796,6 +796,80 @@ def probe_eval(X, labels, W, b, num_classes, l2, *, chunk_rows=None, dW=None, db
     return dW, db, F, counts
 
 
+def calib_blocks(n, ld) -> int:
+    """The workgroups (partials) ``calib_eval`` and ``calib_stats`` use for ``n`` rows of stride ``ld``: a function of the two alone."""
+    nb = C.c_int64(0)
+    L.check(L.lib().uvc_calib_blocks(int(n), int(ld), C.byref(nb)), "uvc_calib_blocks")
+    return int(nb.value)
+
+
+def calib_workspace_bytes(n, ld, num_classes, bins=0) -> int:
+    """The workspace of ``calib_eval`` (``bins`` = 0) or ``calib_stats``."""
+    nb = C.c_int64(0)
+    L.check(L.lib().uvc_calib_workspace_bytes(int(n), int(ld), int(num_classes), int(bins), C.byref(nb)), "uvc_calib_workspace_bytes")
+    return int(nb.value)
+
+
+def _calib_args(what, logits, labels, scale, shift, num_classes, bins, workspace):
+    L.require_cuda(logits, labels, scale, shift, workspace)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise L.UvcHipError(f"{what}: logits must be float32 [n, ld] with unit element stride")
+    if labels.dim() != 1 or labels.dtype not in (torch.int32, torch.int64) or labels.shape[0] != logits.shape[0] or not labels.is_contiguous():
+        raise L.UvcHipError(f"{what}: labels must be contiguous int32 or int64 [n]")
+    n = logits.shape[0]
+    ld = logits.stride(0) if n > 1 else logits.shape[1]
+    Cc = logits.shape[1] if num_classes is None else int(num_classes)
+    if Cc > logits.shape[1]:
+        raise L.UvcHipError(f"{what}: num_classes {Cc} is more than the logits' {logits.shape[1]} columns")
+    if scale.dtype != torch.float32 or scale.dim() != 1 or not scale.is_contiguous() or \
+            (shift is not None and (shift.dtype != torch.float32 or tuple(shift.shape) != (Cc,) or not shift.is_contiguous())):
+        raise L.UvcHipError(f"{what}: scale must be contiguous float32 [1] or [{Cc}] and shift float32 [{Cc}] or None")
+    a = L.uvc_calib_args()
+    a.logits, a.labels, a.scale, a.shift = L.ptr(logits), L.ptr(labels), L.ptr(scale), L.ptr(shift)
+    a.n, a.ld, a.C, a.scale_len, a.labels_i64, a.bins = n, ld, Cc, scale.numel(), int(labels.dtype == torch.int64), int(bins)
+    if workspace is None and n >= 1 and 1 <= Cc <= 65536 and (what == "calib_eval" or 1 <= bins <= 64):      # (the call itself refuses the rest, by name)
+        workspace = torch.empty(calib_workspace_bytes(n, ld, Cc, bins), dtype=torch.uint8, device=logits.device)
+    if workspace is not None:
+        a.workspace, a.workspace_bytes = L.ptr(workspace), workspace.numel() * workspace.element_size()
+    return a, Cc, workspace
+
+
+def calib_eval(logits, labels, scale, shift=None, num_classes=None, *, F=None, dscale=None, dshift=None, counts=None, workspace=None):
+    """(F float64 [1], dscale float32 like ``scale``, dshift float32 [C] or None, counts int64 [2] = (hits, m)), all on the device: the mean
+    negative log-likelihood of ``z' = scale * z + shift`` over the rows whose label lies in [0, C), and its gradient in ``scale`` (float32 [1]:
+    temperature scaling, s = 1/T; [C]: vector scaling) and ``shift`` (float32 [C] or None) -- one pass over the float32 ``logits`` [n, ld] whose
+    columns [0, num_classes) are valid (default: all), nothing of their size is written (uvc_calib_eval).  Nothing is synchronised."""
+    a, Cc, workspace = _calib_args("calib_eval", logits, labels, scale, shift, num_classes, 0, workspace)
+    dev = logits.device
+    F = torch.empty(1, dtype=torch.float64, device=dev) if F is None else F
+    dscale = torch.empty_like(scale) if dscale is None else dscale
+    if dshift is None and shift is not None:                         # (a dshift handed in without a shift is left untouched)
+        dshift = torch.empty(Cc, dtype=torch.float32, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev) if counts is None else counts
+    _chk(F, dscale, dshift, counts)
+    if F.dtype != torch.float64 or F.numel() < 1 or dscale.dtype != torch.float32 or dscale.numel() != scale.numel() or counts.dtype != torch.int64 or \
+            counts.numel() < 2 or (dshift is not None and (dshift.dtype != torch.float32 or dshift.numel() != Cc)):
+        raise L.UvcHipError("calib_eval: F float64 [1], dscale float32 like scale, dshift float32 [C], counts int64 [2]")
+    a.F, a.dscale, a.dshift, a.counts = L.ptr(F), L.ptr(dscale), L.ptr(dshift), L.ptr(counts)
+    L.check(L.lib().uvc_calib_eval(C.byref(a), L.cur_stream()), "uvc_calib_eval")
+    return F, dscale, dshift, counts
+
+
+def calib_stats(logits, labels, scale, shift=None, num_classes=None, bins=15, *, workspace=None):
+    """(bin_count int64 [bins], bin_conf float64 [bins], bin_hit int64 [bins], sums float64 [2] = (nll, Brier) sums, counts int64 [2] =
+    (hits, m)), all on the device: the reliability histogram of ``softmax(scale * z + shift)`` over the rows whose label lies in [0, C) --
+    confidence = the largest probability, bins ((j - 1) / bins, j / bins] (uvc_calib_stats).  Operands as ``calib_eval`` takes them."""
+    a, Cc, workspace = _calib_args("calib_stats", logits, labels, scale, shift, num_classes, bins, workspace)
+    dev = logits.device
+    nb = max(int(bins), 1)
+    bin_count, bin_hit = torch.empty(nb, dtype=torch.int64, device=dev), torch.empty(nb, dtype=torch.int64, device=dev)
+    bin_conf, sums = torch.empty(nb, dtype=torch.float64, device=dev), torch.empty(2, dtype=torch.float64, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    a.bin_count, a.bin_conf, a.bin_hit, a.sums, a.counts = L.ptr(bin_count), L.ptr(bin_conf), L.ptr(bin_hit), L.ptr(sums), L.ptr(counts)
+    L.check(L.lib().uvc_calib_stats(C.byref(a), L.cur_stream()), "uvc_calib_stats")
+    return bin_count, bin_conf, bin_hit, sums, counts
+
+
 def patch_rank(scores, offset=0, descending=True, np=None):
     """int32 [B, np]: the removal order of every image's patches from float32 ``scores`` [B, ld], the patches being columns
     [offset, offset + np) (default np: the rest of the row) -- rank[b, p] patches come before p; larger score first with ``descending``,
