@@ -618,7 +618,11 @@ int uvc_cast_transpose(const float* W, int32_t R, int32_t C, void* w_bf16, void*
 int uvc_cast_transpose_multi(const float* params, void* shadow, int32_t n, const int64_t* srcs, const int32_t* Rs, const int32_t* Cs,
                              const int64_t* ws, const int64_t* wts, int32_t dtype, void* stream);
 /* Keyed Exp(1) noise for the Gumbel draws (model_distilled.py:40,485; uvc_utils.py:443-449): out[i] is a pure function of
- * (seed, step, site, i) -- counter-based, no generator state, identical on every data-parallel replica and after a resume. */
+ * (seed, step, site, i) -- counter-based, no generator state, identical on every data-parallel replica and after a resume.
+ * out[i] = -logf(u), u = min(float32(c + 1/2) * 2^-24, 1 - 2^-24) for the 24-bit counter c = splitmix64(key ^ splitmix64(i)) >> 40
+ * (24-bit resolution below u = 1/2, 23-bit above: c + 1/2 rounds to even from c = 2^23 up).  Every draw is finite and strictly
+ * positive: the largest is 25 ln 2 = 17.3287 (c = 0), the smallest -logf(1 - 2^-24) = 2^-24 = 5.9604645e-08 (c = 2^24 - 1, the one
+ * counter the min() changes: unclamped it gave u = 1 and a draw of -0, whose Gumbel value -log(E) is +inf).  Refuses n <= 0. */
 int uvc_exp_noise(float* out, int64_t n, uint64_t seed, uint64_t step, uint32_t site, void* stream);
 
 /* block-gate distributions (model_distilled.py:480-488): d[L,2] from g[L,2] and Exp(1) draws. */

@@ -764,7 +764,12 @@ extern "C" int uvc_cast_transpose_multi(const float* params, void* shadow, int32
 // draw (seed, step, site) is a pure function of those four numbers (splitmix64 finaliser over a 64-bit key/counter mix), so
 // data-parallel replicas produce identical noise without sharing -- or being able to desynchronise -- a stateful global RNG
 // (the reference relies on identically seeded torch generators, joint_train.py:191-196, and breaks that itself by sampling the
-// FLOPs report on rank 0 only, :509), and a resumed run needs no RNG state.  E = -log(U), U uniform on (0, 1) with 24 bits.
+// FLOPs report on rank 0 only, :509), and a resumed run needs no RNG state.  E = -log(U), U = (c + 1/2) 2^-24 rounded to float32
+// from the 24-bit counter c = h >> 40: every c < 2^23 has its own U (smallest 2^-25: the largest draw, 17.3287); from 2^23 up the
+// sum c + 1/2 is no float32 and rounds to the even neighbour, so an odd c shares the U of c + 1 (ties to even) and the upper half
+// of (0, 1) has 23-bit resolution.  c = 2^24 - 1 would round to U = 1 and draw -0.0f, whose Gumbel value -log(E) is +inf (NaN in
+// every softmax that takes it): that one U is clamped to 1 - 2^-24, the smallest draw, 2^-24 = 5.9604645e-08 (Gumbel value 16.6355).  No
+// other draw is touched by the clamp, so recorded (seed, step, site) keys replay bit for bit.
 __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -775,7 +780,7 @@ __global__ __launch_bounds__(256) void k_exp_noise(float* __restrict__ out, int6
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const uint64_t h = splitmix64(key ^ splitmix64((uint64_t)i));
     const float u = ((float)(uint32_t)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);
-    out[i] = -logf(u);
+    out[i] = -logf(fminf(u, 0x1.fffffep-1f));
   }
 }
 extern "C" int uvc_exp_noise(float* out, int64_t n, uint64_t seed, uint64_t step, uint32_t site, void* stream) {
