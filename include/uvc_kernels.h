@@ -429,6 +429,34 @@ int uvc_ig_accumulate(const float* d_rows, float* acc, int64_t n, int32_t count,
 int uvc_pixel_maps(const float* a, const void* x, const void* x0, float scale, int32_t B, int32_t C, int32_t S, int32_t P, int32_t dtype,
                    float* pixel, float* patch, float* total, float* partial, void* stream);
 
+/* Adversarial robustness of compact models (python -m uvc_amd.compact_robust): L-infinity FGSM and PGD (Goodfellow et al. 2015; Madry et
+ * al. 2018) around uvc_vit_compact_loss_grad of uvc_vit.h.  Each call returns UVC_OK or refuses before anything is launched (outputs
+ * untouched); no atomics, one writer per output element, fixed reduction trees: the same bits on a repeat and in any batch.
+ *
+ * uvc_loss_seed: the per-image attack loss and its gradient at the head outputs.  lg float32 [B, ld], lgd the same or NULL, labels int32
+ * [B]; the eval logits are z = lg, or (lg + lgd) / 2 with lgd, over columns [0, n_valid), 1 <= n_valid <= ld.  A label is clamped into
+ * [0, n_valid) on the device: callers check it on the host.  kind 0, cross-entropy: L = lse(z) - z_y, dz = softmax(z) - onehot(y), float32
+ * arithmetic with the row maximum subtracted and uvc_logits_topk's reduction trees (a wave butterfly, then the waves in order); the mean of
+ * the two heads and a logit's distance from the maximum are carried as exact float32 pairs (exp to second order in the small part) and the sum
+ * of the exponentials is compensated,
+ * so dz is within 4 float32 spacings of max(p, 2^-24) of the float64 value on the same float32 logits.  kind 1, margin: L = z_j - z_y,
+ * dz = onehot(j) - onehot(y), j the FIRST maximum of the exact z over c != y; needs n_valid >= 2 (UVC_ERR_ARG).  dl = dz without lgd
+ * (dld is not touched and may be NULL), dl = dld = dz / 2 with it; exact +0 in columns [n_valid, ld), which are never read.  loss float32
+ * [B], or NULL.  One workgroup per image.
+ *
+ * uvc_pgd_step: one projected step on patch rows (uvc_patchify's layout, K0 = C * P * P, the channel of column k is k / (P * P)).
+ * x (the iterate), x0 (the clean rows), dir and out float32 [rows, K0]; step, eps, lo, hi HOST float32 [C], C <= 4, eps >= 0, lo <= hi.
+ * mode 0: d = (dir > 0) - (dir < 0) (a NaN or a zero of either sign gives 0); mode 1: d = dir (the random start: dir uniform in [-1, 1),
+ * step = eps).  v = min(max(x + step_c * d, max(x0 - eps_c, lo_c)), min(x0 + eps_c, hi_c)), every operation a separate float32 operation
+ * rounded once, min / max as torch.minimum / torch.maximum take them (a NaN operand is the result): the bits of that statement in
+ * float32 PyTorch.  out = v and may be x itself; out_t T [rows, K0] (dtype UVC_F32 / UVC_BF16), or NULL: v rounded once to T, the rows the
+ * next forward reads, made in the same pass.  Every element is read once; 16-byte loads and stores where P * P is a multiple of 4 (of 8
+ * for the 16-byte bf16 store, else 8 bytes) and every pointer is aligned, element by element otherwise; offsets are 64-bit. */
+int uvc_loss_seed(const float* lg, const float* lgd, const int32_t* labels, int32_t B, int32_t ld, int32_t n_valid, int32_t kind, float* dl,
+                  float* dld, float* loss, void* stream);
+int uvc_pgd_step(const float* x, const float* x0, const float* dir, int64_t rows, int32_t P, int32_t C, const float* step, const float* eps,
+                 const float* lo, const float* hi, int32_t mode, float* out, void* out_t, int32_t dtype, void* stream);
+
 /* Nearest neighbours in a feature bank and the weighted k-NN vote (python -m uvc_amd.compact_transfer; Wu et al. 2018, DINO's
  * knn_classifier).  Each call returns UVC_OK or refuses before anything is launched (outputs untouched); no atomics, every output
  * element has one writer, the same bits on a repeat.

@@ -262,6 +262,17 @@ int64_t uvc_vit_compact_input_grad_workspace_bytes(const uvc_vit_cfg* cfg, const
 int uvc_vit_compact_input_grad(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, const int32_t* target,
                                int32_t num_labels, float* d_rows, int32_t* target_out, void* stream);
 
+/* The gradient of a per-image attack LOSS with respect to the input, as patch rows: what FGSM and PGD (python -m uvc_amd.compact_robust) step
+ * along.  uvc_vit_compact_input_grad with the one-hot seed replaced by uvc_loss_seed of uvc_kernels.h (the same kernel): kind 0 cross-entropy,
+ * dz = softmax(z) - onehot(label); kind 1 margin, dz = onehot(j) - onehot(label), j the first maximum among the other labels (num_labels >= 2,
+ * otherwise UVC_ERR_ARG).  The same workspace (uvc_vit_compact_input_grad_workspace_bytes), the same transposed copy of the patch weight, the
+ * same dgrad walk.  labels: device int32 [B], clamped into [0, num_labels) by the kernel -- callers check them on the host.  d_rows float32
+ * [B * np, K0] = dL_b / d rows of image b's OWN loss (not the batch mean): a batch's rows do not depend on its neighbours.  loss_out: device
+ * float32 [B], or NULL.  io as for uvc_vit_compact_input_grad (x or patches_in; logits / logits_dist are the eval forward's bits).  Every
+ * refusal comes before anything is launched.  One stream, deterministic. */
+int uvc_vit_compact_loss_grad(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, const int32_t* labels,
+                              int32_t num_labels, int32_t kind, float* d_rows, float* loss_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -249,6 +249,8 @@ _SIGNATURES = {
     "uvc_ig_rows": [VP, VP, VP, I64, I32, I32, I32, I32, I32, VP],
     "uvc_ig_accumulate": [VP, VP, I64, I32, I32, VP],
     "uvc_pixel_maps": [VP, VP, VP, F32, I32, I32, I32, I32, I32, VP, VP, VP, VP, VP],
+    "uvc_loss_seed": [VP, VP, VP, I32, I32, I32, I32, VP, VP, VP, VP],
+    "uvc_pgd_step": [VP, VP, VP, I64, I32, I32, VP, VP, VP, VP, I32, VP, VP, I32, VP],
     "uvc_knn_workspace_bytes": [I32, I32, I32, I32, C.POINTER(I64), C.POINTER(I32)],
     "uvc_knn_topk": [C.POINTER(uvc_knn_args), VP],
     "uvc_knn_vote": [VP, VP, VP, I32, I32, I32, I32, I32, F32, VP, VP, VP],
@@ -317,6 +319,7 @@ VIT_SYMBOLS = ["uvc_vit_layout", "uvc_vit_workspace_bytes", "uvc_vit_ws_offsets"
                "uvc_vit_compact_rollout_workspace_bytes", "uvc_vit_compact_rollout",   # (attention rollout maps: uvc_amd/compact.py)
                "uvc_vit_compact_attribution_workspace_bytes", "uvc_vit_compact_attribution",   # (uvc_amd/compact_attribution.py)
                "uvc_vit_compact_input_grad_workspace_bytes", "uvc_vit_compact_input_grad",   # (input gradients: uvc_amd/compact_pixel.py)
+               "uvc_vit_compact_loss_grad",   # (the gradient of an attack loss: uvc_amd/compact_robust.py)
                "uvc_vit_compact_features"]   # (features for k-NN and re-heading: uvc_amd/compact_transfer.py)
 
 

@@ -23,8 +23,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-Wno-unused-value", "-Wno-unused-result",
           "-I" + os.path.join(os.path.dirname(HERE), "include")]
 # the scalar primal-dual update must round like the reference's separate float32 ops; the image resampling coefficients
-# must round like PIL's float64 C (include/uvc_data.h)
-PER_FILE = {"uvc_engine.hip": ["-ffp-contract=off"], "image_prep.hip": ["-ffp-contract=off"]}
+# must round like PIL's float64 C (include/uvc_data.h); the projected step of an attack must be the float32 PyTorch statement, x + step * d
+# as a product and a sum (the __fmul_rn / __fadd_rn of this toolchain are plain operators, which contraction fuses)
+PER_FILE = {"uvc_engine.hip": ["-ffp-contract=off"], "image_prep.hip": ["-ffp-contract=off"], "robust.hip": ["-ffp-contract=off"]}
 
 
 def _sources():

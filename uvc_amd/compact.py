@@ -419,6 +419,7 @@ def _bind():
         for n in ("layout", "workspace_bytes", "update_shadows"):
             tails["train_" + n] = tails[n]
         tails["input_grad"] = tails["attribution"]
+        tails["loss_grad"] = [C.POINTER(uvc_vit_io), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         tails["features"] = [C.POINTER(uvc_vit_io), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         tails["rollout_workspace_bytes"] = tails["attribution_workspace_bytes"] = tails["input_grad_workspace_bytes"] = tails["workspace_bytes"]
         for n, tail in tails.items():

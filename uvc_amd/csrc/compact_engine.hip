@@ -9,7 +9,8 @@
 // per attention block, then one uvc_attention_rollout_step per such block, last block first.  uvc_vit_compact_attribution is the training forward,
 // a target pick, and the same backward walk without any parameter gradient, with one uvc_attention_relevance_step per attention block.
 // uvc_vit_compact_input_grad is that forward and target pick, the dgrad walk through every block, the masked row copy of token assembly's
-// backward and the patch-embedding dgrad: the gradient of the class logit at the input, as patch rows.
+// backward and the patch-embedding dgrad: the gradient of the class logit at the input, as patch rows.  uvc_vit_compact_loss_grad is the same
+// with the seed of an attack loss (uvc_loss_seed, robust.hip) in the target pick's place.
 #include "engine_host.h"
 
 namespace {
@@ -746,6 +747,27 @@ extern "C" int uvc_vit_compact_input_grad(const uvc_vit_cfg* cfg, const uvc_comp
                                                                  target_out);
   UVC_CHECK_LAUNCH();
   // W_patch^T in the operand type: the pinned shadow layouts hold no such copy, so it is made per call (K0 D elements beside the pass's GEMMs)
+  uvc_vit_offsets o;
+  TRY(uvc_vit_compact_layout(cfg, blocks, nblocks, &o, nullptr));
+  TRY(uvc_cast_transpose(io->params + o.patch_w, d.D, d.K0, nullptr, c.w.wpt, d.dtype, stream));
+  return backward_walk(c, cfg, blocks, nblocks, c.w.dl[0], c.w.dl[1], nullptr, nullptr, nullptr, d_rows);
+}
+
+// ---- the gradient of an attack loss at the input (FGSM, PGD) ------------------------------------------------------------------------------
+// uvc_vit_compact_input_grad with uvc_loss_seed (robust.hip) in k_attrib_target's place: the same workspace, weight copy and walk.
+extern "C" int uvc_vit_compact_loss_grad(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, const int32_t* labels,
+                                         int32_t num_labels, int32_t kind, float* d_rows, float* loss_out, void* stream) {
+  if (!d_rows || !labels) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_loss_grad: null d_rows or labels");
+  Ctx c;
+  TRY(setup_train(c, cfg, blocks, nblocks, io, stream, CARVE_INPUT));
+  if ((!io->x && !io->patches_in) || !io->logits || (cfg->ntok == 2 && !io->logits_dist))
+    return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_loss_grad: null io member");
+  const CDims& d = c.d;
+  if (num_labels < 1 || num_labels > d.NC) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_loss_grad: num_labels must lie in [1, num_classes]");
+  if (kind != 0 && kind != 1) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_loss_grad: kind is 0 (cross-entropy) or 1 (margin)");
+  if (kind == 1 && num_labels < 2) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_loss_grad: the margin loss needs num_labels >= 2");
+  TRY(forward(c, cfg, blocks, nblocks, 1));
+  TRY(uvc_loss_seed(io->logits, d.ntok == 2 ? io->logits_dist : nullptr, labels, d.B, d.NC, num_labels, kind, c.w.dl[0], c.w.dl[1], loss_out, stream));
   uvc_vit_offsets o;
   TRY(uvc_vit_compact_layout(cfg, blocks, nblocks, &o, nullptr));
   TRY(uvc_cast_transpose(io->params + o.patch_w, d.D, d.K0, nullptr, c.w.wpt, d.dtype, stream));

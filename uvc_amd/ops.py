@@ -1005,6 +1005,70 @@ def pixel_maps(a, C, S, P, x=None, x0=None, scale=1.0):
     return pixel, patch, total
 
 
+LOSS_KINDS = ("ce", "margin")                       # uvc_loss_seed's kind 0 / 1
+
+
+def loss_seed(logits, labels, n_valid=None, kind="ce", logits_dist=None, dl=None, dld=None, want_loss=True):
+    """``(dl, dld or None, loss float32 [B] or None)`` of float32 ``logits`` [B, ld] (and ``logits_dist``: the eval logits are their mean)
+    and int32 ``labels`` [B] on the device: the attack loss ``kind`` ("ce": lse(z) - z_y; "margin": z_j - z_y, j the first maximum among the
+    other labels) over columns [0, n_valid) and its gradient at the head outputs -- dz, or dz / 2 on both heads (uvc_loss_seed)."""
+    _chk(logits, logits_dist, labels, dl, dld)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or (logits_dist is not None and (logits_dist.dtype != torch.float32 or logits_dist.shape != logits.shape)):
+        raise L.UvcHipError("loss_seed: logits (and logits_dist) must be float32 [B, ld]")
+    B, ld = logits.shape
+    if labels.dtype != torch.int32 or tuple(labels.shape) != (B,):
+        raise L.UvcHipError("loss_seed: labels must be int32 [B]")
+    if kind not in LOSS_KINDS:
+        raise L.UvcHipError(f"loss_seed: kind must be one of {LOSS_KINDS}")
+    n_valid = ld if n_valid is None else int(n_valid)
+    if dl is None:
+        dl = torch.empty_like(logits)
+    if dld is None and logits_dist is not None:
+        dld = torch.empty_like(logits)
+    for t in (dl, dld):
+        if t is not None and (t.dtype != torch.float32 or t.shape != logits.shape):
+            raise L.UvcHipError("loss_seed: dl / dld must be float32 [B, ld]")
+    loss = torch.empty(B, dtype=torch.float32, device=logits.device) if want_loss else None
+    L.check(L.lib().uvc_loss_seed(L.ptr(logits), L.ptr(logits_dist), L.ptr(labels), B, ld, n_valid, LOSS_KINDS.index(kind), L.ptr(dl),
+                                  L.ptr(dld if logits_dist is not None else None), L.ptr(loss), L.cur_stream()), "uvc_loss_seed")
+    return dl, (dld if logits_dist is not None else None), loss
+
+
+def _channel_floats(v, Cc, what):
+    import ctypes as C
+    v = [float(u) for u in (v.tolist() if hasattr(v, "tolist") else v)]
+    if len(v) != Cc:
+        raise L.UvcHipError(f"pgd_step: {what} must hold one value per channel ({Cc})")
+    return (C.c_float * Cc)(*v)
+
+
+def pgd_step(x, x0, direction, P, step, eps, lo, hi, mode=0, out=None, out_t=None):
+    """``out`` float32 [rows, K0]: one projected step on float32 patch rows (``patchify``'s layout) --
+    ``min(max(x + step_c d, max(x0 - eps_c, lo_c)), min(x0 + eps_c, hi_c))`` with ``d = sign(direction)`` (``mode`` 0; NaN and zeros give 0) or
+    ``d = direction`` (``mode`` 1), every operation a float32 operation rounded once; ``step``, ``eps``, ``lo``, ``hi``: one float per channel
+    on the host.  ``out`` may be ``x`` (default: a new tensor); ``out_t`` (float32 or bfloat16 [rows, K0]): the same values rounded once to its
+    type, written in the same pass (uvc_pgd_step)."""
+    _chk(x, x0, direction, out, out_t)
+    P = int(P)
+    if x.dim() != 2 or x.dtype != torch.float32 or P < 1 or x.shape[1] % (P * P) or x.shape[0] == 0:
+        raise L.UvcHipError("pgd_step: x must be float32 [rows, C * P * P]")
+    Cc = x.shape[1] // (P * P)
+    if out is None:
+        out = torch.empty_like(x)
+    for t in (x0, direction, out):
+        if t.dtype != torch.float32 or t.shape != x.shape:
+            raise L.UvcHipError("pgd_step: x0, direction and out must be float32 of x's shape")
+    dt = UVC_F32
+    if out_t is not None:
+        dt = _row_dtype(out_t, "pgd_step")
+        if out_t.shape != x.shape:
+            raise L.UvcHipError("pgd_step: out_t must have x's shape")
+    args = [_channel_floats(v, Cc, n) for v, n in ((step, "step"), (eps, "eps"), (lo, "lo"), (hi, "hi"))]
+    L.check(L.lib().uvc_pgd_step(L.ptr(x), L.ptr(x0), L.ptr(direction), x.shape[0], P, Cc, *args, int(mode), L.ptr(out), L.ptr(out_t), dt,
+                                 L.cur_stream()), "uvc_pgd_step")
+    return out
+
+
 def image_crop_desc_dtype():
     """numpy dtype with the layout of uvc_image_crop_desc: a crop window inside an image of a resident store."""
     import numpy as np
