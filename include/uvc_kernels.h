@@ -177,7 +177,11 @@ typedef struct uvc_attn_args {
                                 masked proj columns, which need the head's output.
                                 Backward: dq / dk / dv of heads with 0 are written as zeros without being computed -- exact when dout is
                                 zero on the head's 64 columns, i.e. when attn.proj's input columns of that head are zero in the weights
-                                the dgrad used (Stage-2 masked fine-tuning) */
+                                the dgrad used (Stage-2 masked fine-tuning): the whole dqkv then carries the bits of the call without the
+                                table.  Only the value 0 skips a head; any other value keeps it, and a kept head's o, lse, dq, dk, dv and
+                                delta carry the bits they have without the table.
+                                lse (forward) and delta (backward) of a head with 0 are NOT WRITTEN, in any kernel family (short, persistent,
+                                dq + dk/dv pair, one-pass, streaming): the caller's bytes stay (tests/test_attention_head_keep_gpu.py) */
   int32_t variant;   /* backward, tuning / A-B: 0 = kernel picked by shape (bf16, 193 <= N <= 200, B * H >= 1024: the one-pass persistent kernel
                         k_attn_bwd_one, otherwise the dq + dk/dv pair); 1 = the pair; 2 = the one-pass kernel or UVC_ERR_UNSUPPORTED */
   int32_t grid;      /* backward, one-pass kernel: 0 = one persistent workgroup per CU; > 0 = that many (tests: several heads per workgroup
@@ -260,7 +264,9 @@ typedef struct uvc_attn_tok_args {
   void* dqkv;        /* T [B, N, 3, H, 64] backward output */
   int32_t B, N, H, head_dim, ntok, dtype;
   float scale;
-  const int32_t* head_keep;  /* optional device [H], forward and backward as in uvc_attn_args */
+  const int32_t* head_keep;  /* optional device [H], forward and backward as in uvc_attn_args: the ntok rows of o, or all N rows of dq, dk, dv,
+                                of a head with 0 are written as zeros.  These kernels have no lse or delta output, so a head with 0 writes
+                                nothing else */
 } uvc_attn_tok_args;
 int uvc_attention_tok_fwd(const uvc_attn_tok_args* args, void* stream);
 int uvc_attention_tok_bwd(const uvc_attn_tok_args* args, void* stream);

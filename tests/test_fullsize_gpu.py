@@ -227,6 +227,76 @@ def test_stage2_step_at_the_bench_shape_with_compacted_mlps():
     assert np.isfinite(float(out["loss"])) and np.isfinite(float(out["gnorm"]))
 
 
+def stage2_bench_trainer(batch):
+    """The Stage-2 trainer of bench.py --stage 2 at another batch: bench.stage2_checkpoint_state's masks (one pruned head in every block), and -- as
+    bench.py does, since the masks arrive after the constructor derived its tables -- the MLP compaction and the pruned-head table derived again."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    from uvc_amd.post_train import Stage2Trainer, default_args
+    torch.manual_seed(730)
+    a = default_args(model_type="deit_tiny_patch16_224", precision="bf16", train_batch_size=batch)
+    tr = Stage2Trainer(a, device="cuda", distributed=False, world_size=1)
+    bench.stage2_checkpoint_state(tr.model)
+    tr.mlp_widths = tr.model.set_mlp_compaction()
+    tr.head_keep = tr.model.set_head_skipping()
+    tr.model.skip_pruned_head_grads = tr.model._head_keep is not None
+    hk = tr.model._head_keep
+    assert hk is not None and tuple(hk.shape) == (12, 3) and bool((hk == 0).sum(1).eq(1).all()), hk      # one dead head in every block
+    assert tr.model.skip_pruned_head_grads
+    return a, tr
+
+
+def test_stage2_backward_skipping_pruned_heads_is_exact_where_the_one_pass_kernel_runs():
+    """test_stage2_gpu.py's test_training_backward_skipping_pruned_heads_is_exact at the size Stage 2 trains and is benchmarked at: DeiT-Tiny, bf16, batch
+    344 = 1032 heads of N = 197, where uvc_attention_bwd picks the one-pass persistent kernel, whose workgroups draw runs of dead and live heads from a
+    device counter.  With uvc_vit_io.head_keep_bwd the dq / dk / dv of the pruned heads are written as zeros instead of being computed; the step masks the
+    weights first, so their dL/d(attention output) is exactly zero: the loss, the clip norm and every parameter gradient equal those of the step that
+    computes them, bit for bit."""
+    batch = 344
+    assert batch * 3 >= 1024
+    x, y = inputs(batch)
+    res = []
+    for skip in (True, False):
+        a, tr = stage2_bench_trainer(batch)
+        tr.model.skip_pruned_head_grads = skip
+        tr.begin_epoch(a.warmup_epochs + 1)
+        out = tr.step(x, y, zero_grad=False)
+        torch.cuda.synchronize()
+        res.append((out["loss"].detach().clone(), torch.as_tensor(out["gnorm"]).detach().clone(),
+                    {n: p.grad.detach().clone() for n, p in tr.model.named_parameters() if p.grad is not None}))
+        del tr, out
+    assert bool(torch.isfinite(res[0][0]).all()) and bool(torch.isfinite(res[0][1]).all())
+    assert torch.equal(res[0][0], res[1][0]), (res[0][0], res[1][0])
+    assert torch.equal(res[0][1], res[1][1]), (res[0][1], res[1][1])
+    assert res[0][2].keys() == res[1][2].keys() and any(n.endswith("attn.qkv.weight") for n in res[0][2])
+    for n in res[0][2]:
+        assert torch.equal(res[0][2][n], res[1][2][n]), n
+
+
+def test_stage2_eval_forward_skipping_pruned_heads_is_exact_where_the_forward_is_persistent():
+    """The same model, a no-grad forward of 176 images = 528 heads: with the table the plain attention forward runs, persistent above 512 heads (a few
+    of its 512 workgroups walk a second head, with another h), and the last block's token-query kernel; without it (set_head_skipping(False)) the fused
+    qkv + attention kernel.  The skipped heads' outputs only meet masked attn.proj columns, so the logits are equal bit for bit."""
+    batch = 176
+    assert batch * 3 > 512
+    _, tr = stage2_bench_trainer(batch)
+    m = tr.model
+    m.apply_masks()
+    x, _ = inputs(batch)
+    m.eval()
+    with torch.no_grad():
+        out_skip, _ = m(x)
+        assert m._head_keep is not None
+        m.set_head_skipping(False)
+        assert m._head_keep is None
+        out_dense, _ = m(x)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(out_skip.float()).all())
+    assert torch.equal(out_skip, out_dense)
+
+
 def test_t2t_14_config5_stage1_properties_at_the_benched_batch():
     """BASELINE config 5 AT THE BENCHED SHAPE: T2T-ViT-14 with patch + block gating, per-GPU batch 128, bf16 -- where the attention
     backward takes the dq + dk/dv pair (768 heads < 1024) and the D = 384 row kernels their production tiling; the oracle-checked runs of this model are at

@@ -179,8 +179,11 @@ def attention_tok_fwd(qkv, o, B, N, H, ntok, dtype, head_keep=None):
     L.check(L.lib().uvc_attention_tok_fwd(C.byref(a), L.cur_stream()), "uvc_attention_tok_fwd")
 
 
-def attention_tok_bwd(qkv, o, dout, dqkv, B, N, H, ntok, dtype):
+def attention_tok_bwd(qkv, o, dout, dqkv, B, N, H, ntok, dtype, head_keep=None):
     a = _attn_tok_args(qkv, o, B, N, H, ntok, dtype, dout, dqkv)
+    if head_keep is not None:
+        _chk(head_keep)
+        a.head_keep = L.ptr(head_keep)
     L.check(L.lib().uvc_attention_tok_bwd(C.byref(a), L.cur_stream()), "uvc_attention_tok_bwd")
 
 
