@@ -573,6 +573,45 @@ int uvc_calib_workspace_bytes(int64_t n, int32_t ld, int32_t C, int32_t bins, in
 int uvc_calib_eval(const uvc_calib_args* args, void* stream);
 int uvc_calib_stats(const uvc_calib_args* args, void* stream);
 
+/* Out-of-distribution detectors on a bank (python -m uvc_amd.compact_ood; Hendrycks & Gimpel 2017, Liu et al. 2020, Lee et al. 2018, Ren et al.
+ * 2021, Sun et al. 2022).  Each call returns UVC_OK or refuses before anything is launched (outputs untouched); no atomics, one writer per
+ * output element in every launch, the same bits on a repeat, a row's result does not depend on the rows beside it, every row offset is
+ * 64-bit, 16-byte accesses where the stride and the pointer allow and element by element otherwise, workgroup counts functions of the shape
+ * alone (ood.hip).
+ *
+ * uvc_ood_logit_scores: logits float32 [n, ld] of which columns [0, n_valid) are valid (the rest is never read into a result); per row, in
+ * float32, with m the first maximum and d_c = z_c - m:  msp = 1 / sum_c exp(d_c),  maxlogit = m,  energy = m + T log sum_c exp(d_c / T)
+ * (= T log sum_c exp(z_c / T)),  entropy = sum_c p_c log p_c (the NEGATIVE entropy of softmax(z), 0 log 0 = 0) -- every score is higher for
+ * an in-distribution row.  The maximum's own term is exactly 1 and the sums are taken without it (log1p of the rest); n_valid = 1 gives
+ * 1, z_0, z_0, 0.  A NaN in a valid column gives NaN in that row's four results.  Each of the four outputs float32 [n] may be NULL (not all).
+ * One pass: up to 2048 columns a group of 1 .. 64 lanes holds a row in registers, beyond one workgroup takes a row (read twice, once from
+ * cache).  1 <= n < 2^31, 1 <= n_valid <= ld < 2^31, T > 0 and finite (UVC_ERR_ARG); n_valid <= 65536 (UVC_ERR_UNSUPPORTED).
+ *
+ * uvc_class_moments: X float32 [n, D] (row stride ldx), labels [n] (int32, or int64 with labels_i64); rows whose label lies outside [0, C)
+ * are skipped.  perm int64 [n]: the permutation of a STABLE ascending sort of the labels (position j of the sorted order holds row perm[j];
+ * an entry outside [0, n) reads nothing and counts as a skipped row).  counts int64 [C]; means float32 [C, D], 16-byte aligned: every
+ * (class, column) sum is taken in float64 over the class's rows in ascending row order -- in slices of 256 positions of the sorted order,
+ * the slices' partial sums added in ascending order: an order that is a function of (n, C, D) and the labels alone --, divided by the count
+ * and rounded once; an empty class gives count 0 and a row of +0.  The bank is read once, whatever C is.  D a multiple of 8 (UVC_ERR_ARG)
+ * up to 1016 (UVC_ERR_UNSUPPORTED), 1 <= C (UVC_ERR_ARG) <= 65536 (UVC_ERR_UNSUPPORTED), 1 <= n < 2^31, ldx >= D,
+ * workspace >= uvc_class_moments_workspace_bytes(n, D) and 8-byte aligned (UVC_ERR_ARG).
+ *
+ * uvc_center_rows: out [n, D] (row stride ldo) = x_i - means[y_i] in float32, one rounding; a skipped row becomes a row of +0 (it adds
+ * nothing to a scatter matrix).  Limits as uvc_class_moments'.
+ *
+ * uvc_rows_sqnorm_aug: Z float32 [n, ldz], ldz >= D + 8: sq[i] = sum_{d < D} z_id^2 in float32 -- lane l of the row's wave takes columns
+ * (64 u + l) 4 .. + 3, u ascending, as one fmaf chain, then the xor butterfly -- and Z[i, D .. D + 8) = 1, 0, .. 0: the row becomes a query of
+ * uvc_knn_topk against class rows (m_c, -|m_c|^2 / 2, 0 .. 0), whose best similarity s gives min_c |z - m_c|^2 = sq - 2 s.  Columns [0, D)
+ * and [D + 8, ldz) are not written.  D as above. */
+int uvc_ood_logit_scores(const float* logits, int64_t n, int64_t ld, int32_t n_valid, float temperature, float* msp, float* maxlogit,
+                         float* energy, float* entropy, void* stream);
+int uvc_class_moments_workspace_bytes(int64_t n, int32_t D, int64_t* bytes);
+int uvc_class_moments(const float* X, int64_t ldx, const void* labels, int32_t labels_i64, const int64_t* perm, int64_t n, int32_t D,
+                      int32_t C, int64_t* counts, float* means, void* workspace, int64_t workspace_bytes, void* stream);
+int uvc_center_rows(const float* X, int64_t ldx, const void* labels, int32_t labels_i64, const float* means, int64_t n, int32_t D, int32_t C,
+                    float* out, int64_t ldo, void* stream);
+int uvc_rows_sqnorm_aug(float* Z, int64_t ldz, int64_t n, int32_t D, float* sq, void* stream);
+
 /* clip_grad_norm_(max_norm) + AdamW over flat float32 buffers (joint_train.py:428-429;
  * torch.optim.AdamW(lr, betas, eps, weight_decay) semantics, decoupled decay).
  * uvc_grad_sqnorm accumulates sum(g^2) of a segment into sq[0] (accumulate = 0 for the first segment) and leaves sqrt(sq[0]) -- the

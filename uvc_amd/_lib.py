@@ -262,6 +262,11 @@ _SIGNATURES = {
     "uvc_calib_workspace_bytes": [I64, I32, I32, I32, C.POINTER(I64)],
     "uvc_calib_eval": [C.POINTER(uvc_calib_args), VP],
     "uvc_calib_stats": [C.POINTER(uvc_calib_args), VP],
+    "uvc_ood_logit_scores": [VP, I64, I64, I32, F32, VP, VP, VP, VP, VP],
+    "uvc_class_moments_workspace_bytes": [I64, I32, C.POINTER(I64)],
+    "uvc_class_moments": [VP, I64, VP, I32, VP, I64, I32, I32, VP, VP, VP, I64, VP],
+    "uvc_center_rows": [VP, I64, VP, I32, VP, I64, I32, I32, VP, I64, VP],
+    "uvc_rows_sqnorm_aug": [VP, I64, I64, I32, VP, VP],
     "uvc_grad_sqnorm": [VP, I64, VP, VP, I32, VP],
     "uvc_adamw_step": [C.POINTER(uvc_adamw_args), VP],
     "uvc_scale_by_clip": [VP, I64, VP, F32, VP],

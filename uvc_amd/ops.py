@@ -873,6 +873,153 @@ def calib_stats(logits, labels, scale, shift=None, num_classes=None, bins=15, *,
     return bin_count, bin_conf, bin_hit, sums, counts
 
 
+OOD_MAX_D = 1016                                    # D + 8 augmentation columns is knn_topk's widest row
+OOD_CHUNK_ROWS = 65536                              # tools/ood_time.py: within 5 % of the best of 16 384 / 65 536 / 262 144 at both ImageNet shapes
+
+
+def _rows_f32(t, what):
+    if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise L.UvcHipError(f"{what} must be float32 [n, D] with unit element stride")
+    return t.shape[0], t.shape[1], (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def _labels_1d(labels, n, what):
+    if labels.dim() != 1 or labels.dtype not in (torch.int32, torch.int64) or labels.shape[0] != n or not labels.is_contiguous():
+        raise L.UvcHipError(f"{what}: labels must be contiguous int32 or int64 [n]")
+    return int(labels.dtype == torch.int64)
+
+
+def ood_logit_scores(logits, n_valid=None, temperature=1.0, outs=None):
+    """(msp, maxlogit, energy, entropy), float32 [n] each: the maximum softmax probability, the maximum logit, ``T log sum exp(z / T)`` and
+    the NEGATIVE entropy of ``softmax(z)`` over columns [0, n_valid) (default: all) of the float32 ``logits`` [n, ld], one pass
+    (uvc_ood_logit_scores).  ``outs``: four contiguous float32 tensors to write into, None for a score that is not wanted."""
+    L.require_cuda(logits)
+    n, cols, ld = _rows_f32(logits, "ood_logit_scores: logits")
+    n_valid = cols if n_valid is None else int(n_valid)
+    if n_valid > cols:
+        raise L.UvcHipError(f"ood_logit_scores: n_valid {n_valid} is more than the logits' {cols} columns")
+    if outs is None:
+        outs = tuple(torch.empty(n, dtype=torch.float32, device=logits.device) for _ in range(4))
+    outs = tuple(outs)
+    _chk(*outs)
+    if len(outs) != 4 or any(o is not None and (o.dtype != torch.float32 or o.numel() < n) for o in outs):
+        raise L.UvcHipError("ood_logit_scores: outs must be four float32 tensors of at least n elements (or None)")
+    L.check(L.lib().uvc_ood_logit_scores(L.ptr(logits), n, ld, n_valid, float(temperature), *[L.ptr(o) for o in outs], L.cur_stream()),
+            "uvc_ood_logit_scores")
+    return outs
+
+
+def class_moments(X, labels, num_classes, *, counts=None, means=None):
+    """(counts int64 [C], means float32 [C, D]) of the float32 bank ``X`` [n, D] by the int32 / int64 ``labels``: rows with a label outside
+    [0, C) are skipped, every sum is float64 in a fixed order and rounded once, an empty class gives 0 and a row of +0 (uvc_class_moments).
+    The rows of a class are found through the permutation of a stable device sort of the labels."""
+    L.require_cuda(X, labels, counts, means)
+    n, D, ldx = _rows_f32(X, "class_moments: X")
+    i64 = _labels_1d(labels, n, "class_moments")
+    Cc = int(num_classes)
+    dev = X.device
+    counts = torch.empty(max(Cc, 0), dtype=torch.int64, device=dev) if counts is None else counts
+    means = torch.empty(max(Cc, 0), D, dtype=torch.float32, device=dev) if means is None else means
+    _chk(counts, means)
+    if counts.dtype != torch.int64 or counts.numel() < Cc or means.dtype != torch.float32 or means.numel() < Cc * D:
+        raise L.UvcHipError("class_moments: counts int64 [C] and means float32 [C, D]")
+    perm = torch.sort(labels, stable=True)[1]
+    ws, nbytes = None, 0
+    if n >= 1 and 8 <= D <= OOD_MAX_D and D % 8 == 0:                # (the call itself refuses the rest, by name)
+        b = C.c_int64(0)
+        L.check(L.lib().uvc_class_moments_workspace_bytes(n, D, C.byref(b)), "uvc_class_moments_workspace_bytes")
+        nbytes = int(b.value)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.check(L.lib().uvc_class_moments(L.ptr(X), ldx, L.ptr(labels), i64, L.ptr(perm), n, D, Cc, L.ptr(counts), L.ptr(means), L.ptr(ws), nbytes,
+                                      L.cur_stream()), "uvc_class_moments")
+    return counts, means
+
+
+def center_rows(X, labels, means, out=None):
+    """``out`` float32 [n, D] = x_i - means[y_i], one rounding; a row whose label lies outside [0, C) becomes +0 (uvc_center_rows)."""
+    L.require_cuda(X, labels, means, out)
+    n, D, ldx = _rows_f32(X, "center_rows: X")
+    i64 = _labels_1d(labels, n, "center_rows")
+    if means.dim() != 2 or means.dtype != torch.float32 or means.shape[1] != D or not means.is_contiguous():
+        raise L.UvcHipError("center_rows: means must be contiguous float32 [C, D]")
+    out = torch.empty(n, D, dtype=torch.float32, device=X.device) if out is None else out
+    if tuple(out.shape) != (n, D):
+        raise L.UvcHipError("center_rows: out must be float32 [n, D]")
+    _, _, ldo = _rows_f32(out, "center_rows: out")
+    L.check(L.lib().uvc_center_rows(L.ptr(X), ldx, L.ptr(labels), i64, L.ptr(means), n, D, means.shape[0], L.ptr(out), ldo, L.cur_stream()),
+            "uvc_center_rows")
+    return out
+
+
+def class_gaussian_fit(X, labels, num_classes, chunk_rows=None):
+    """(counts int64 [C], means float32 [C, D], scatter float32 [D, D]): ``class_moments``, then per chunk of ``chunk_rows`` rows (default
+    65 536) ``center_rows`` and ``gemm_tn`` in float32 onto ``scatter = sum_i (x_i - mean_{y_i}) (x_i - mean_{y_i})^T`` (beta = 1 after the first
+    chunk).  The same ``chunk_rows`` gives the same bits; different ones differ by float32 summation order."""
+    counts, means = class_moments(X, labels, num_classes)
+    n, D = X.shape
+    chunk = max(1, min(n, OOD_CHUNK_ROWS if chunk_rows is None else int(chunk_rows)))
+    dev = X.device
+    scatter = torch.empty(D, D, dtype=torch.float32, device=dev)
+    buf = torch.empty(chunk, D, dtype=torch.float32, device=dev)
+    ws = torch.empty(max(gemm_tn_workspace_bytes(chunk, D, D), 16), dtype=torch.uint8, device=dev)
+    for r0 in range(0, n, chunk):
+        rows = min(chunk, n - r0)
+        center_rows(X[r0:r0 + rows], labels[r0:r0 + rows], means, out=buf[:rows])
+        gemm_tn(buf, buf, scatter, ws, dtype=UVC_F32, beta=0.0 if r0 == 0 else 1.0, M=rows, N1=D, N2=D)
+    return counts, means, scatter
+
+
+def rows_sqnorm_aug(Z, D, sq=None):
+    """``sq`` float32 [n] = the sum of squares of columns [0, D) of every row of the float32 ``Z`` [n, >= D + 8]; columns [D, D + 8) are set
+    to 1, 0 .. 0 (uvc_rows_sqnorm_aug)."""
+    L.require_cuda(Z, sq)
+    n, _, ldz = _rows_f32(Z, "rows_sqnorm_aug: Z")
+    if Z.shape[1] < int(D) + 8:
+        raise L.UvcHipError("rows_sqnorm_aug: Z must have at least D + 8 columns")
+    sq = torch.empty(n, dtype=torch.float32, device=Z.device) if sq is None else sq
+    _chk(sq)
+    if sq.dtype != torch.float32 or sq.numel() < n:
+        raise L.UvcHipError("rows_sqnorm_aug: sq must be float32 [n]")
+    L.check(L.lib().uvc_rows_sqnorm_aug(L.ptr(Z), ldz, n, int(D), L.ptr(sq), L.cur_stream()), "uvc_rows_sqnorm_aug")
+    return sq
+
+
+def gauss_scores(X, whiten, mean0, wmeans=None, counts=None):
+    """``(min_d2 float32 [n], argmin int32 [n])``: the smallest squared Mahalanobis distance ``|whiten (x - mean_c)|^2`` of every row of the
+    float32 ``X`` [n, D] to a class with ``counts[c] > 0``, and that class; ``wmeans`` float32 [C, D] holds ``whiten (mean_c - mean0)``.  With
+    ``wmeans=None``: just ``|whiten (x - mean0)|^2``.  z = x whiten^T - whiten mean0 is ``gemm_nt`` in float32 with its bias epilogue into rows
+    of stride D + 8, ``rows_sqnorm_aug`` takes |z|^2 and appends 1, 0 .. 0, and ``knn_topk`` with k = 1 against the rows
+    (m_c, -|m_c|^2 / 2, 0 .. 0) finds ``max_c (z . m_c - |m_c|^2 / 2)``: min_c |z - m_c|^2 = |z|^2 - 2 max_c (..).  The class rows (C x D, once
+    per call), the final ``sq - 2 s`` and the map from kept rows back to classes are plain torch statements; everything of size n x D or
+    n x C is a kernel."""
+    L.require_cuda(X, whiten, mean0, wmeans, counts)
+    n, D, ldx = _rows_f32(X, "gauss_scores: X")
+    if D % 8 or not 8 <= D <= OOD_MAX_D:
+        raise L.UvcHipError(f"gauss_scores: D must be a multiple of 8 in [8, {OOD_MAX_D}], not {D}")
+    if whiten.dtype != torch.float32 or tuple(whiten.shape) != (D, D) or not whiten.is_contiguous() or mean0.dtype != torch.float32 or \
+            tuple(mean0.shape) != (D,) or not mean0.is_contiguous():
+        raise L.UvcHipError("gauss_scores: whiten must be contiguous float32 [D, D] and mean0 float32 [D]")
+    dev = X.device
+    bias = torch.empty(1, D, dtype=torch.float32, device=dev)
+    gemm_nt(mean0.view(1, D), whiten, bias, dtype=UVC_F32, alpha=-1.0)
+    z = torch.empty(n, D + 8, dtype=torch.float32, device=dev)
+    gemm_nt(X, whiten, z, dtype=UVC_F32, epilogue=EPI_BIAS, bias=bias.view(D), M=n, N=D, K=D, lda=ldx, ldc=D + 8)
+    sq = rows_sqnorm_aug(z, D)
+    if wmeans is None:
+        return sq
+    if wmeans.dtype != torch.float32 or wmeans.dim() != 2 or wmeans.shape[1] != D or counts is None or counts.shape[0] != wmeans.shape[0]:
+        raise L.UvcHipError("gauss_scores: wmeans must be float32 [C, D] with counts [C]")
+    kept = torch.nonzero(counts > 0)[:, 0]
+    if kept.numel() == 0:
+        raise L.UvcHipError("gauss_scores: every class is empty")
+    m = wmeans[kept]
+    aug = torch.zeros(kept.numel(), D + 8, dtype=torch.float32, device=dev)
+    aug[:, :D] = m
+    aug[:, D] = (-0.5 * m.double().square().sum(dim=1)).float()      # rounded once
+    sims, idx = knn_topk(z, aug, 1)
+    return sq - 2.0 * sims[:, 0], kept[idx[:, 0].long()].to(torch.int32)
+
+
 def patch_rank(scores, offset=0, descending=True, np=None):
     """int32 [B, np]: the removal order of every image's patches from float32 ``scores`` [B, ld], the patches being columns
     [offset, offset + np) (default np: the rest of the row) -- rank[b, p] patches come before p; larger score first with ``descending``,
