@@ -34,6 +34,7 @@ Another label set -- the model's features for a dataset (``CompactVisionTransfor
 from __future__ import annotations
 
 import argparse
+import copy
 import ctypes as C
 import json
 import math
@@ -179,6 +180,27 @@ def check_export(export: dict) -> dict:
 
 def load_compact(path) -> dict:
     return check_export(torch.load(path, map_location="cpu"))
+
+
+def as_export(export_or_path) -> dict:
+    """The checked compact dict of what a command was handed: the dict itself, or the file at a path."""
+    return check_export(export_or_path) if isinstance(export_or_path, dict) else load_compact(export_or_path)
+
+
+def with_state(export: dict, state_dict: dict, cfg: Optional[dict] = None) -> dict:
+    """A compact dict with the given weights (and ``cfg``; default: the source's): ``blocks`` and ``cfg`` are copies, every other value
+    is the source's."""
+    out = {k: v for k, v in export.items() if k not in ("cfg", "state_dict", "blocks")}
+    out.update(cfg=copy.deepcopy(export["cfg"] if cfg is None else cfg), blocks=copy.deepcopy(export["blocks"]), state_dict=state_dict)
+    return check_export(out)
+
+
+def num_labels(cfg, num_labels=None) -> int:
+    """The valid logits of a head: ``num_labels`` (default: all ``num_classes``), refused outside the head."""
+    nl = cfg["num_classes"] if num_labels is None else int(num_labels)
+    if not 1 <= nl <= cfg["num_classes"]:
+        raise ValueError(f"num_labels {nl} must lie in [1, {cfg['num_classes']}] (the model's head)")
+    return nl
 
 
 def reference_forward(export: dict, x: torch.Tensor) -> torch.Tensor:
@@ -836,8 +858,6 @@ def predict_command(args, dev):
     """``predict``, ``explain`` and ``attribute``: one JSON line per image to --output (or stdout), then the summary line
     ``{"images", "errors", "batches", "img_per_s"}``.  ``attribute`` is ``explain`` with method "attribution" on a ``CompactAttributionViT``:
     a file with more than 256 tokens fails here, before any image is listed or read."""
-    import sys
-    import time
     from . import data
     export = load_compact(args.compact)
     classes = read_classes(args.classes) if args.classes else None
@@ -847,23 +867,34 @@ def predict_command(args, dev):
     files = data.list_images(args.images)
     if args.cmd != "attribute":
         cm = CompactVisionTransformer(export, precision=args.precision, device=dev)
-    out = open(args.output, "w", encoding="utf-8") if args.output else sys.stdout
+    kw = dict(topk=args.topk, batch_size=args.batch_size, preset=args.preset, interpolation=args.interpolation, crop_pct=args.crop_pct,
+              num_labels=args.num_labels, classes=classes, num_workers=args.num_workers, fused_input=bool(args.fused_input))
+    if args.cmd == "attribute":
+        recs = explain(cm, files, method="attribution", target=args.target, overlay_dir=args.overlay_dir, **kw)
+    else:
+        recs = explain(cm, files, method=args.method, overlay_dir=args.overlay_dir, **kw) if args.cmd == "explain" else predict(cm, files, **kw)
+    return write_records(recs, args.output, batch_size=args.batch_size)
+
+
+def write_records(records, output, batch_size=None):
+    """The JSON-lines writer of the image-file commands: one line per record of the generator ``records`` (nothing of it has run yet) to
+    the file ``output`` (None: stdout), which is closed whatever happens.  With ``batch_size`` the summary line ``{"images", "errors",
+    "batches", "img_per_s"}`` follows the records and is returned."""
+    import sys
+    import time
+    out = open(output, "w", encoding="utf-8") if output else sys.stdout
     n = nerr = 0
+    summary = None
     t0 = time.perf_counter()
     try:
-        kw = dict(topk=args.topk, batch_size=args.batch_size, preset=args.preset, interpolation=args.interpolation, crop_pct=args.crop_pct,
-                  num_labels=args.num_labels, classes=classes, num_workers=args.num_workers, fused_input=bool(args.fused_input))
-        if args.cmd == "attribute":
-            recs = explain(cm, files, method="attribution", target=args.target, overlay_dir=args.overlay_dir, **kw)
-        else:
-            recs = explain(cm, files, method=args.method, overlay_dir=args.overlay_dir, **kw) if args.cmd == "explain" else predict(cm, files, **kw)
-        for rec in recs:
+        for rec in records:
             out.write(json.dumps(rec) + "\n")
             n += 1
             nerr += "error" in rec
-        dt = time.perf_counter() - t0
-        summary = dict(images=n, errors=nerr, batches=math.ceil(n / args.batch_size), img_per_s=n / dt if dt > 0 else 0.0)
-        out.write(json.dumps(summary) + "\n")
+        if batch_size is not None:
+            dt = time.perf_counter() - t0
+            summary = dict(images=n, errors=nerr, batches=math.ceil(n / batch_size), img_per_s=n / dt if dt > 0 else 0.0)
+            out.write(json.dumps(summary) + "\n")
     finally:
         if out is not sys.stdout:
             out.close()
@@ -920,11 +951,21 @@ def _parser():
 
 def _add_predict_flags(q):
     """``predict``'s flags; ``explain`` takes the same ones with the same defaults."""
-    from .data import INTERPOLATIONS
     q.add_argument("--compact", required=True, help="the compact file (a dense checkpoint goes through `export` first)")
+    add_image_file_flags(q)
+    q.add_argument("--fused_input", type=int, default=FUSED_INPUT_DEFAULT,
+                   help="1: the resampler writes the patch rows (uvc_image_prep_patches); 0: images, then uvc_patchify")
+
+
+def add_image_file_flags(q, *, topk=True, classes=True):
+    """--images --output [--topk] --batch_size --num_workers --precision --preset --interpolation --crop_pct [--classes] --num_labels: what
+    the commands that read image files share (``predict`` / ``explain`` / ``attribute``, ``compact_pixel``, ``compact_perturb``).  A flag
+    of this block is added here and nowhere else."""
+    from .data import INTERPOLATIONS
     q.add_argument("--images", nargs="+", required=True, help="image files, or directories walked recursively for image files (sorted)")
     q.add_argument("--output", default=None, help="JSON-lines file; default: stdout")
-    q.add_argument("--topk", type=_int_in(1, MAX_TOPK, "--topk"), default=5)
+    if topk:
+        q.add_argument("--topk", type=_int_in(1, MAX_TOPK, "--topk"), default=5)
     q.add_argument("--batch_size", type=_int_in(1, 65535, "--batch_size"), default=64)
     q.add_argument("--num_workers", type=int, default=8, help="decode threads (at most 16)")
     q.add_argument("--precision", default="bf16")
@@ -933,11 +974,11 @@ def _add_predict_flags(q):
     q.add_argument("--interpolation", choices=list(INTERPOLATIONS), default="bilinear")
     q.add_argument("--crop_pct", type=_crop_pct_arg, default=None,
                    help="imagenet preset: resize the short side to floor(img_size / crop_pct) before the centre crop; default: img_size * 256 // 224")
-    q.add_argument("--classes", default=None, help="class names: one per line, or a JSON list")
+    if classes:
+        q.add_argument("--classes", default=None, help="class names: one per line, or a JSON list")
     q.add_argument("--num_labels", type=_int_in(1, 1 << 20, "--num_labels"), default=None,
-                   help="the valid logits (the rest of the head is padding); default: the length of --classes, else the file's num_classes")
-    q.add_argument("--fused_input", type=int, default=FUSED_INPUT_DEFAULT,
-                   help="1: the resampler writes the patch rows (uvc_image_prep_patches); 0: images, then uvc_patchify")
+                   help="the valid logits (the rest of the head is padding); default: " + ("the length of --classes, else " if classes else "")
+                   + "the file's num_classes")
 
 
 def _dense_model(args, dev):

@@ -27,13 +27,12 @@ from typing import Optional, Sequence
 import torch
 
 from . import compact as CP
-from . import compact_probe as PB
-from . import compact_transfer as CT
+from . import compact_tools as TL
 
 METHODS = ("temperature", "vector")
 MAX_BINS = 64                                       # uvc_calib_stats' limit
-BANK_KEYS = ("logits", "labels", "data_classes", "num_classes", "meta")
-META_KEYS = tuple(k for k in CT.META_KEYS if k != "embed_dim")
+BANK_KEYS = TL.LOGITS_BANK_KEYS
+META_KEYS = tuple(k for k in TL.META_KEYS if k != "embed_dim")
 
 
 # ---- written specs ----------------------------------------------------------------------------------------------------------------
@@ -119,7 +118,7 @@ class DeviceEvaluator:
     dtype = torch.float32
 
     def __init__(self, chunk_rows=None, device=None):
-        self.device = CT._device(device)
+        self.device = TL.device(device)
         self.chunk_rows = None if chunk_rows is None else int(chunk_rows)
         self._ws = None
 
@@ -159,7 +158,7 @@ class DeviceEvaluator:
 def device_scorer(logits, labels, scale, shift, classes, bins=15, device=None):
     """``reliability`` of ``ops.calib_stats``: the scorer of a bank on the device (``logits`` and ``labels`` from anywhere)."""
     from . import ops
-    dev = CT._device(device)
+    dev = TL.device(device)
     with torch.cuda.device(dev):
         Z = torch.as_tensor(logits).to(dev, torch.float32).contiguous()
         y = torch.as_tensor(labels).to(dev).contiguous()
@@ -202,30 +201,21 @@ def fit_calibration(logits, labels, classes, method="temperature", *, evaluator=
         if init is not None:
             u.copy_(torch.as_tensor(init[0]).to(u).reshape(1).log())
         params = [u.requires_grad_()]
-    tol_change = (0.0 if dtype == torch.float64 else 1e-11) if tol_change is None else tol_change      # (as fit_probe: the device's F is summed in float64)
-    opt = torch.optim.LBFGS(params, lr=1.0, max_iter=int(max_iter), max_eval=int(max_iter) * 5 // 4 + 1, history_size=int(history),
-                            tolerance_grad=float(tol_grad), tolerance_change=float(tol_change), line_search_fn="strong_wolfe")
-    last = {}
 
-    def closure():
-        with torch.no_grad():
-            if vector:
-                F, ds, dd, hits = evaluator(Z, y, a.detach(), d.detach(), classes)[:4]
-                a.grad, d.grad = torch.as_tensor(ds).to(a).reshape(a.shape), torch.as_tensor(dd).to(d).reshape(d.shape)
-            else:
-                s = u.detach().exp()
-                F, ds, _, hits = evaluator(Z, y, s, None, classes)[:4]
-                u.grad = (s * torch.as_tensor(ds).to(u).reshape(1))
-        F = torch.as_tensor(F, dtype=torch.float64).reshape(())
-        last.update(F=F, hits=hits)
-        return F
+    def evaluate():
+        if vector:
+            F, ds, dd, hits = evaluator(Z, y, a.detach(), d.detach(), classes)[:4]
+            a.grad, d.grad = torch.as_tensor(ds).to(a).reshape(a.shape), torch.as_tensor(dd).to(d).reshape(d.shape)
+        else:
+            s = u.detach().exp()
+            F, ds, _, hits = evaluator(Z, y, s, None, classes)[:4]
+            u.grad = (s * torch.as_tensor(ds).to(u).reshape(1))
+        return F, hits
 
-    opt.step(closure)
-    F = closure()                                                    # the objective, gradient and hits AT the returned point
-    st = opt.state[params[0]]
+    F, last, g, iterations, evaluations = TL.lbfgs(params, evaluate, max_iter=max_iter, history=history, tol_grad=tol_grad, tol_change=tol_change,
+                                                   dtype=dtype)
     m = int(((y >= 0) & (y < classes)).sum())
-    out = dict(F=float(F), top1=100.0 * int(last["hits"]) / m if m else 0.0, grad_inf=max(float(p.grad.abs().max()) for p in params),
-               iterations=int(st.get("n_iter", 0)), evaluations=int(st.get("func_evals", 0)) + 1, rows=m)
+    out = dict(F=F, top1=100.0 * int(last["hits"]) / m if m else 0.0, grad_inf=g, iterations=iterations, evaluations=evaluations, rows=m)
     if vector:
         out.update(scale=a.detach().cpu().clone(), shift=d.detach().cpu().clone())
     else:
@@ -236,13 +226,8 @@ def fit_calibration(logits, labels, classes, method="temperature", *, evaluator=
 
 # ---- banks ------------------------------------------------------------------------------------------------------------------------
 def make_logits_bank(logits, labels, data_classes, **meta):
-    """The logits bank's dict: tensors and plain values only."""
-    logits = logits.detach().float().cpu().contiguous()
-    labels = labels.detach().to(torch.int64).cpu().contiguous()
-    if logits.dim() != 2 or labels.shape != (logits.shape[0],):
-        raise ValueError("logits [n, num_classes] and one label per row")
-    return dict(logits=logits, labels=labels, data_classes=int(data_classes), num_classes=int(logits.shape[1]),
-                meta={k: meta.get(k) for k in META_KEYS})
+    """The logits bank's dict (``compact_tools.make_bank``): ``BANK_KEYS``, no ``embed_dim`` in ``meta``."""
+    return TL.make_bank(labels, data_classes, logits=logits, **meta)
 
 
 def check_logits_bank(bank, export=None, data_classes=None):
@@ -271,35 +256,13 @@ def load_logits_bank(path) -> dict:
         raise ValueError(f"{path}: {e}") from None
 
 
-@torch.no_grad()
-def logits_of_dataset(model, loader):
-    """``(eval logits float32 [n, num_classes], labels int64 [n])`` on the device: ``forward`` over every batch ``loader`` yields, in its order."""
-    out, labels = [], []
-    for x, y in loader:
-        out.append(model(x)[0].float())
-        labels.append(y.to(torch.int64))
-    if not out:
-        raise ValueError("the loader yields no batch")
-    return torch.cat(out), torch.cat(labels)
-
-
 def logits_command(export_or_path, args, dev=None):
-    """``logits``: the bank dict of ``args.split`` (saved to ``args.output`` when given) and the summary."""
-    export = CP.load_compact(export_or_path) if not isinstance(export_or_path, dict) else CP.check_export(export_or_path)
-    dev = CT._device(dev)
-    model, loader, classes = CT._model_and_loader(export, args, args.split, dev)
-    with torch.cuda.device(dev):
-        t0 = time.perf_counter()
-        z, labels = logits_of_dataset(model, loader)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-    meta = CT._meta(export, args, args.split)
-    bank = check_logits_bank(make_logits_bank(z, labels, classes, **meta), export, classes)
-    if getattr(args, "output", None):
-        torch.save(bank, args.output)
-    n = int(z.shape[0])
-    return bank, dict(output=getattr(args, "output", None), images=n, img_per_s=n / dt if dt > 0 else 0.0, data_classes=classes,
-                      num_classes=bank["num_classes"])
+    """``logits``: the bank dict of ``args.split`` -- ``forward``'s eval logits of every batch -- (saved to ``args.output`` when given) and
+    the summary."""
+    export = CP.as_export(export_or_path)
+    return TL.bank_command(export, args, dev, lambda model, x: (model(x)[0].float(),),
+                           lambda z, labels, classes, **meta: check_logits_bank(make_logits_bank(z, labels, classes, **meta), export, classes),
+                           lambda bank: dict(num_classes=bank["num_classes"]))
 
 
 # ---- the file ---------------------------------------------------------------------------------------------------------------------
@@ -324,9 +287,7 @@ def calibrated_head(export, scale, shift, classes):
             w, b = sd[name + ".weight"], sd[name + ".bias"]
             w[:classes] = (a[:, None] * w[:classes].double()).to(w.dtype)
             b[:classes] = (a * b[:classes].double() + d).to(b.dtype)
-    out = {k: v for k, v in export.items() if k not in ("cfg", "state_dict", "blocks")}
-    out.update(cfg=dict(export["cfg"]), blocks=[dict(b) for b in export["blocks"]], state_dict=sd)
-    return CP.check_export(out)
+    return CP.with_state(export, sd)
 
 
 # ---- the commands -----------------------------------------------------------------------------------------------------------------
@@ -337,7 +298,7 @@ def _bank_arg(b):
 def fit_command(args, dev=None, evaluator=None, scorer=None):
     """``fit``.  ``evaluator`` / ``scorer``: None runs on the device (``DeviceEvaluator``, ``device_scorer``); ``reference_objective`` and
     ``reference_scorer`` run the same command on the CPU."""
-    export = CP.load_compact(args.compact) if not isinstance(args.compact, dict) else CP.check_export(args.compact)
+    export = CP.as_export(args.compact)
     bank = check_logits_bank(_bank_arg(args.bank), export)
     classes = int(bank["data_classes"])
     fit, val = (bank["logits"], bank["labels"]), None
@@ -345,10 +306,10 @@ def fit_command(args, dev=None, evaluator=None, scorer=None):
         vb = check_logits_bank(_bank_arg(args.val_bank), export, classes)
         val = (vb["logits"], vb["labels"])
     elif args.val_fraction is not None:
-        fit, val = PB.split_bank(dict(features=bank["logits"], labels=bank["labels"]), args.val_fraction, args.seed)
+        fit, val = TL.split_bank(dict(features=bank["logits"], labels=bank["labels"]), args.val_fraction, args.seed)
     on_device = evaluator is None or scorer is None
     if on_device:
-        dev = CT._device(dev)
+        dev = TL.device(dev)
     if evaluator is None:
         evaluator = DeviceEvaluator(args.chunk_rows, dev)
     if scorer is None:
@@ -379,36 +340,23 @@ def fit_command(args, dev=None, evaluator=None, scorer=None):
 def score_command(args, dev=None, scorer=None):
     bank = _bank_arg(args.bank)
     if scorer is None:
-        dev = CT._device(dev)
+        dev = TL.device(dev)
         scorer = lambda z, y, a, d, c, bins: device_scorer(z, y, a, d, c, bins, dev)
     rec = scorer(bank["logits"], bank["labels"], torch.ones(1), None, int(bank["data_classes"]), args.bins)
     return dict(images=int(bank["logits"].shape[0]), data_classes=int(bank["data_classes"]), num_classes=int(bank["num_classes"]), bins=int(args.bins), **rec)
 
 
 def build_parser():
-    from .data import INTERPOLATIONS
     p = argparse.ArgumentParser(prog="python -m uvc_amd.compact_calibrate", description="Reliability, temperature scaling and vector scaling of a compact model")
     sub = p.add_subparsers(dest="cmd", required=True)
     l, f, s = (sub.add_parser(n) for n in ("logits", "fit", "score"))
     for q in (l, f):
         q.add_argument("--compact", required=True, help="the compact file")
-    l.add_argument("--dataset", choices=["cifar10", "cifar100", "imagenet"], default="imagenet")
-    l.add_argument("--data_dir", default=None)
-    l.add_argument("--eval_batch_size", type=CP._int_in(1, 65535, "--eval_batch_size"), default=256)
-    l.add_argument("--num_workers", type=int, default=8, help="decode threads (at most 16)")
-    l.add_argument("--precision", choices=["bf16", "fp32"], default="bf16")
-    l.add_argument("--interpolation", choices=list(INTERPOLATIONS), default="bilinear")
-    l.add_argument("--crop_pct", type=CP._crop_pct_arg, default=None)
-    l.add_argument("--packed_dir", default=None, help="DIR/train.uvcpack and DIR/val.uvcpack replace the folders or pickles under --data_dir")
-    l.add_argument("--resident", type=int, default=0, choices=[0, 1], help="1: keep the split's pixels on the device")
-    l.add_argument("--split", choices=["train", "test"], default="train")
+    TL.add_dataset_flags(l)
     l.add_argument("--output", required=True, help="the bank file: eval logits, labels, data_classes, num_classes, meta")
     f.add_argument("--bank", required=True, help="the logits bank to fit on (a held-out split: compact_calibrate logits)")
     f.add_argument("--method", choices=list(METHODS), default="temperature")
-    v = f.add_mutually_exclusive_group()
-    v.add_argument("--val_bank", default=None, help="a logits bank to report the held-out record on")
-    v.add_argument("--val_fraction", type=PB._fraction, default=None, help="hold out this fraction of --bank (a --seed permutation's last rows)")
-    f.add_argument("--seed", type=int, default=0)
+    TL.add_val_flags(f, "a logits bank to report the held-out record on")
     f.add_argument("--max_iter", type=CP._int_in(1, 1000000, "--max_iter"), default=500)
     f.add_argument("--chunk_rows", type=CP._int_in(1, 2 ** 31 - 1, "--chunk_rows"), default=None, help="rows per call of the evaluator (default: the whole bank)")
     f.add_argument("--output", required=True, help="the compact file with the calibration folded into its head")
@@ -421,8 +369,7 @@ def build_parser():
 def main(argv: Optional[Sequence[str]] = None):
     args = build_parser().parse_args(argv)
     if args.cmd == "logits":
-        if not args.data_dir and not args.packed_dir:
-            raise SystemExit("need --data_dir or --packed_dir")
+        TL.need_data(args)
         summary = logits_command(args.compact, args)[1]
     else:
         summary = fit_command(args)[0] if args.cmd == "fit" else score_command(args)

@@ -37,6 +37,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import compact as CP
+from . import compact_tools as TL
 from . import compact_transfer as CT
 
 METHODS = ("msp", "maxlogit", "energy", "entropy", "mahalanobis", "rmd", "knn")
@@ -165,12 +166,7 @@ def metrics(id_scores, ood_scores, method=None):
 # ---- the bank and detector files ------------------------------------------------------------------------------------------------------
 def make_ood_bank(features, logits, labels, data_classes, **meta):
     """``compact_transfer.make_bank``'s dict plus the eval logits float32 [n, num_classes], ``num_classes`` and ``normalized: False``."""
-    bank = CT.make_bank(features, labels, data_classes, **meta)
-    logits = logits.detach().float().cpu().contiguous()
-    if logits.dim() != 2 or logits.shape[0] != bank["features"].shape[0]:
-        raise ValueError("logits [n, num_classes]: one row per feature row")
-    bank.update(logits=logits, num_classes=int(logits.shape[1]), normalized=False)
-    return bank
+    return TL.make_bank(labels, data_classes, features=features, logits=logits, normalized=False, **meta)
 
 
 def check_ood_bank(bank, what="the bank"):
@@ -240,7 +236,7 @@ def fit_detector(bank, shrinkage=1e-6, knn_fraction=1.0, seed=0, chunk_rows=None
     if D % 8 or not 8 <= D <= MAX_D:
         raise ValueError(f"embed_dim must be a multiple of 8 in [8, {MAX_D}], not {D}")
     rows = knn_rows(n, knn_fraction, seed)
-    dev = CT._device(dev)
+    dev = TL.device(dev)
     with torch.cuda.device(dev):
         counts, means, scatter = ops.class_gaussian_fit(bank["features"].to(dev), bank["labels"].to(dev), C, chunk_rows=chunk_rows)
         counts, means, scatter = counts.cpu(), means.cpu(), scatter.cpu()
@@ -259,7 +255,7 @@ def score_bank(detector, bank, methods=METHODS, k=50, temperature=1.0, precision
     selects the operand type of the k-NN search."""
     from . import ops
     check_request(detector, methods, k, temperature)
-    dev = CT._device(dev)
+    dev = TL.device(dev)
     out = {}
     C = int(detector["data_classes"])
     with torch.cuda.device(dev):
@@ -293,7 +289,7 @@ def evaluate(detector, id_bank, ood_bank, methods=METHODS, k=50, temperature=1.0
     check_against(detector, id_bank, "the ID bank", data_classes=True)
     check_against(detector, ood_bank, "the OOD bank")
     check_request(detector, methods, k, temperature)
-    dev = CT._device(dev)
+    dev = TL.device(dev)
     t0 = time.perf_counter()
     si = score_bank(detector, id_bank, methods, k, temperature, precision, dev)
     so = score_bank(detector, ood_bank, methods, k, temperature, precision, dev)
@@ -311,32 +307,11 @@ def evaluate(detector, id_bank, ood_bank, methods=METHODS, k=50, temperature=1.0
 
 
 # ---- the commands -------------------------------------------------------------------------------------------------------------------------
-@torch.no_grad()
 def bank_command(export_or_path, args, dev=None):
-    """``bank``: the bank dict of ``args.split`` (saved to ``args.output`` when given) and ``compact_transfer embed``'s summary plus
-    ``"normalized": False, "logits": True``."""
-    export = CP.load_compact(export_or_path) if not isinstance(export_or_path, dict) else CP.check_export(export_or_path)
-    dev = CT._device(dev)
-    model, loader, classes = CT._model_and_loader(export, args, args.split, dev)
-    feats, logits, labels = [], [], []
-    with torch.cuda.device(dev):
-        t0 = time.perf_counter()
-        for x, y in loader:
-            z, f = model.features(x, normalize=False)
-            logits.append(z)
-            feats.append(f)
-            labels.append(y.to(torch.int64))
-        if not feats:
-            raise ValueError("the loader yields no batch")
-        feats, logits, labels = torch.cat(feats), torch.cat(logits), torch.cat(labels)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-    bank = make_ood_bank(feats, logits, labels, classes, **CT._meta(export, args, args.split))
-    if getattr(args, "output", None):
-        torch.save(bank, args.output)
-    n = int(feats.shape[0])
-    return bank, dict(output=getattr(args, "output", None), images=n, img_per_s=n / dt if dt > 0 else 0.0, data_classes=classes,
-                      embed_dim=int(feats.shape[1]), normalized=False, logits=True)
+    """``bank``: the bank dict of ``args.split`` -- the eval logits and raw features of ONE ``features(normalize=False)`` call per batch --
+    (saved to ``args.output`` when given) and ``compact_transfer embed``'s summary plus ``"normalized": False, "logits": True``."""
+    return TL.bank_command(export_or_path, args, dev, lambda model, x: model.features(x, normalize=False)[::-1], make_ood_bank,
+                           lambda bank: dict(embed_dim=int(bank["features"].shape[1]), normalized=False, logits=True))
 
 
 def fit_command(args, dev=None):
@@ -363,21 +338,11 @@ def score_command(args, dev=None):
 
 
 def build_parser():
-    from .data import INTERPOLATIONS
     p = argparse.ArgumentParser(prog="python -m uvc_amd.compact_ood", description="Out-of-distribution detection for a compact model")
     sub = p.add_subparsers(dest="cmd", required=True)
     b = sub.add_parser("bank")
     b.add_argument("--compact", required=True, help="the compact file")
-    b.add_argument("--dataset", choices=["cifar10", "cifar100", "imagenet"], default="imagenet")
-    b.add_argument("--data_dir", default=None)
-    b.add_argument("--eval_batch_size", type=CP._int_in(1, 65535, "--eval_batch_size"), default=256)
-    b.add_argument("--num_workers", type=int, default=8, help="decode threads (at most 16)")
-    b.add_argument("--precision", choices=["bf16", "fp32"], default="bf16")
-    b.add_argument("--interpolation", choices=list(INTERPOLATIONS), default="bilinear")
-    b.add_argument("--crop_pct", type=CP._crop_pct_arg, default=None)
-    b.add_argument("--packed_dir", default=None, help="DIR/train.uvcpack and DIR/val.uvcpack replace the folders or pickles under --data_dir")
-    b.add_argument("--resident", type=int, default=0, choices=[0, 1], help="1: keep the split's pixels on the device")
-    b.add_argument("--split", choices=["train", "test"], default="train")
+    TL.add_dataset_flags(b)
     b.add_argument("--output", required=True, help="the bank file: raw features, eval logits, labels, data_classes, num_classes, meta")
     f = sub.add_parser("fit")
     f.add_argument("--bank", required=True, help="a raw bank of the ID train split (bank --split train)")
@@ -401,8 +366,7 @@ def build_parser():
 def main(argv: Optional[Sequence[str]] = None):
     args = build_parser().parse_args(argv)
     if args.cmd == "bank":
-        if not args.data_dir and not args.packed_dir:
-            raise SystemExit("need --data_dir or --packed_dir")
+        TL.need_data(args)
         summary = bank_command(args.compact, args)[1]
     elif args.cmd == "fit":
         summary = fit_command(args)[1]

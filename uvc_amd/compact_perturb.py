@@ -16,7 +16,6 @@ plain PyTorch.
 from __future__ import annotations
 
 import argparse
-import json
 import os
 from typing import Optional, Sequence
 
@@ -65,13 +64,6 @@ def _counts_of(npatch, steps, counts):
     return counts
 
 
-def _num_labels(cfg, num_labels):
-    nl = cfg["num_classes"] if num_labels is None else int(num_labels)
-    if not 1 <= nl <= cfg["num_classes"]:
-        raise ValueError(f"num_labels {nl} must lie in [1, {cfg['num_classes']}] (the model's head)")
-    return nl
-
-
 def _targets(target, B, nl):
     t = torch.as_tensor(target)
     if t.is_floating_point() or t.dtype == torch.bool:
@@ -105,7 +97,7 @@ def perturbation_curves(model, x, maps, target, *, order="positive", steps=10, c
     from . import ops
     descending = _order_flag(order)
     c = model._export["cfg"]
-    nl = _num_labels(c, num_labels)
+    nl = CP.num_labels(c, num_labels)
     x = model._prep(x)
     B, P = x.shape[0], c["patch_size"]
     npatch, width = (c["img_size"] // P) ** 2, c["in_chans"] * P * P
@@ -166,7 +158,7 @@ def reference_perturbation(export, x, maps, target, *, order="positive", steps=1
     each grid point's batch."""
     descending = _order_flag(order)
     cfg = CP.check_export(export)["cfg"]
-    nl = _num_labels(cfg, num_labels)
+    nl = CP.num_labels(cfg, num_labels)
     B, P = x.shape[0], cfg["patch_size"]
     g = cfg["img_size"] // P
     npatch, ntok = g * g, 2 if cfg["enable_dist"] else 1
@@ -239,7 +231,7 @@ def evaluate(export_or_path, files, *, methods=("rollout",), orders=ORDERS, step
         raise ValueError(f"preset must be one of {CP.PRESETS}, not {preset!r}")
     export = CP.load_compact(export_or_path) if isinstance(export_or_path, (str, os.PathLike)) else CP.check_export(export_or_path)
     c = export["cfg"]
-    nl = _num_labels(c, num_labels)
+    nl = CP.num_labels(c, num_labels)
     if target is not None and not 0 <= int(target) < nl:
         raise ValueError(f"target {target} must lie in [0, {nl}) (num_labels)")
     modules = modules or build_modules(export, methods, precision, device)
@@ -298,11 +290,9 @@ def evaluate(export_or_path, files, *, methods=("rollout",), orders=ORDERS, step
 
 # ---- command line -------------------------------------------------------------------------------------------------------------
 def build_parser():
-    from .data import INTERPOLATIONS
     p = argparse.ArgumentParser(prog="python -m uvc_amd.compact_perturb",
                                 description="Perturbation test (deletion curves and their areas) of a compact model's relevance maps")
     p.add_argument("--compact", required=True, help="the compact file")
-    p.add_argument("--images", nargs="+", required=True, help="image files, or directories walked recursively for image files (sorted)")
     p.add_argument("--methods", nargs="+", choices=list(PERTURB_METHODS), default=["rollout"],
                    help="the maps put to the test; random: a seeded random order, the baseline")
     p.add_argument("--orders", nargs="+", choices=list(ORDERS), default=list(ORDERS),
@@ -311,24 +301,13 @@ def build_parser():
     p.add_argument("--target", type=CP._int_in(0, (1 << 20) - 1, "--target"), default=None,
                    help="the class whose probability is followed, in [0, num_labels); default: every image's own top-1 label on the intact image")
     p.add_argument("--seed", type=int, default=0, help="seed of the random baseline")
-    p.add_argument("--output", default=None, help="JSON-lines file; default: stdout")
-    p.add_argument("--batch_size", type=CP._int_in(1, 65535, "--batch_size"), default=64)
-    p.add_argument("--num_workers", type=int, default=8, help="decode threads (at most 16)")
-    p.add_argument("--precision", default="bf16")
-    p.add_argument("--preset", choices=list(CP.PRESETS), default="imagenet",
-                   help="imagenet: resize, centre crop, ImageNet mean / std; cifar: square resize, mean / std 0.5")
-    p.add_argument("--interpolation", choices=list(INTERPOLATIONS), default="bilinear")
-    p.add_argument("--crop_pct", type=CP._crop_pct_arg, default=None,
-                   help="imagenet preset: resize the short side to floor(img_size / crop_pct) before the centre crop; default: img_size * 256 // 224")
-    p.add_argument("--num_labels", type=CP._int_in(1, 1 << 20, "--num_labels"), default=None,
-                   help="the valid logits (the rest of the head is padding); default: the file's num_classes")
+    CP.add_image_file_flags(p, topk=False, classes=False)
     return p
 
 
 def main(argv: Optional[Sequence[str]] = None):
     """One JSON line per record of ``evaluate`` to --output (or stdout); returns the summaries.  With ``attribution`` among the methods a
     file with more than 256 tokens fails before any image is listed."""
-    import sys
     from . import data
     args = build_parser().parse_args(argv)
     methods, orders = _check_methods(args.methods, args.orders)
@@ -336,18 +315,17 @@ def main(argv: Optional[Sequence[str]] = None):
     export = CP.load_compact(args.compact)
     modules = build_modules(export, methods, args.precision, dev)
     files = data.list_images(args.images)
-    out = open(args.output, "w", encoding="utf-8") if args.output else sys.stdout
     summaries = []
-    try:
+
+    def records():
         for rec in evaluate(export, files, methods=methods, orders=orders, steps=args.steps, target=args.target, seed=args.seed,
                             precision=args.precision, preset=args.preset, interpolation=args.interpolation, crop_pct=args.crop_pct,
                             num_labels=args.num_labels, batch_size=args.batch_size, num_workers=args.num_workers, modules=modules):
-            out.write(json.dumps(rec) + "\n")
             if "images" in rec:
                 summaries.append(rec)
-    finally:
-        if out is not sys.stdout:
-            out.close()
+            yield rec
+
+    CP.write_records(records(), args.output)
     return summaries
 
 

@@ -22,8 +22,6 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
-import math
 import os
 from typing import Optional, Sequence
 
@@ -36,13 +34,6 @@ METHODS = ("saliency", "gradxinput", "ig")
 BASELINES = ("mean", "black")
 MAX_TOKENS = 256                                    # compact_attribution.MAX_TOKENS: the attention backward at a value width
 MAX_CHUNK_IMAGES = 64                               # the default chunk of integrated_gradients holds at most this many interpolated images
-
-
-def _num_labels(cfg, num_labels):
-    nl = cfg["num_classes"] if num_labels is None else int(num_labels)
-    if not 1 <= nl <= cfg["num_classes"]:
-        raise ValueError(f"num_labels {nl} must lie in [1, {cfg['num_classes']}] (the model's head)")
-    return nl
 
 
 def _check_steps(steps, chunk):
@@ -100,7 +91,7 @@ def reference_input_grad(export: dict, x: torch.Tensor, target=None, num_labels=
     ``compact._reference_walk``'s network.  ``target``: an int, or B indices; None: the first maximum of the eval logits over the first
     ``num_labels`` columns (default num_classes)."""
     cfg = CP.check_export(export)["cfg"]
-    nl = _num_labels(cfg, num_labels)
+    nl = CP.num_labels(cfg, num_labels)
     with torch.enable_grad():
         xg = x.detach().clone().requires_grad_(True)
         logits = _eval_logit_graph(export, xg)
@@ -115,7 +106,7 @@ def reference_integrated_gradients(export: dict, x: torch.Tensor, target=None, n
     midpoint rule ``alpha_s = (s + 1/2) / steps``, s ascending.  ``baseline``: None (zeros), a ``[C]`` colour or ``[B, C, S, S]``.
     ``y`` / ``y_baseline``: the target's eval logit at ``x`` / at the baseline; ``ig.sum((1, 2, 3))`` tends to their difference as steps grow."""
     cfg = CP.check_export(export)["cfg"]
-    nl = _num_labels(cfg, num_labels)
+    nl = CP.num_labels(cfg, num_labels)
     steps, _ = _check_steps(steps, None)
     x0 = _baseline_image(baseline, x)
     x0 = torch.zeros_like(x) if x0 is None else x0
@@ -181,7 +172,7 @@ class CompactPixelViT(CompactAttributionViT):
         from . import ops
         if (x is None) == (patches is None):
             raise ValueError("patch rows stand in for the image batch: pass one of x / patches")
-        nl = _num_labels(self._export["cfg"], num_labels)
+        nl = CP.num_labels(self._export["cfg"], num_labels)
         if x is not None:
             x = self._prep(x)
         B = x.shape[0] if x is not None else self._prep_patches(patches)
@@ -205,7 +196,7 @@ class CompactPixelViT(CompactAttributionViT):
         ``chunk``: default the largest divisor of ``steps`` with ``chunk * B <= 64`` images (at least 1)."""
         from . import ops
         cfg = self._export["cfg"]
-        nl = _num_labels(cfg, num_labels)
+        nl = CP.num_labels(cfg, num_labels)
         steps, chunk = _check_steps(steps, chunk)
         x = self._prep(x)
         B, dev = x.shape[0], self._flat.device
@@ -313,7 +304,7 @@ def explain_pixels(model, files, *, method="saliency", steps=32, baseline="mean"
     classes = None if classes is None else list(classes)
     if num_labels is None and classes is not None:
         num_labels = len(classes)
-    nl, topk = _num_labels(c, num_labels), int(topk)
+    nl, topk = CP.num_labels(c, num_labels), int(topk)
     if classes is not None and len(classes) < nl:
         raise ValueError(f"{len(classes)} class names for {nl} labels")
     if not 1 <= topk <= min(CP.MAX_TOPK, nl):
@@ -364,11 +355,9 @@ def explain_pixels(model, files, *, method="saliency", steps=32, baseline="mean"
 
 # ---- command line ------------------------------------------------------------------------------------------------------------------------
 def build_parser():
-    from .data import INTERPOLATIONS
     p = argparse.ArgumentParser(prog="python -m uvc_amd.compact_pixel",
                                 description="Pixel-resolution maps of a compact model: saliency, gradient x input, integrated gradients")
     p.add_argument("--compact", required=True, help="the compact file")
-    p.add_argument("--images", nargs="+", required=True, help="image files, or directories walked recursively for image files (sorted)")
     p.add_argument("--method", choices=list(METHODS), required=True,
                    help="saliency: |dy/dx|; gradxinput: |x dy/dx|; ig: integrated gradients from the baseline to the image")
     p.add_argument("--steps", type=CP._int_in(1, 4096, "--steps"), default=32, help="ig: points of the midpoint rule")
@@ -376,29 +365,15 @@ def build_parser():
                    help="ig: mean = the dataset's mean colour (zeros in the normalised input, what compact_perturb removes patches to); black")
     p.add_argument("--target", type=CP._int_in(0, (1 << 20) - 1, "--target"), default=None,
                    help="the class explained, in [0, num_labels); default: every image's own top-1 label among --num_labels")
-    p.add_argument("--output", default=None, help="JSON-lines file; default: stdout")
     p.add_argument("--overlay_dir", default=None, help="write <index>_<basename>.png per readable image: the model's view with the patch map in red")
     p.add_argument("--pixel_dir", default=None, help="write <index>_<basename>.png per readable image: the pixel map, greyscale, divided by its maximum")
-    p.add_argument("--topk", type=CP._int_in(1, CP.MAX_TOPK, "--topk"), default=5)
-    p.add_argument("--batch_size", type=CP._int_in(1, 65535, "--batch_size"), default=64)
-    p.add_argument("--num_workers", type=int, default=8, help="decode threads (at most 16)")
-    p.add_argument("--precision", default="bf16")
-    p.add_argument("--preset", choices=list(CP.PRESETS), default="imagenet",
-                   help="imagenet: resize, centre crop, ImageNet mean / std; cifar: square resize, mean / std 0.5")
-    p.add_argument("--interpolation", choices=list(INTERPOLATIONS), default="bilinear")
-    p.add_argument("--crop_pct", type=CP._crop_pct_arg, default=None,
-                   help="imagenet preset: resize the short side to floor(img_size / crop_pct) before the centre crop; default: img_size * 256 // 224")
-    p.add_argument("--classes", default=None, help="class names: one per line, or a JSON list")
-    p.add_argument("--num_labels", type=CP._int_in(1, 1 << 20, "--num_labels"), default=None,
-                   help="the valid logits (the rest of the head is padding); default: the length of --classes, else the file's num_classes")
+    CP.add_image_file_flags(p)
     return p
 
 
 def main(argv: Optional[Sequence[str]] = None):
     """One JSON line per image to --output (or stdout), then ``predict``'s summary line ``{"images", "errors", "batches", "img_per_s"}``,
     which is returned.  A file with more than 256 tokens fails before any image is listed or read."""
-    import sys
-    import time
     from . import data
     args = build_parser().parse_args(argv)
     export = CP.load_compact(args.compact)
@@ -407,24 +382,11 @@ def main(argv: Optional[Sequence[str]] = None):
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
     model = CompactPixelViT(export, precision=args.precision, device=dev)
     files = data.list_images(args.images)
-    out = open(args.output, "w", encoding="utf-8") if args.output else sys.stdout
-    n = nerr = 0
-    t0 = time.perf_counter()
-    try:
-        for rec in explain_pixels(model, files, method=args.method, steps=args.steps, baseline=args.baseline, target=args.target,
-                                  overlay_dir=args.overlay_dir, pixel_dir=args.pixel_dir, topk=args.topk, batch_size=args.batch_size,
-                                  preset=args.preset, interpolation=args.interpolation, crop_pct=args.crop_pct, num_labels=args.num_labels,
-                                  classes=classes, num_workers=args.num_workers):
-            out.write(json.dumps(rec) + "\n")
-            n += 1
-            nerr += "error" in rec
-        dt = time.perf_counter() - t0
-        summary = dict(images=n, errors=nerr, batches=math.ceil(n / args.batch_size), img_per_s=n / dt if dt > 0 else 0.0)
-        out.write(json.dumps(summary) + "\n")
-    finally:
-        if out is not sys.stdout:
-            out.close()
-    return summary
+    recs = explain_pixels(model, files, method=args.method, steps=args.steps, baseline=args.baseline, target=args.target,
+                          overlay_dir=args.overlay_dir, pixel_dir=args.pixel_dir, topk=args.topk, batch_size=args.batch_size, preset=args.preset,
+                          interpolation=args.interpolation, crop_pct=args.crop_pct, num_labels=args.num_labels, classes=classes,
+                          num_workers=args.num_workers)
+    return CP.write_records(recs, args.output, batch_size=args.batch_size)
 
 
 if __name__ == "__main__":

@@ -27,6 +27,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import compact as CP
+from . import compact_tools as TL
 from . import compact_transfer as CT
 
 PAD_BIAS = -1e4                                     # the bias of a head's padding rows: `compact eval` takes its argmax over all num_classes logits
@@ -68,7 +69,7 @@ class DeviceEvaluator:
     ``prepare`` moves a bank's features to the device in the precision's operand type once."""
 
     def __init__(self, classes, precision="bf16", chunk_rows=None, device=None):
-        self.device = CT._device(device)
+        self.device = TL.device(device)
         self.classes, self.precision, self.chunk_rows = int(classes), precision, chunk_rows
         self.rows = -(-self.classes // CT.HEAD_MULTIPLE) * CT.HEAD_MULTIPLE
         self.dtype = torch.float32
@@ -115,29 +116,19 @@ def fit_probe(features, labels, classes, l2, *, bias=True, max_iter=1000, histor
         if bias and init[1] is not None:
             b[:classes] = init[1][:classes].to(b)
     params = [W.requires_grad_()] + ([b.requires_grad_()] if bias else [])
-    tol_change = (0.0 if dtype == torch.float64 else 1e-11) if tol_change is None else tol_change      # (the device's F is summed in float64: changes below torch's default 1e-9 still carry signal)
-    opt = torch.optim.LBFGS(params, lr=1.0, max_iter=int(max_iter), max_eval=int(max_iter) * 5 // 4 + 1, history_size=int(history),
-                            tolerance_grad=float(tol_grad), tolerance_change=float(tol_change), line_search_fn="strong_wolfe")
-    last = {}
 
-    def closure():
-        with torch.no_grad():
-            F, dW, db, hits = evaluator(W.detach(), None if b is None else b.detach(), X, y, l2)
+    def evaluate():
+        F, dW, db, hits = evaluator(W.detach(), None if b is None else b.detach(), X, y, l2)
         W.grad = dW.to(W).reshape(W.shape)
         if bias:
             b.grad = db.to(b)
-        F = torch.as_tensor(F, dtype=torch.float64)
-        last.update(F=F, hits=hits)
-        return F
+        return F, hits
 
-    opt.step(closure)
-    F = closure()                                                    # the objective, gradient and hits AT the returned point
-    st = opt.state[params[0]]
+    F, last, g, iterations, evaluations = TL.lbfgs(params, evaluate, max_iter=max_iter, history=history, tol_grad=tol_grad, tol_change=tol_change,
+                                                   dtype=dtype)
     m = int(((y >= 0) & (y < classes)).sum())
-    g = max(float(p.grad.abs().max()) for p in params)
-    return dict(W=W.detach()[:classes].cpu().clone(), b=None if b is None else b.detach()[:classes].cpu().clone(), F=float(F),
-                top1=100.0 * int(last["hits"]) / m if m else 0.0, grad_inf=g, iterations=int(st.get("n_iter", 0)),
-                evaluations=int(st.get("func_evals", 0)) + 1, rows=m)
+    return dict(W=W.detach()[:classes].cpu().clone(), b=None if b is None else b.detach()[:classes].cpu().clone(), F=F,
+                top1=100.0 * int(last["hits"]) / m if m else 0.0, grad_inf=g, iterations=iterations, evaluations=evaluations, rows=m)
 
 
 def l2_grid(count, lo=1e-6, hi=1e-1):
@@ -219,35 +210,15 @@ def check_probe_bank(bank, export, bias, data_classes=None):
     return bank
 
 
-@torch.no_grad()
-def embed_raw(model, loader):
-    """``compact_transfer.embed_dataset`` with the un-normalised features."""
-    feats, labels = [], []
-    for x, y in loader:
-        feats.append(model.features(x, normalize=False)[1])
-        labels.append(y.to(torch.int64))
-    if not feats:
-        raise ValueError("the loader yields no batch")
-    return torch.cat(feats), torch.cat(labels)
+def make_raw_bank(features, labels, data_classes, **meta):
+    """``compact_transfer.make_bank``'s dict of the UN-normalised features plus ``"normalized": False``."""
+    return TL.make_bank(labels, data_classes, features=features, normalized=False, **meta)
 
 
 def embed(export_or_path, args, dev=None):
-    """``embed``: ``compact_transfer.make_bank``'s dict of the raw features plus ``"normalized": False``, and the summary."""
-    export = CP.load_compact(export_or_path) if not isinstance(export_or_path, dict) else CP.check_export(export_or_path)
-    dev = CT._device(dev)
-    model, loader, classes = CT._model_and_loader(export, args, args.split, dev)
-    with torch.cuda.device(dev):
-        t0 = time.perf_counter()
-        feats, labels = embed_raw(model, loader)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-    bank = CT.make_bank(feats, labels, classes, **CT._meta(export, args, args.split))
-    bank["normalized"] = False                                       # (make_bank drops unknown meta keys: a top-level key, added after it)
-    if getattr(args, "output", None):
-        torch.save(bank, args.output)
-    n = int(feats.shape[0])
-    return bank, dict(output=getattr(args, "output", None), images=n, img_per_s=n / dt if dt > 0 else 0.0, data_classes=classes,
-                      embed_dim=int(feats.shape[1]), normalized=False)
+    """``embed``: ``make_raw_bank``'s dict of ``args.split`` (saved to ``args.output`` when given), and the summary."""
+    return TL.bank_command(export_or_path, args, dev, lambda model, x: (model.features(x, normalize=False)[1],), make_raw_bank,
+                           lambda bank: dict(embed_dim=int(bank["features"].shape[1]), normalized=False))
 
 
 # ---- the file ---------------------------------------------------------------------------------------------------------------------
@@ -285,19 +256,11 @@ def file_head(export, classes):
 
 
 # ---- the commands -----------------------------------------------------------------------------------------------------------------
-def split_bank(bank, fraction, seed):
-    """``(train, val)`` as ``(features, labels)``: the last ``floor(fraction * n)`` rows of a CPU ``torch.Generator(seed)`` permutation are held out."""
-    n = bank["features"].shape[0]
-    k = int(math.floor(float(fraction) * n))
-    if not 0 < k < n:
-        raise ValueError(f"--val_fraction {fraction} holds out {k} of {n} rows")
-    perm = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed)))
-    tr, va = perm[:n - k], perm[n - k:]
-    return (bank["features"][tr], bank["labels"][tr]), (bank["features"][va], bank["labels"][va])
+split_bank = TL.split_bank
 
 
 def fit_command(args, dev=None):
-    export = CP.load_compact(args.compact) if not isinstance(args.compact, dict) else CP.check_export(args.compact)
+    export = CP.as_export(args.compact)
     bank = CT.load_bank(args.bank) if not isinstance(args.bank, dict) else args.bank
     bias = bool(args.bias)
     check_probe_bank(bank, export, bias)
@@ -316,7 +279,7 @@ def fit_command(args, dev=None):
         raise ValueError("--l2 must not be negative")
     if len(values) > 1 and val is None:
         raise ValueError("more than one l2 value needs --val_bank or --val_fraction to choose by")
-    dev = CT._device(dev)
+    dev = TL.device(dev)
     with torch.cuda.device(dev):
         t0 = time.perf_counter()
         ev = DeviceEvaluator(classes, args.precision, args.chunk_rows, dev)
@@ -348,14 +311,14 @@ def fit_command(args, dev=None):
 
 
 def score_command(args, dev=None):
-    export = CP.load_compact(args.compact) if not isinstance(args.compact, dict) else CP.check_export(args.compact)
+    export = CP.as_export(args.compact)
     bank = CT.load_bank(args.bank) if not isinstance(args.bank, dict) else args.bank
     CT.check_bank(bank, export)
     classes = int(bank["data_classes"])
     W, b = file_head(export, classes)
     if bank_is_normalized(bank) and bool((b != 0).any()):
         raise ValueError("the bank holds normalized features and the file's head has a non-zero bias: score it on a raw bank (python -m uvc_amd.compact_probe embed)")
-    dev = CT._device(dev)
+    dev = TL.device(dev)
     with torch.cuda.device(dev):
         X = CT.operand(bank["features"].to(dev), args.precision).contiguous()
         top1 = score_head(W, b, X, bank["labels"].to(dev), classes)
@@ -363,36 +326,17 @@ def score_command(args, dev=None):
                 normalized_bank=bank_is_normalized(bank), top1=top1)
 
 
-def _fraction(v):
-    f = float(v)
-    if not 0.0 < f < 1.0:
-        raise argparse.ArgumentTypeError(f"--val_fraction must lie in (0, 1), not {v}")
-    return f
-
-
 def build_parser():
-    from .data import INTERPOLATIONS
     p = argparse.ArgumentParser(prog="python -m uvc_amd.compact_probe", description="A linear probe on a compact model's frozen features")
     sub = p.add_subparsers(dest="cmd", required=True)
     e, f, s = (sub.add_parser(n) for n in ("embed", "fit", "score"))
     for q in (e, f, s):
         q.add_argument("--compact", required=True, help="the compact file")
         q.add_argument("--precision", choices=["bf16", "fp32"], default="bf16")
-    e.add_argument("--dataset", choices=["cifar10", "cifar100", "imagenet"], default="imagenet")
-    e.add_argument("--data_dir", default=None)
-    e.add_argument("--eval_batch_size", type=CP._int_in(1, 65535, "--eval_batch_size"), default=256)
-    e.add_argument("--num_workers", type=int, default=8, help="decode threads (at most 16)")
-    e.add_argument("--interpolation", choices=list(INTERPOLATIONS), default="bilinear")
-    e.add_argument("--crop_pct", type=CP._crop_pct_arg, default=None)
-    e.add_argument("--packed_dir", default=None, help="DIR/train.uvcpack and DIR/val.uvcpack replace the folders or pickles under --data_dir")
-    e.add_argument("--resident", type=int, default=0, choices=[0, 1], help="1: keep the split's pixels on the device")
-    e.add_argument("--split", choices=["train", "test"], default="train")
+    TL.add_dataset_flags(e, precision=False)
     e.add_argument("--output", required=True, help="the bank file: raw features, labels, data_classes, meta, normalized = False")
     f.add_argument("--bank", required=True, help="the bank to fit on (compact_probe embed --split train)")
-    v = f.add_mutually_exclusive_group()
-    v.add_argument("--val_bank", default=None, help="a bank to choose l2 on")
-    v.add_argument("--val_fraction", type=_fraction, default=None, help="hold out this fraction of --bank (a --seed permutation's last rows)")
-    f.add_argument("--seed", type=int, default=0)
+    TL.add_val_flags(f, "a bank to choose l2 on")
     g = f.add_mutually_exclusive_group()
     g.add_argument("--l2", type=float, nargs="+", default=None, help="the regulariser value(s); default 1e-3")
     g.add_argument("--l2_grid", type=CP._int_in(1, 1000, "--l2_grid"), default=None, help="this many values, log-spaced in [--l2_min, --l2_max]")
@@ -410,8 +354,7 @@ def build_parser():
 def main(argv: Optional[Sequence[str]] = None):
     args = build_parser().parse_args(argv)
     if args.cmd == "embed":
-        if not args.data_dir and not args.packed_dir:
-            raise SystemExit("need --data_dir or --packed_dir")
+        TL.need_data(args)
         summary = embed(args.compact, args)[1]
     else:
         summary = fit_command(args) if args.cmd == "fit" else score_command(args)

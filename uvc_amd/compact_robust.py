@@ -30,7 +30,8 @@ from typing import Optional, Sequence
 import torch
 
 from . import compact as CP
-from .compact_pixel import CompactPixelViT, _eval_logit_graph, _num_labels, _pick_target, check_tokens
+from . import compact_tools as TL
+from .compact_pixel import CompactPixelViT, _eval_logit_graph, _pick_target, check_tokens
 
 LOSSES = ("ce", "margin")                           # ops.LOSS_KINDS: uvc_loss_seed's kind 0 / 1
 ATTACKS = ("fgsm", "pgd")
@@ -98,7 +99,7 @@ def reference_loss_grad(export: dict, x: torch.Tensor, labels, num_labels=None, 
     ``lse(z) - z_y`` or "margin" ``z_j - z_y`` (j the first maximum over the other labels) of the eval logits z over the first ``num_labels``
     columns on ``compact._reference_walk``'s network, and ``grad = d loss_b / d x`` of every image's own loss."""
     cfg = CP.check_export(export)["cfg"]
-    nl = _num_labels(cfg, num_labels)
+    nl = CP.num_labels(cfg, num_labels)
     check_attack(0, None, 0, loss, nl)
     y = _check_labels(labels, x.shape[0], nl).to(x.device)
     with torch.enable_grad():
@@ -120,7 +121,7 @@ def reference_attack(export: dict, x: torch.Tensor, labels, num_labels=None, *, 
     bounds of ``linf_bounds`` taken to x's dtype.  ``start``: None, or the random start's draw in [-1, 1) of x's shape.  ``info`` as
     ``attack``'s."""
     cfg = CP.check_export(export)["cfg"]
-    nl = _num_labels(cfg, num_labels)
+    nl = CP.num_labels(cfg, num_labels)
     eps, alpha, steps = check_attack(eps, alpha, steps, loss, nl)
     y = _check_labels(labels, x.shape[0], nl).to(x.device)
     view = lambda t: t.to(device=x.device, dtype=x.dtype).view(1, -1, 1, 1)
@@ -184,7 +185,7 @@ class CompactRobustViT(CompactPixelViT):
             raise ValueError("patch rows stand in for the image batch: pass one of x / patches")
         if labels is None:
             raise ValueError("loss_grad needs labels")
-        nl = _num_labels(self._export["cfg"], num_labels)
+        nl = CP.num_labels(self._export["cfg"], num_labels)
         check_attack(0, None, 0, loss, nl)
         if x is not None:
             x = self._prep(x)
@@ -211,7 +212,7 @@ class CompactRobustViT(CompactPixelViT):
         An iterate is one ``uvc_vit_compact_loss_grad`` call on patch rows and one ``uvc_pgd_step``; one plain forward scores the last."""
         from . import ops
         cfg = self._export["cfg"]
-        nl = _num_labels(cfg, num_labels)
+        nl = CP.num_labels(cfg, num_labels)
         eps, alpha, steps = check_attack(eps, alpha, steps, loss, nl)
         x = self._prep(x)
         B, dev = x.shape[0], self._flat.device
@@ -282,19 +283,17 @@ def evaluate(export_or_path, args, dev=None):
     """The command's record: ``{"images", "attack", "eps", "alpha", "steps", "loss", "labels", "clean_top1", "robust_top1",
     "mean_loss_clean", "mean_loss_adv", "img_per_s"}`` plus ``compact._report``'s widths, parameters and MACs.  ``clean_top1``: the labels
     hit on the images themselves (100 with ``--labels own``); ``robust_top1``: hit at every iterate of the attack."""
-    from . import data, ops
-    from .compact_transfer import _device
+    from . import ops
     eps, alpha, steps, random_start = attack_plan(args)
-    export = CP.load_compact(export_or_path) if not isinstance(export_or_path, dict) else CP.check_export(export_or_path)
+    export = CP.as_export(export_or_path)
     check_tokens(export)
     known = {"cifar10": 10, "cifar100": 100}.get(args.dataset)
     if known is not None:                                # the data's label set against the model's head, before any data is read
-        check_attack(eps, alpha, steps, args.loss, _num_labels(export["cfg"], known))
-    dev = _device(dev)
-    args.img_size = export["cfg"]["img_size"]
+        check_attack(eps, alpha, steps, args.loss, CP.num_labels(export["cfg"], known))
+    dev = TL.device(dev)
     model = CompactRobustViT(export, precision=args.precision, device=dev)
-    loader, classes = data.build_eval_loader(args, args.split)
-    nl = _num_labels(export["cfg"], classes)
+    loader, classes = TL.eval_loader(export, args, args.split)
+    nl = CP.num_labels(export["cfg"], classes)
     check_attack(eps, alpha, steps, args.loss, nl)
     mean, std = preset_stats(args.dataset)
     n = clean = robust = 0
@@ -324,19 +323,9 @@ def evaluate(export_or_path, args, dev=None):
 
 
 def build_parser():
-    from .data import INTERPOLATIONS
     p = argparse.ArgumentParser(prog="python -m uvc_amd.compact_robust", description="Top-1 of a compact model under an L-infinity FGSM or PGD attack")
     p.add_argument("--compact", required=True, help="the compact file")
-    p.add_argument("--dataset", choices=["cifar10", "cifar100", "imagenet"], default="imagenet")
-    p.add_argument("--data_dir", default=None)
-    p.add_argument("--eval_batch_size", type=CP._int_in(1, 65535, "--eval_batch_size"), default=64)
-    p.add_argument("--num_workers", type=int, default=8, help="decode threads (at most 16)")
-    p.add_argument("--precision", choices=["bf16", "fp32"], default="bf16")
-    p.add_argument("--interpolation", choices=list(INTERPOLATIONS), default="bilinear")
-    p.add_argument("--crop_pct", type=CP._crop_pct_arg, default=None)
-    p.add_argument("--packed_dir", default=None, help="DIR/train.uvcpack and DIR/val.uvcpack replace the folders or pickles under --data_dir")
-    p.add_argument("--resident", type=int, default=0, choices=[0, 1], help="1: keep the split's pixels on the device")
-    p.add_argument("--split", choices=["train", "test"], default="test")
+    TL.add_dataset_flags(p, eval_batch_size=64, split_default="test")
     p.add_argument("--attack", choices=list(ATTACKS), default="pgd", help="fgsm: one step of eps; pgd: --steps projected steps")
     p.add_argument("--eps", type=float, default=4.0, help="the L-infinity radius in units of 1/255 of the pixel range")
     p.add_argument("--alpha", type=float, default=None, help="the step in the same units; default: eps (fgsm), 2.5 eps / steps (pgd)")
@@ -354,8 +343,7 @@ def main(argv: Optional[Sequence[str]] = None):
     fewer than 2 labels, labels outside the model's head -- come before any image is read."""
     args = build_parser().parse_args(argv)
     attack_plan(args)
-    if not args.data_dir and not args.packed_dir:
-        raise SystemExit("need --data_dir or --packed_dir")
+    TL.need_data(args)
     summary = evaluate(args.compact, args)
     print(json.dumps(summary))
     return summary

@@ -67,10 +67,10 @@ def padding_masks(export: dict):
 
 
 def with_state(export: dict, state_dict) -> dict:
-    """A version-1 compact dict with the source file's ``cfg`` / ``blocks`` and the given weights (float32, CPU)."""
+    """``compact.with_state`` with the given weights taken to float32 on the CPU, in the source file's shapes."""
     CP.check_export(export)
-    sd = {k: state_dict[k].detach().to(device="cpu", dtype=torch.float32).reshape(v.shape).clone() for k, v in export["state_dict"].items()}
-    return dict(format=CP.FORMAT, version=CP.VERSION, cfg=copy.deepcopy(export["cfg"]), blocks=copy.deepcopy(export["blocks"]), state_dict=sd)
+    return CP.with_state(export, {k: state_dict[k].detach().to(device="cpu", dtype=torch.float32).reshape(v.shape).clone()
+                                  for k, v in export["state_dict"].items()})
 
 
 class _CompactFunction(torch.autograd.Function):

@@ -26,6 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from . import compact as CP
+from . import compact_tools as TL
 
 MAX_K = 64                                          # uvc_knn_topk's and uvc_knn_vote's limit
 HEAD_MULTIPLE = 8                                   # the engine's head widths (data.build_loaders: 10 -> 16, 100 -> 104)
@@ -86,17 +87,9 @@ def reference_vote(sims, idx, labels, num_classes: int, temperature: float = 0.0
 
 
 # ---- features of a dataset ----------------------------------------------------------------------------------------------------------
-@torch.no_grad()
-def embed_dataset(model, loader):
-    """``(features float32 [n, D] on the device, normalised; labels int64 [n] on the device)`` of every sample ``loader`` yields, in
-    its order (an eval loader: dataset order, the short last batch included)."""
-    feats, labels = [], []
-    for x, y in loader:
-        feats.append(model.features(x)[1])
-        labels.append(y.to(torch.int64))
-    if not feats:
-        raise ValueError("the loader yields no batch")
-    return torch.cat(feats), torch.cat(labels)
+def _features(model, x):
+    """The walk's call: the normalised float32 features of one batch."""
+    return (model.features(x)[1],)
 
 
 def operand(features, precision):
@@ -116,18 +109,12 @@ def knn_classify(queries, bank, labels, num_classes, k=20, temperature=0.07):
 
 
 # ---- the bank file ------------------------------------------------------------------------------------------------------------------
-META_KEYS = ("img_size", "dataset", "split", "interpolation", "crop_pct", "precision", "embed_dim")
+META_KEYS = TL.META_KEYS
 
 
 def make_bank(features, labels, data_classes, **meta):
-    """The bank file's dict: tensors and plain values only."""
-    features = features.detach().float().cpu().contiguous()
-    labels = labels.detach().to(torch.int64).cpu().contiguous()
-    if features.dim() != 2 or labels.shape != (features.shape[0],):
-        raise ValueError("features [n, D] and one label per row")
-    meta = {k: meta.get(k) for k in META_KEYS}
-    meta["embed_dim"] = int(features.shape[1])
-    return dict(features=features, labels=labels, data_classes=int(data_classes), meta=meta)
+    """The bank file's dict (``compact_tools.make_bank``): ``{"features", "labels", "data_classes", "meta"}``."""
+    return TL.make_bank(labels, data_classes, features=features, **meta)
 
 
 def load_bank(path) -> dict:
@@ -180,63 +167,31 @@ def rehead(export: dict, bank: Optional[dict], init: str = "mean", scale: float 
         if name + ".weight" in sd:
             sd[name + ".weight"] = W.to(sd[name + ".weight"].dtype)
             sd[name + ".bias"] = torch.zeros(width, dtype=sd[name + ".bias"].dtype)
-    cfg = dict(export["cfg"])
-    cfg["num_classes"] = width
-    out = {k: v for k, v in export.items() if k not in ("cfg", "state_dict", "blocks")}
-    out.update(cfg=cfg, blocks=[dict(b) for b in export["blocks"]], state_dict=sd)
-    return CP.check_export(out), top1
+    return CP.with_state(export, sd, dict(export["cfg"], num_classes=width)), top1
 
 
 # ---- the commands ---------------------------------------------------------------------------------------------------------------------
-def _model_and_loader(export, args, split, dev):
-    from . import data
-    args.img_size = export["cfg"]["img_size"]
-    model = getattr(args, "_model", None)
-    if model is None:
-        model = args._model = CP.CompactVisionTransformer(export, precision=args.precision, device=dev)
-    loader, classes = data.build_eval_loader(args, split)
-    return model, loader, classes
-
-
-def _meta(export, args, split):
-    return dict(img_size=export["cfg"]["img_size"], dataset=args.dataset, split=split, interpolation=args.interpolation, crop_pct=args.crop_pct,
-                precision=args.precision)
-
-
 def embed(export_or_path, args, dev=None):
     """``embed``: the bank dict of ``args.split`` (saved to ``args.output`` when given) and the summary ``{"images", "img_per_s", ...}``."""
-    export = CP.load_compact(export_or_path) if not isinstance(export_or_path, dict) else CP.check_export(export_or_path)
-    dev = _device(dev)
-    model, loader, classes = _model_and_loader(export, args, args.split, dev)
-    with torch.cuda.device(dev):
-        t0 = time.perf_counter()
-        feats, labels = embed_dataset(model, loader)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-    bank = make_bank(feats, labels, classes, **_meta(export, args, args.split))
-    if getattr(args, "output", None):
-        torch.save(bank, args.output)
-    n = int(feats.shape[0])
-    return bank, dict(output=getattr(args, "output", None), images=n, img_per_s=n / dt if dt > 0 else 0.0, data_classes=classes,
-                      embed_dim=int(feats.shape[1]))
+    return TL.bank_command(export_or_path, args, dev, _features, make_bank, lambda bank: dict(embed_dim=int(bank["features"].shape[1])))
 
 
 def evaluate(export_or_path, args, dev=None):
     """``knn``: the weighted k-NN top-1 of the test split against the train split's features (or ``args.bank``): the summary
     ``{"k", "temperature", "bank_images", "query_images", "top1", "img_per_s"}`` plus ``compact._report``'s widths, parameters and MACs.
     The bank is held on the device in the precision's operand type; the test split is embedded, searched and voted on batch by batch."""
-    export = CP.load_compact(export_or_path) if not isinstance(export_or_path, dict) else CP.check_export(export_or_path)
-    dev = _device(dev)
+    export = CP.as_export(export_or_path)
+    dev = TL.device(dev)
     if not 1 <= int(args.k) <= MAX_K:
         raise ValueError(f"--k must lie in [1, {MAX_K}], not {args.k}")
-    model, test_loader, classes = _model_and_loader(export, args, "test", dev)
+    model = CP.CompactVisionTransformer(export, precision=args.precision, device=dev)
+    test_loader, classes = TL.eval_loader(export, args, "test")
     with torch.cuda.device(dev):
         if getattr(args, "bank", None):
             bank = check_bank(load_bank(args.bank) if not isinstance(args.bank, dict) else args.bank, export, classes)
             feats, labels = bank["features"].to(dev), bank["labels"].to(dev)
         else:
-            _, train_loader, _ = _model_and_loader(export, args, "train", dev)
-            feats, labels = embed_dataset(model, train_loader)
+            (feats,), labels = TL.walk(TL.eval_loader(export, args, "train")[0], lambda x: _features(model, x))
         bank_t = operand(feats, args.precision).contiguous()
         del feats
         hits = torch.zeros((), dtype=torch.int64, device=dev)
@@ -255,35 +210,15 @@ def evaluate(export_or_path, args, dev=None):
                 top1=100.0 * int(hits) / n, img_per_s=n / dt if dt > 0 else 0.0, **CP._report(export))
 
 
-def _device(dev):
-    from . import _lib as L
-    if dev is None:
-        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-    dev = torch.device(dev)
-    if dev.type != "cuda":
-        raise L.UvcHipError("uvc_amd models run on MI355X only (no CPU fallback)")
-    return dev
-
-
 def build_parser():
-    from .data import INTERPOLATIONS
     p = argparse.ArgumentParser(prog="python -m uvc_amd.compact_transfer",
                                 description="Features, k-NN top-1 and a new head for a compact model on another dataset")
     sub = p.add_subparsers(dest="cmd", required=True)
     for name in ("embed", "knn", "rehead"):
         s = sub.add_parser(name)
         s.add_argument("--compact", required=True, help="the compact file")
-        s.add_argument("--dataset", choices=["cifar10", "cifar100", "imagenet"], default="imagenet")
-        s.add_argument("--data_dir", default=None)
-        s.add_argument("--eval_batch_size", type=CP._int_in(1, 65535, "--eval_batch_size"), default=256)
-        s.add_argument("--num_workers", type=int, default=8, help="decode threads (at most 16)")
-        s.add_argument("--precision", choices=["bf16", "fp32"], default="bf16")
-        s.add_argument("--interpolation", choices=list(INTERPOLATIONS), default="bilinear")
-        s.add_argument("--crop_pct", type=CP._crop_pct_arg, default=None)
-        s.add_argument("--packed_dir", default=None, help="DIR/train.uvcpack and DIR/val.uvcpack replace the folders or pickles under --data_dir")
-        s.add_argument("--resident", type=int, default=0, choices=[0, 1], help="1: keep the split's pixels on the device")
+        TL.add_dataset_flags(s, split=name == "embed")                 # (rehead reads none of them and goes on accepting them)
     e, k, r = (sub.choices[n] for n in ("embed", "knn", "rehead"))
-    e.add_argument("--split", choices=["train", "test"], default="train")
     e.add_argument("--output", required=True, help="the bank file: features, labels, data_classes, meta")
     k.add_argument("--bank", default=None, help="a bank of the train split (embed --split train); default: embed it now")
     k.add_argument("--k", type=CP._int_in(1, MAX_K, "--k"), default=20)
@@ -306,8 +241,7 @@ def main(argv: Optional[Sequence[str]] = None):
                        data_classes=int(bank["data_classes"]), class_mean_top1=top1)
         print(json.dumps(summary))
         return summary
-    if not args.data_dir and not args.packed_dir:
-        raise SystemExit("need --data_dir or --packed_dir")
+    TL.need_data(args)
     summary = embed(args.compact, args)[1] if args.cmd == "embed" else evaluate(args.compact, args)
     print(json.dumps(summary))
     return summary

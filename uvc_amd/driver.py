@@ -1,6 +1,8 @@
 """What the command-line drivers share (``cli`` = Stage 1, ``post_train`` = Stage 2, ``compact eval`` and ``compact finetune``): the data,
 Mixup and teacher flags, written once, the process-group set-up, the real-data loaders with their Mixup, and the top-1 validation loop.
 A flag of one of these blocks is added here and nowhere else; where the drivers' defaults differ, the call site says so.
+The stand-alone compact tools have two blocks of their own, kept the same way: ``compact_tools.add_dataset_flags`` (one split under the eval
+transform) and ``compact.add_image_file_flags`` (image files).
 """
 from __future__ import annotations
 
