@@ -612,6 +612,38 @@ int uvc_center_rows(const float* X, int64_t ldx, const void* labels, int32_t lab
                     float* out, int64_t ldo, void* stream);
 int uvc_rows_sqnorm_aug(float* Z, int64_t ldz, int64_t n, int32_t D, float* sq, void* stream);
 
+/* Two models on one split (python -m uvc_amd.compact_compare; Milani Fard et al. 2016, Yan et al. 2021, Hooker et al. 2019, Stanton et al.
+ * 2021): uvc_logits_pair_stats reads za float32 [n, lda] and zb float32 [n, ldb] ONCE -- of both, columns [0, C) are valid and the rest is
+ * never read into a result -- and labels [n] (int32, or int64 with labels_i64; may be NULL) and writes, per row, each output [n] that is
+ * not NULL (a NULL output is not wanted and not touched; not all may be NULL).  Per row and matrix, all in float32: m the FIRST maximum,
+ * d_c = z_c - m, S = sum_c exp(d_c) with the maximum's own term exactly 1, l_c = d_c - log S, p_c = exp(d_c) / S, 0 log 0 = 0:
+ *   top1_a, top1_b  int32   the first maximum's column
+ *   conf_a, conf_b  float32 1 / S
+ *   kl_ab           float32 sum_c p_a,c (l_a,c - l_b,c);  kl_ba likewise with a and b swapped
+ *   js              float32 max(0, 1/2 sum p_a (l_a - l_m) + 1/2 sum p_b (l_b - l_m)),  l_m = max(l_a, l_b) + log1p(exp(-|l_a - l_b|)) - log 2
+ *   tv              float32 1/2 sum_c |p_a,c - p_b,c|
+ *   nll_a, nll_b    float32 -l_y
+ *   rank_a, rank_b  int32   #{c < C : z_c > z_y or (z_c = z_y and c < y)}: 0 means the label is the top-1 under the first-maximum rule
+ *   rank_b_top1a    int32   the same count in zb for the column top1_a;  rank_a_top1b: in za for the column top1_b
+ * The differences of log-probabilities stay finite where log(p_a / p_b) would not: a 200-logit gap gives KL ~ 200, JS ~ log 2, TV ~ 1.
+ * Two equal rows give kl = js = tv = 0 exactly.  A label outside [0, C), or NULL labels: nll_* = NaN and rank_a = rank_b = -1, the rest is
+ * computed.  A NaN in a valid column of either row: every float output of the row NaN, every int output -1.  Logits are finite otherwise.
+ * Up to uvc_logits_pair_stats_reg_max() = 1024 columns a group of 1 .. 64 lanes holds both rows in registers, the next pair fetched before
+ * the current one is worked on; beyond, one workgroup takes a row pair (read three times, twice from cache).  16-byte loads when lda and
+ * ldb are multiples of 4 and za and zb 16-byte aligned, element by element otherwise -- the same bits either way.  No atomics, one writer
+ * per element, the same bits on a repeat and for a row alone or in a batch, 64-bit row offsets, workgroup counts functions of the shape
+ * alone (compare.hip).  za, zb not NULL, 1 <= n < 2^31, 1 <= C <= lda, ldb < 2^31 (UVC_ERR_ARG); C <= 65536 (UVC_ERR_UNSUPPORTED).  Every
+ * refusal happens before anything is launched. */
+typedef struct uvc_pair_stats_args {
+  const float* za; const float* zb; const void* labels;
+  int32_t* top1_a; int32_t* top1_b; float* conf_a; float* conf_b; float* kl_ab; float* kl_ba; float* js; float* tv; float* nll_a; float* nll_b;
+  int32_t* rank_a; int32_t* rank_b; int32_t* rank_b_top1a; int32_t* rank_a_top1b;
+  int64_t n, lda, ldb;
+  int32_t C, labels_i64;
+} uvc_pair_stats_args;
+int uvc_logits_pair_stats(const uvc_pair_stats_args* args, void* stream);
+int uvc_logits_pair_stats_reg_max(void);
+
 /* clip_grad_norm_(max_norm) + AdamW over flat float32 buffers (joint_train.py:428-429;
  * torch.optim.AdamW(lr, betas, eps, weight_decay) semantics, decoupled decay).
  * uvc_grad_sqnorm accumulates sum(g^2) of a segment into sq[0] (accumulate = 0 for the first segment) and leaves sqrt(sq[0]) -- the

@@ -138,6 +138,12 @@ class uvc_calib_args(C.Structure):
                [(n, C.c_int64) for n in ("workspace_bytes", "n", "ld")] + [(n, C.c_int32) for n in ("C", "scale_len", "labels_i64", "bins")]
 
 
+class uvc_pair_stats_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("za", "zb", "labels", "top1_a", "top1_b", "conf_a", "conf_b", "kl_ab", "kl_ba", "js", "tv", "nll_a", "nll_b",
+                                          "rank_a", "rank_b", "rank_b_top1a", "rank_a_top1b")] + \
+               [(n, C.c_int64) for n in ("n", "lda", "ldb")] + [(n, C.c_int32) for n in ("C", "labels_i64")]
+
+
 class uvc_knn_args(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("queries", "bank", "sims", "idx", "workspace")] + \
                [(n, C.c_int64) for n in ("workspace_bytes", "ldq", "ldb")] + \
@@ -267,6 +273,8 @@ _SIGNATURES = {
     "uvc_class_moments": [VP, I64, VP, I32, VP, I64, I32, I32, VP, VP, VP, I64, VP],
     "uvc_center_rows": [VP, I64, VP, I32, VP, I64, I32, I32, VP, I64, VP],
     "uvc_rows_sqnorm_aug": [VP, I64, I64, I32, VP, VP],
+    "uvc_logits_pair_stats": [C.POINTER(uvc_pair_stats_args), VP],
+    "uvc_logits_pair_stats_reg_max": [],
     "uvc_grad_sqnorm": [VP, I64, VP, VP, I32, VP],
     "uvc_adamw_step": [C.POINTER(uvc_adamw_args), VP],
     "uvc_scale_by_clip": [VP, I64, VP, F32, VP],

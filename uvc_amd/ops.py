@@ -1020,6 +1020,100 @@ def gauss_scores(X, whiten, mean0, wmeans=None, counts=None):
     return sq - 2.0 * sims[:, 0], kept[idx[:, 0].long()].to(torch.int32)
 
 
+PAIR_STATS = ("top1_a", "top1_b", "conf_a", "conf_b", "kl_ab", "kl_ba", "js", "tv", "nll_a", "nll_b", "rank_a", "rank_b", "rank_b_top1a",
+              "rank_a_top1b")
+PAIR_STATS_INT = ("top1_a", "top1_b", "rank_a", "rank_b", "rank_b_top1a", "rank_a_top1b")
+
+
+def logits_pair_stats_reg_max() -> int:
+    """The widest row pair ``logits_pair_stats`` holds in registers; one more column and a workgroup takes the pair."""
+    return int(L.lib().uvc_logits_pair_stats_reg_max())
+
+
+def logits_pair_stats(za, zb, labels=None, n_valid=None, outs=None):
+    """``{name: [n]}`` over ``PAIR_STATS``: per row of the float32 logits ``za`` [n, lda] and ``zb`` [n, ldb] (columns [0, n_valid) valid,
+    default: the narrower of the two), the top-1 columns, confidences, KL both ways, Jensen-Shannon, total variation, the label's NLL and
+    the ranks of the label and of the other model's top-1 -- one read of both (uvc_logits_pair_stats; include/uvc_kernels.h has the
+    formulas, the tie rule and the NaN rule).  ``PAIR_STATS_INT`` are int32, the rest float32.  ``labels``: contiguous int32 / int64 [n],
+    or None (NLL NaN, label ranks -1).  ``outs``: a dict of contiguous tensors to write into; with it, a name that is missing or None is
+    not wanted and not computed into anything."""
+    L.require_cuda(za, zb, labels)
+    n, ca, lda = _rows_f32(za, "logits_pair_stats: za")
+    nb, cb, ldb = _rows_f32(zb, "logits_pair_stats: zb")
+    if nb != n:
+        raise L.UvcHipError(f"logits_pair_stats: za has {n} rows and zb {nb}")
+    Cc = min(ca, cb) if n_valid is None else int(n_valid)
+    if Cc > min(ca, cb):
+        raise L.UvcHipError(f"logits_pair_stats: n_valid {Cc} is more than the logits' {min(ca, cb)} columns")
+    i64 = 0 if labels is None else _labels_1d(labels, n, "logits_pair_stats")
+    dev = za.device
+    if outs is None:
+        outs = {k: torch.empty(n, dtype=torch.int32 if k in PAIR_STATS_INT else torch.float32, device=dev) for k in PAIR_STATS}
+    if set(outs) - set(PAIR_STATS):
+        raise L.UvcHipError(f"logits_pair_stats: outs names {sorted(set(outs) - set(PAIR_STATS))} are not among {PAIR_STATS}")
+    outs = {k: outs.get(k) for k in PAIR_STATS}
+    _chk(*outs.values())
+    for k, o in outs.items():
+        if o is not None and (o.dtype != (torch.int32 if k in PAIR_STATS_INT else torch.float32) or o.numel() < n):
+            raise L.UvcHipError("logits_pair_stats: outs must be int32 (top1_*, rank_*) / float32 tensors of at least n elements (or None)")
+    a = L.uvc_pair_stats_args()
+    a.za, a.zb, a.labels = L.ptr(za), L.ptr(zb), L.ptr(labels)
+    for k, o in outs.items():
+        setattr(a, k, L.ptr(o))
+    a.n, a.lda, a.ldb, a.C, a.labels_i64 = n, lda, ldb, Cc, i64
+    L.check(L.lib().uvc_logits_pair_stats(C.byref(a), L.cur_stream()), "uvc_logits_pair_stats")
+    return outs
+
+
+def _cka_width(D, what):
+    if D % 8 or not 8 <= D <= OOD_MAX_D:
+        raise L.UvcHipError(f"linear_cka: {what} must have a multiple of 8 columns in [8, {OOD_MAX_D}], not {D}")
+
+
+def linear_cka_matrices(X, Y, chunk_rows=None):
+    """(Xc^T Yc [D1, D2], Xc^T Xc [D1, D1], Yc^T Yc [D2, D2]) float32 of the column-centred float32 banks ``X`` [n, D1], ``Y`` [n, D2]: the
+    column means through ``class_moments`` with one class (float64 sums, one rounding), ``center_rows``, and per chunk of ``chunk_rows``
+    rows (default ``OOD_CHUNK_ROWS``) three float32 ``gemm_tn`` calls, beta = 1 after the first chunk.  The same ``chunk_rows`` gives the
+    same bits."""
+    L.require_cuda(X, Y)
+    n, D1, _ = _rows_f32(X, "linear_cka: X")
+    n2, D2, _ = _rows_f32(Y, "linear_cka: Y")
+    if n2 != n:
+        raise L.UvcHipError(f"linear_cka: X has {n} rows and Y {n2}")
+    _cka_width(D1, "X")
+    _cka_width(D2, "Y")
+    dev = X.device
+    zeros = torch.zeros(n, dtype=torch.int32, device=dev)
+    mx, my = class_moments(X, zeros, 1)[1], class_moments(Y, zeros, 1)[1]
+    chunk = max(1, min(n, OOD_CHUNK_ROWS if chunk_rows is None else int(chunk_rows)))
+    bx, by = torch.empty(chunk, D1, dtype=torch.float32, device=dev), torch.empty(chunk, D2, dtype=torch.float32, device=dev)
+    kxy, kxx, kyy = (torch.empty(a_, b_, dtype=torch.float32, device=dev) for a_, b_ in ((D1, D2), (D1, D1), (D2, D2)))
+    ws = torch.empty(max(gemm_tn_workspace_bytes(chunk, D1, D2), gemm_tn_workspace_bytes(chunk, D1, D1), gemm_tn_workspace_bytes(chunk, D2, D2), 16),
+                     dtype=torch.uint8, device=dev)
+    for r0 in range(0, n, chunk):
+        rows = min(chunk, n - r0)
+        center_rows(X[r0:r0 + rows], zeros[r0:r0 + rows], mx, out=bx[:rows])
+        center_rows(Y[r0:r0 + rows], zeros[r0:r0 + rows], my, out=by[:rows])
+        beta = 0.0 if r0 == 0 else 1.0
+        gemm_tn(bx, by, kxy, ws, dtype=UVC_F32, beta=beta, M=rows, N1=D1, N2=D2)
+        gemm_tn(bx, bx, kxx, ws, dtype=UVC_F32, beta=beta, M=rows, N1=D1, N2=D1)
+        gemm_tn(by, by, kyy, ws, dtype=UVC_F32, beta=beta, M=rows, N1=D2, N2=D2)
+    return kxy, kxx, kyy
+
+
+def cka_from_matrices(kxy, kxx, kyy):
+    """``|Xc^T Yc|_F^2 / (|Xc^T Xc|_F |Yc^T Yc|_F)`` in float64 on the host; None when the denominator is zero (constant features)."""
+    num = float(kxy.double().square().sum())
+    den = float(kxx.double().square().sum().sqrt()) * float(kyy.double().square().sum().sqrt())
+    return num / den if den > 0.0 else None
+
+
+def linear_cka(X, Y, chunk_rows=None):
+    """Linear CKA (Kornblith et al. 2019) of two float32 banks with one row per image: ``cka_from_matrices(*linear_cka_matrices(X, Y))``,
+    a float, or None on constant features."""
+    return cka_from_matrices(*linear_cka_matrices(X, Y, chunk_rows))
+
+
 def patch_rank(scores, offset=0, descending=True, np=None):
     """int32 [B, np]: the removal order of every image's patches from float32 ``scores`` [B, ld], the patches being columns
     [offset, offset + np) (default np: the rest of the row) -- rank[b, p] patches come before p; larger score first with ``descending``,
