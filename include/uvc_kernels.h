@@ -573,6 +573,53 @@ int uvc_calib_workspace_bytes(int64_t n, int32_t ld, int32_t C, int32_t bins, in
 int uvc_calib_eval(const uvc_calib_args* args, void* stream);
 int uvc_calib_stats(const uvc_calib_args* args, void* stream);
 
+/* Split conformal prediction on a logits bank (python -m uvc_amd.compact_conformal; Sadinle et al. 2019, Romano et al. 2020, Angelopoulos et
+ * al. 2021).  logits float32 [n, ld] of which columns [0, C) are valid (the rest is never read into a result); p = softmax(z * inv_temperature)
+ * over the valid columns.  The classes of a row are ordered by descending z, ties by ascending index, -0 = +0 -- the order is taken on the
+ * float32 inputs through order-preserving integer keys, so a rank is an exact integer; r_c in 1 .. C is the rank of class c and M_c the sum
+ * of p_j over the classes ranked ahead of c.  u float32 [n], one value per row, or NULL (= 1 for every row).  The score of class c:
+ *   UVC_CONFORMAL_LAC   s(c) = 1 - p_c
+ *   UVC_CONFORMAL_APS   s(c) = M_c + u p_c
+ *   UVC_CONFORMAL_RAPS  s(c) = M_c + u p_c + lam max(0, r_c - k_reg)
+ * -inf logits are allowed (p = 0, ordered by index at the end).  A NaN in a valid column neither hangs nor reads or writes out of bounds;
+ * that row's results are otherwise unspecified.
+ *
+ * uvc_conformal_scores: scores float32 [n] = s(y_i) of the rows whose label (int32, or int64 with labels_i64) lies in [0, C) and NaN for the
+ * others; counts int64 [1] = m, the rows that count.  One pass, O(C) per row: only the label's rank and the mass ahead of it are taken.  Up
+ * to 2048 classes a group of 1 .. 64 lanes holds a row in registers, the next row fetched before the current one is worked on -- 16-byte
+ * loads when ld % 4 == 0 and logits is 16-byte aligned, element by element otherwise, the same bits either way --; beyond, up to 65536, one
+ * workgroup takes a row (read twice, once from cache).  m is counted by a launch of its own over the labels.
+ *
+ * uvc_conformal_sets: the sets {c : s(c) <= qhat}: size int32 [n]; covered uint8 [n] = the label is in the set (0 for a row whose label lies
+ * outside [0, C)), NULL together with labels when there are none; members uint32 [n, ceil(C / 32)] or NULL: bit c % 32 of word c / 32, the
+ * padding bits zero.  qhat = +inf gives size = C.  A row's (key, index) pairs are sorted by a bitonic network in LDS, the exponentials
+ * summed along the sorted order; ceil-pow2(C) / 2 threads (at most 256) take a row, so a workgroup holds 32 rows of 10 classes and 4 of
+ * 100.  C <= 2048 (UVC_ERR_UNSUPPORTED beyond).  Nothing of size [n, C] is written by either call but members.
+ *
+ * Arithmetic: e_c = expf of the float32 rounding of (z_c - z_max) * inv_temperature, formed in float64; the sums of e (all of them, and
+ * those ahead of a class) are float64 sums of these float32 terms in a fixed order, and s is formed in float64 and rounded to float32 once.
+ * What remains is the error of the terms: with |d_c| <= ln(1 / p_c) and sum_c p_c ln(1 / p_c) <= ln C, the mass ahead, p_c and with them s
+ * are within 2 * 2^-23 * (1 + ln C) + 2^-24 max(1, s) of the exact value -- 2.2e-6 at C = 2048.
+ *
+ * Both: no atomics, one writer per element, the same bits on a repeat, a row's result does not depend on the rows beside it, 64-bit row
+ * offsets, workgroup counts functions of the shape alone (conformal.hip).  1 <= n < 2^31, 1 <= C <= ld < 2^31, method one of the three,
+ * inv_temperature > 0 and finite, lam >= 0 and finite, k_reg >= 0, qhat not NaN, no NULL among logits and the call's outputs, scores / u /
+ * members / size / int32 labels 4-byte and counts / int64 labels 8-byte aligned (UVC_ERR_ARG); scores: C <= 65536, sets: C <= 2048
+ * (UVC_ERR_UNSUPPORTED).  Every refusal happens before anything is launched, outputs untouched. */
+#define UVC_CONFORMAL_LAC 0
+#define UVC_CONFORMAL_APS 1
+#define UVC_CONFORMAL_RAPS 2
+typedef struct uvc_conformal_args {
+  const float* logits; const void* labels; const float* u;
+  float* scores; int64_t* counts;                       /* uvc_conformal_scores */
+  int32_t* size; uint8_t* covered; uint32_t* members;   /* uvc_conformal_sets */
+  int64_t n, ld;
+  int32_t C, labels_i64, method, k_reg;
+  float inv_temperature, lam, qhat, reserved;
+} uvc_conformal_args;
+int uvc_conformal_scores(const uvc_conformal_args* args, void* stream);
+int uvc_conformal_sets(const uvc_conformal_args* args, void* stream);
+
 /* Out-of-distribution detectors on a bank (python -m uvc_amd.compact_ood; Hendrycks & Gimpel 2017, Liu et al. 2020, Lee et al. 2018, Ren et al.
  * 2021, Sun et al. 2022).  Each call returns UVC_OK or refuses before anything is launched (outputs untouched); no atomics, one writer per
  * output element in every launch, the same bits on a repeat, a row's result does not depend on the rows beside it, every row offset is

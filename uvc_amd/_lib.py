@@ -138,6 +138,12 @@ class uvc_calib_args(C.Structure):
                [(n, C.c_int64) for n in ("workspace_bytes", "n", "ld")] + [(n, C.c_int32) for n in ("C", "scale_len", "labels_i64", "bins")]
 
 
+class uvc_conformal_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("logits", "labels", "u", "scores", "counts", "size", "covered", "members")] + \
+               [(n, C.c_int64) for n in ("n", "ld")] + [(n, C.c_int32) for n in ("C", "labels_i64", "method", "k_reg")] + \
+               [(n, C.c_float) for n in ("inv_temperature", "lam", "qhat", "reserved")]
+
+
 class uvc_pair_stats_args(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("za", "zb", "labels", "top1_a", "top1_b", "conf_a", "conf_b", "kl_ab", "kl_ba", "js", "tv", "nll_a", "nll_b",
                                           "rank_a", "rank_b", "rank_b_top1a", "rank_a_top1b")] + \
@@ -268,6 +274,8 @@ _SIGNATURES = {
     "uvc_calib_workspace_bytes": [I64, I32, I32, I32, C.POINTER(I64)],
     "uvc_calib_eval": [C.POINTER(uvc_calib_args), VP],
     "uvc_calib_stats": [C.POINTER(uvc_calib_args), VP],
+    "uvc_conformal_scores": [C.POINTER(uvc_conformal_args), VP],
+    "uvc_conformal_sets": [C.POINTER(uvc_conformal_args), VP],
     "uvc_ood_logit_scores": [VP, I64, I64, I32, F32, VP, VP, VP, VP, VP],
     "uvc_class_moments_workspace_bytes": [I64, I32, C.POINTER(I64)],
     "uvc_class_moments": [VP, I64, VP, I32, VP, I64, I32, I32, VP, VP, VP, I64, VP],

@@ -873,7 +873,75 @@ def calib_stats(logits, labels, scale, shift=None, num_classes=None, bins=15, *,
     return bin_count, bin_conf, bin_hit, sums, counts
 
 
-OOD_MAX_D = 1016                                    # D + 8 augmentation columns is knn_topk's widest row
+CONFORMAL_METHODS = ("lac", "aps", "raps")          # UVC_CONFORMAL_*
+CONFORMAL_SETS_MAX_C = 2048                         # uvc_conformal_sets keeps a row's pairs in LDS
+
+
+def _conformal_args(what, logits, labels, u, num_classes, method, temperature, lam, k_reg):
+    L.require_cuda(logits, labels, u)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise L.UvcHipError(f"{what}: logits must be float32 [n, ld] with unit element stride")
+    n = logits.shape[0]
+    if labels is not None and (labels.dim() != 1 or labels.dtype not in (torch.int32, torch.int64) or labels.shape[0] != n or not labels.is_contiguous()):
+        raise L.UvcHipError(f"{what}: labels must be contiguous int32 or int64 [n]")
+    if u is not None and (u.dtype != torch.float32 or tuple(u.shape) != (n,) or not u.is_contiguous()):
+        raise L.UvcHipError(f"{what}: u must be contiguous float32 [n] or None")
+    Cc = logits.shape[1] if num_classes is None else int(num_classes)
+    if Cc > logits.shape[1]:
+        raise L.UvcHipError(f"{what}: num_classes {Cc} is more than the logits' {logits.shape[1]} columns")
+    a = L.uvc_conformal_args()
+    a.logits, a.labels, a.u = L.ptr(logits), L.ptr(labels), L.ptr(u)
+    a.n, a.ld, a.C, a.labels_i64 = n, (logits.stride(0) if n > 1 else logits.shape[1]), Cc, int(labels is not None and labels.dtype == torch.int64)
+    a.method = CONFORMAL_METHODS.index(method) if method in CONFORMAL_METHODS else -1      # (the call itself refuses the rest, by name)
+    t = float(temperature)
+    a.inv_temperature, a.lam, a.k_reg = (1.0 / t if t > 0 else -1.0), float(lam), int(k_reg)
+    return a, n, Cc
+
+
+def conformal_scores(logits, labels, num_classes=None, method="aps", u=None, *, temperature=1.0, lam=0.0, k_reg=0, scores=None, counts=None):
+    """(scores float32 [n], counts int64 [1] = m), on the device: the conformal score of every row's label under ``softmax(z / temperature)``
+    -- ``"lac"``: 1 - p_y; ``"aps"``: the mass ranked ahead of the label + u p_y; ``"raps"``: that + lam max(0, rank - k_reg) --, NaN for a row
+    whose label lies outside [0, num_classes); ``u`` float32 [n] or None (= 1).  One pass over the float32 ``logits`` [n, ld] whose columns
+    [0, num_classes) are valid (default: all); nothing of their size is written (uvc_conformal_scores).  Nothing is synchronised."""
+    a, n, Cc = _conformal_args("conformal_scores", logits, labels, u, num_classes, method, temperature, lam, k_reg)
+    if labels is None:
+        raise L.UvcHipError("conformal_scores: labels must be contiguous int32 or int64 [n]")
+    dev = logits.device
+    scores = torch.empty(n, dtype=torch.float32, device=dev) if scores is None else scores
+    counts = torch.empty(1, dtype=torch.int64, device=dev) if counts is None else counts
+    _chk(scores, counts)
+    if scores.dtype != torch.float32 or scores.numel() != n or counts.dtype != torch.int64 or counts.numel() < 1:
+        raise L.UvcHipError("conformal_scores: scores float32 [n], counts int64 [1]")
+    a.scores, a.counts = L.ptr(scores), L.ptr(counts)
+    L.check(L.lib().uvc_conformal_scores(C.byref(a), L.cur_stream()), "uvc_conformal_scores")
+    return scores, counts
+
+
+def conformal_sets(logits, qhat, labels=None, num_classes=None, method="aps", u=None, *, temperature=1.0, lam=0.0, k_reg=0, members=False,
+                   size=None, covered=None):
+    """(size int32 [n], covered uint8 [n] or None without ``labels``, members uint32 [n, ceil(C / 32)] or None), on the device: the prediction
+    sets ``{c : s(c) <= qhat}`` of ``conformal_scores``' score; ``covered``: the label is in the set; ``members`` (True, or a tensor to
+    fill): bit c % 32 of word c / 32 (uvc_conformal_sets).  At most 2048 classes.  Operands as ``conformal_scores`` takes them."""
+    a, n, Cc = _conformal_args("conformal_sets", logits, labels, u, num_classes, method, temperature, lam, k_reg)
+    dev = logits.device
+    W = (max(Cc, 1) + 31) // 32
+    size = torch.empty(n, dtype=torch.int32, device=dev) if size is None else size
+    if covered is None and labels is not None:
+        covered = torch.empty(n, dtype=torch.uint8, device=dev)
+    if members is True:
+        members = torch.empty(n, W, dtype=torch.int32, device=dev)      # (torch has no arithmetic on uint32: the words' bits, as int32)
+    elif members is False:
+        members = None
+    _chk(size, covered, members)
+    if size.dtype != torch.int32 or size.numel() != n or (covered is not None and (covered.dtype != torch.uint8 or covered.numel() != n)) or \
+            (members is not None and (members.dtype not in (torch.int32, torch.uint32) or tuple(members.shape) != (n, W))):
+        raise L.UvcHipError("conformal_sets: size int32 [n], covered uint8 [n], members int32 or uint32 [n, ceil(C / 32)]")
+    a.size, a.covered, a.members, a.qhat = L.ptr(size), L.ptr(covered), L.ptr(members), float(qhat)
+    L.check(L.lib().uvc_conformal_sets(C.byref(a), L.cur_stream()), "uvc_conformal_sets")
+    return size, covered, members
+
+
+OOD_MAX_D = 1016                                   # D + 8 augmentation columns is knn_topk's widest row
 OOD_CHUNK_ROWS = 65536                              # tools/ood_time.py: within 5 % of the best of 16 384 / 65 536 / 262 144 at both ImageNet shapes
 
 
