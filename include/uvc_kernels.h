@@ -691,6 +691,61 @@ typedef struct uvc_pair_stats_args {
 int uvc_logits_pair_stats(const uvc_pair_stats_args* args, void* stream);
 int uvc_logits_pair_stats_reg_max(void);
 
+/* Common corruptions of a normalised image batch (python -m uvc_amd.compact_corrupt; corrupt.hip), in the style of Hendrycks & Dietterich
+ * (ICLR 2019).  x, out: float32 [B, C, H, W], C <= 4, x = (pixel - mean_c) / std_c; every statement is on pixels p = x std_c + mean_c,
+ * computed on the normalised values and ends with clamp(., lo_c, hi_c), the normalised 0 and 1 the caller passes.  No atomics, one writer
+ * per output element, 64-bit offsets, the same bits on a repeat and for any split of the batch.  Each call returns UVC_OK or refuses before
+ * anything is launched (outputs untouched): null pointers, B C H W == 0, C > 4, a NaN or negative level, std_c <= 0, lo_c > hi_c:
+ * UVC_ERR_ARG; C H W >= 2^31 or more than 2^31 - 1 workgroups: UVC_ERR_UNSUPPORTED.
+ *
+ * uvc_corrupt_noise (kind 0 .. 2), a = level.  Element e of the batch has the global index g = index0 C H W + e (index0: the dataset index of
+ * the batch's first image), so an image's noise does not depend on the batching.  The pair j = g >> 1 draws u1 (site 0) and u2 (site 1)
+ * of uvc_exp_noise's keyed generator, key(seed, stream_id, site) at counter j; r = sqrt(-2 ln u1), t = float32(2 pi_f32 u2), z = r cos t for
+ * even g and r sin t for odd g (logf, sqrtf, sincosf, once per pair).
+ *   UVC_CORRUPT_GAUSSIAN_NOISE   p + a z             out = x + z (a / std_c)
+ *   UVC_CORRUPT_SPECKLE_NOISE    p + a p z           out = x + z (a x + a mean_c / std_c)
+ *   UVC_CORRUPT_IMPULSE_NOISE    u = the uniform of site 2 at counter g: u < a / 2 -> lo_c, a / 2 <= u < a -> hi_c, else x (a <= 1, UVC_ERR_ARG
+ *                                beyond); the comparisons are exact (thresholds rounded up to float32 on the host).
+ * Every element is read once, by 16-byte accesses when x + (e of a multiple of 4 in g) and out are 16-byte aligned, else element by element.
+ *
+ * uvc_corrupt_colour (kind 3, 4):
+ *   UVC_CORRUPT_BRIGHTNESS   p clipped to [0, 1]; V = max_c p_c, V' = min(V + a, 1); p' = p V' / V when V > 0, else V' (the HSV value shift)
+ *   UVC_CORRUPT_CONTRAST     m = the mean of p over the image's channels and pixels; (p - m) a + m, out = a x + (1 - a) (m - mean_c) / std_c.
+ *                            m goes to image_mean float32 [B] (device, required) in a launch of its own: one workgroup per image, float64
+ *                            per-thread sums in a fixed order and a fixed tree, whatever the grid of the pointwise launch.
+ *
+ * uvc_blur_separable: every plane (planes = B C, channel = plane % C) filtered along x, then along y, by the 2 R + 1 taps (host pointer,
+ * 0 <= R <= 32, UVC_ERR_ARG beyond), borders clamp the index; each output is one fma chain over ascending taps from 0; the first pass
+ * goes to scratch (float32, x's size, not x or out).  lo / hi (host [C], both or neither): the clamp of the second pass.
+ * uvc_stencil2d: the dense K x K filter (taps: DEVICE float32 [K, K], K odd in 3 .. 25, UVC_ERR_ARG beyond), borders clamp the index, one fma
+ * chain per output over the taps in row-major order, zero taps skipped.
+ * uvc_pixelate: every pixel becomes the mean of its k x k cell (k >= 1; cells start at 0, a ragged last cell averages what exists): up
+ * to k = 16 one float32 row-major sum per cell divided by the count, beyond a float64 sum in a fixed order; k = 1 returns x's bits.
+ * uvc_box_muller: z0 = r cos t, z1 = r sin t of float32 u1 in (0, 1), u2 in [0, 1), n >= 1: the device function the noise kernels call. */
+#define UVC_CORRUPT_GAUSSIAN_NOISE 0
+#define UVC_CORRUPT_SPECKLE_NOISE 1
+#define UVC_CORRUPT_IMPULSE_NOISE 2
+#define UVC_CORRUPT_BRIGHTNESS 3
+#define UVC_CORRUPT_CONTRAST 4
+typedef struct uvc_corrupt_args {
+  const float* x; float* out;
+  float* image_mean;                                    /* contrast */
+  int64_t index0; uint64_t seed, stream_id;             /* noise */
+  double level;
+  int32_t B, C, H, W, kind, reserved;
+  double mean[4], std[4];                               /* the preset's statistics, as the spec takes them */
+  float lo[4], hi[4];
+} uvc_corrupt_args;
+int uvc_corrupt_noise(const uvc_corrupt_args* args, void* stream);
+int uvc_corrupt_colour(const uvc_corrupt_args* args, void* stream);
+int uvc_blur_separable(const float* x, float* scratch, float* out, const float* taps, int32_t R, int64_t planes, int32_t C, int32_t H,
+                       int32_t W, const float* lo, const float* hi, void* stream);
+int uvc_stencil2d(const float* x, float* out, const float* taps, int32_t K, int64_t planes, int32_t C, int32_t H, int32_t W, const float* lo,
+                  const float* hi, void* stream);
+int uvc_pixelate(const float* x, float* out, int32_t k, int64_t planes, int32_t C, int32_t H, int32_t W, const float* lo, const float* hi,
+                 void* stream);
+int uvc_box_muller(const float* u1, const float* u2, float* z0, float* z1, int64_t n, void* stream);
+
 /* clip_grad_norm_(max_norm) + AdamW over flat float32 buffers (joint_train.py:428-429;
  * torch.optim.AdamW(lr, betas, eps, weight_decay) semantics, decoupled decay).
  * uvc_grad_sqnorm accumulates sum(g^2) of a segment into sq[0] (accumulate = 0 for the first segment) and leaves sqrt(sq[0]) -- the

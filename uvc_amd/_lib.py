@@ -144,6 +144,12 @@ class uvc_conformal_args(C.Structure):
                [(n, C.c_float) for n in ("inv_temperature", "lam", "qhat", "reserved")]
 
 
+class uvc_corrupt_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("x", "out", "image_mean")] + [("index0", C.c_int64), ("seed", C.c_uint64), ("stream_id", C.c_uint64),
+                                                                         ("level", C.c_double)] + \
+               [(n, C.c_int32) for n in ("B", "C", "H", "W", "kind", "reserved")] + [(n, C.c_double * 4) for n in ("mean", "std")] + [(n, C.c_float * 4) for n in ("lo", "hi")]
+
+
 class uvc_pair_stats_args(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("za", "zb", "labels", "top1_a", "top1_b", "conf_a", "conf_b", "kl_ab", "kl_ba", "js", "tv", "nll_a", "nll_b",
                                           "rank_a", "rank_b", "rank_b_top1a", "rank_a_top1b")] + \
@@ -276,6 +282,12 @@ _SIGNATURES = {
     "uvc_calib_stats": [C.POINTER(uvc_calib_args), VP],
     "uvc_conformal_scores": [C.POINTER(uvc_conformal_args), VP],
     "uvc_conformal_sets": [C.POINTER(uvc_conformal_args), VP],
+    "uvc_corrupt_noise": [C.POINTER(uvc_corrupt_args), VP],
+    "uvc_corrupt_colour": [C.POINTER(uvc_corrupt_args), VP],
+    "uvc_blur_separable": [VP, VP, VP, C.POINTER(F32), I32, I64, I32, I32, I32, C.POINTER(F32), C.POINTER(F32), VP],
+    "uvc_stencil2d": [VP, VP, VP, I32, I64, I32, I32, I32, C.POINTER(F32), C.POINTER(F32), VP],
+    "uvc_pixelate": [VP, VP, I32, I64, I32, I32, I32, C.POINTER(F32), C.POINTER(F32), VP],
+    "uvc_box_muller": [VP, VP, VP, VP, I64, VP],
     "uvc_ood_logit_scores": [VP, I64, I64, I32, F32, VP, VP, VP, VP, VP],
     "uvc_class_moments_workspace_bytes": [I64, I32, C.POINTER(I64)],
     "uvc_class_moments": [VP, I64, VP, I32, VP, I64, I32, I32, VP, VP, VP, I64, VP],

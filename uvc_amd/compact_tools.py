@@ -1,5 +1,5 @@
 """What the stand-alone compact tools share (``compact_transfer``, ``compact_probe``, ``compact_calibrate``, ``compact_ood``,
-``compact_compare``, ``compact_robust``): the dataset flags, written once, the eval loader of a compact file, the walk over one split that ends in a bank file,
+``compact_compare``, ``compact_robust``, ``compact_corrupt``): the dataset flags, written once, the eval loader of a compact file, the walk over one split that ends in a bank file,
 the bank dict, the held-out split of a bank and the L-BFGS driver.  A flag of the dataset block is added here and nowhere else; what the
 image-file tools share (``compact predict`` / ``explain`` / ``attribute``, ``compact_pixel``, ``compact_perturb``) is in ``compact``.
 """

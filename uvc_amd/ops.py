@@ -941,7 +941,160 @@ def conformal_sets(logits, qhat, labels=None, num_classes=None, method="aps", u=
     return size, covered, members
 
 
-OOD_MAX_D = 1016                                   # D + 8 augmentation columns is knn_topk's widest row
+CORRUPT_KINDS = ("gaussian_noise", "speckle_noise", "impulse_noise", "brightness", "contrast")      # UVC_CORRUPT_*
+BLUR_MAX_R, STENCIL_MAX_K = 32, 25
+
+
+def _image_batch(what, x, out):
+    _chk(x, out)
+    if x.dim() != 4 or x.dtype != torch.float32 or x.numel() == 0 or x.shape[1] > 4:
+        raise L.UvcHipError(f"{what}: x must be a non-empty float32 [B, C, H, W] with at most 4 channels")
+    if out is None:
+        out = torch.empty_like(x)
+    if out.dtype != torch.float32 or out.shape != x.shape or out.device != x.device:
+        raise L.UvcHipError(f"{what}: out must be float32 of x's shape on x's device")
+    return out
+
+
+def _floats(what, v, n, name):
+    v = [float(u) for u in (v.tolist() if hasattr(v, "tolist") else v)]
+    if len(v) != n:
+        raise L.UvcHipError(f"{what}: {name} must hold {n} values")
+    return v
+
+
+def _clamp_pair(what, lo, hi, Cc):
+    if (lo is None) != (hi is None):
+        raise L.UvcHipError(f"{what}: lo and hi go together")
+    if lo is None:
+        return None, None
+    lo, hi = _floats(what, lo, Cc, "lo"), _floats(what, hi, Cc, "hi")
+    if not all(a <= b for a, b in zip(lo, hi)):
+        raise L.UvcHipError(f"{what}: lo <= hi in every channel")
+    return (C.c_float * Cc)(*lo), (C.c_float * Cc)(*hi)
+
+
+def _corrupt_args(what, x, out, kind, kinds, level, mean, std, lo, hi):
+    import math
+    out = _image_batch(what, x, out)
+    if kind not in kinds:
+        raise L.UvcHipError(f"{what}: kind must be one of {kinds}, not {kind!r}")
+    level = float(level)
+    if not (level >= 0 and math.isfinite(level)):
+        raise L.UvcHipError(f"{what}: the level {level} must be non-negative and finite")
+    if kind == "impulse_noise" and level > 1:
+        raise L.UvcHipError(f"{what}: impulse_noise's level {level} is a share, at most 1")
+    B, Cc, H, W = x.shape
+    if Cc * H * W >= 1 << 31:
+        raise L.UvcHipError(f"{what}: an image of 2^31 elements or more")
+    a = L.uvc_corrupt_args()
+    a.x, a.out = L.ptr(x), L.ptr(out)
+    a.level, a.kind = level, CORRUPT_KINDS.index(kind)
+    a.B, a.C, a.H, a.W = B, Cc, H, W
+    for name, v in (("mean", mean), ("std", std), ("lo", lo), ("hi", hi)):
+        v = _floats(what, v, Cc, name)
+        if not all(math.isfinite(u) for u in v):
+            raise L.UvcHipError(f"{what}: {name} must be finite")
+        getattr(a, name)[:Cc] = v
+    if not all(C.c_float(s).value > 0 and math.isfinite(C.c_float(s).value) for s in a.std[:Cc]):
+        raise L.UvcHipError(f"{what}: std must be positive and finite (in float32)")
+    if not all(l <= h for l, h in zip(a.lo[:Cc], a.hi[:Cc])):
+        raise L.UvcHipError(f"{what}: lo <= hi in every channel")
+    return a, out
+
+
+def corrupt_noise(x, kind, level, *, mean, std, lo, hi, seed=0, stream=0, index0=0, out=None):
+    """``out`` float32 [B, C, H, W]: ``gaussian_noise`` ``p + a z``, ``speckle_noise`` ``p + a p z`` or ``impulse_noise`` (a share ``a / 2`` of
+    the elements to 0, another to 1) on the pixels ``p = x std_c + mean_c`` of the normalised batch ``x``, clamped to ``[lo_c, hi_c]``.  z and u
+    are keyed draws of (``seed``, ``stream``) at the global element index ``index0 C H W + e`` (uvc_corrupt_noise); ``out`` may be ``x``."""
+    a, out = _corrupt_args("corrupt_noise", x, out, kind, CORRUPT_KINDS[:3], level, mean, std, lo, hi)
+    index0 = int(index0)
+    if index0 < 0 or (index0 + x.shape[0]) * (x.numel() // x.shape[0]) >= 1 << 64:
+        raise L.UvcHipError("corrupt_noise: index0 must be non-negative, the last global index below 2^64")
+    a.index0, a.seed, a.stream_id = index0, int(seed) & (2 ** 64 - 1), int(stream) & (2 ** 64 - 1)
+    L.check(L.lib().uvc_corrupt_noise(C.byref(a), L.cur_stream()), "uvc_corrupt_noise")
+    return out
+
+
+def corrupt_colour(x, kind, level, *, mean, std, lo, hi, image_mean=None, out=None):
+    """``out`` float32 [B, C, H, W]: ``brightness`` (the HSV value of the clipped pixel raised by ``level``, at most 1) or ``contrast``
+    (``(p - m) a + m`` around the image's mean ``m``), clamped to ``[lo_c, hi_c]`` (uvc_corrupt_colour).  ``image_mean`` (contrast): float32
+    [B] that receives ``m``; default a new tensor.  Returns ``out``, or ``(out, image_mean)`` for contrast."""
+    a, out = _corrupt_args("corrupt_colour", x, out, kind, CORRUPT_KINDS[3:], level, mean, std, lo, hi)
+    if kind == "contrast":
+        if image_mean is None:
+            image_mean = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        _chk(image_mean)
+        if image_mean.dtype != torch.float32 or image_mean.shape != (x.shape[0],) or image_mean.device != x.device:
+            raise L.UvcHipError("corrupt_colour: image_mean must be float32 [B] on x's device")
+        a.image_mean = L.ptr(image_mean)
+    L.check(L.lib().uvc_corrupt_colour(C.byref(a), L.cur_stream()), "uvc_corrupt_colour")
+    return (out, image_mean) if kind == "contrast" else out
+
+
+def _plane_args(what, x, out, lo, hi):
+    out = _image_batch(what, x, out)
+    if out.data_ptr() == x.data_ptr():
+        raise L.UvcHipError(f"{what}: out must not be x")
+    B, Cc, H, W = x.shape
+    if H * W >= 1 << 31:
+        raise L.UvcHipError(f"{what}: a plane of 2^31 elements or more")
+    lo, hi = _clamp_pair(what, lo, hi, Cc)
+    return out, (B * Cc, Cc, H, W, lo, hi, L.cur_stream())
+
+
+def blur_separable(x, taps, *, lo=None, hi=None, scratch=None, out=None):
+    """``out`` float32 [B, C, H, W]: every plane filtered along x and then along y by the ``2 R + 1`` ``taps`` (host floats, R <= 32), borders
+    clamp the index, each output one fma chain over ascending taps; ``scratch``: the float32 plane between the passes (default: new);
+    ``lo`` / ``hi``: the per-channel clamp of the result (uvc_blur_separable)."""
+    import math
+    taps = [float(t) for t in (taps.tolist() if hasattr(taps, "tolist") else taps)]
+    if len(taps) % 2 == 0 or len(taps) > 2 * BLUR_MAX_R + 1 or not all(math.isfinite(t) for t in taps):
+        raise L.UvcHipError(f"blur_separable: an odd number of finite taps, at most {2 * BLUR_MAX_R + 1}")
+    out, tail = _plane_args("blur_separable", x, out, lo, hi)
+    if scratch is None:
+        scratch = torch.empty_like(x)
+    _chk(scratch)
+    if scratch.dtype != torch.float32 or scratch.shape != x.shape or scratch.device != x.device or scratch.data_ptr() in (x.data_ptr(), out.data_ptr()):
+        raise L.UvcHipError("blur_separable: scratch must be a float32 tensor of x's shape of its own")
+    L.check(L.lib().uvc_blur_separable(L.ptr(x), L.ptr(scratch), L.ptr(out), (C.c_float * len(taps))(*taps), len(taps) // 2, *tail), "uvc_blur_separable")
+    return out
+
+
+def stencil2d(x, taps, *, lo=None, hi=None, out=None):
+    """``out`` float32 [B, C, H, W]: every plane under the dense ``K x K`` filter ``taps`` (float32 [K, K] on the device, K odd in 3 .. 25), borders
+    clamp the index, each output one fma chain over the taps in row-major order, zero taps skipped (uvc_stencil2d)."""
+    _chk(taps)
+    if taps.dim() != 2 or taps.dtype != torch.float32 or taps.shape[0] != taps.shape[1] or taps.shape[0] % 2 == 0 or not 3 <= taps.shape[0] <= STENCIL_MAX_K \
+            or taps.device != x.device:
+        raise L.UvcHipError(f"stencil2d: taps must be float32 [K, K] on x's device, K odd in [3, {STENCIL_MAX_K}]")
+    out, tail = _plane_args("stencil2d", x, out, lo, hi)
+    L.check(L.lib().uvc_stencil2d(L.ptr(x), L.ptr(out), L.ptr(taps), taps.shape[0], *tail), "uvc_stencil2d")
+    return out
+
+
+def pixelate(x, k, *, lo=None, hi=None, out=None):
+    """``out`` float32 [B, C, H, W]: every pixel becomes the mean of its ``k x k`` cell; cells start at 0 and a ragged last cell averages what
+    exists; ``k = 1`` returns x's bits (uvc_pixelate)."""
+    if int(k) != k or int(k) < 1 or int(k) >= 1 << 31:
+        raise L.UvcHipError(f"pixelate: the cell width {k} must be an integer, at least 1")
+    out, tail = _plane_args("pixelate", x, out, lo, hi)
+    L.check(L.lib().uvc_pixelate(L.ptr(x), L.ptr(out), int(k), *tail), "uvc_pixelate")
+    return out
+
+
+def box_muller(u1, u2):
+    """``(z0, z1)`` float32: ``r cos t`` and ``r sin t`` with ``r = sqrt(-2 ln u1)``, ``t = 2 pi u2`` of float32 ``u1`` in (0, 1) and ``u2`` in
+    [0, 1) -- the device function of the noise corruptions on given uniforms (uvc_box_muller)."""
+    _chk(u1, u2)
+    if u1.dtype != torch.float32 or u2.dtype != torch.float32 or u1.dim() != 1 or u1.shape != u2.shape or u1.numel() == 0:
+        raise L.UvcHipError("box_muller: u1 and u2 must be non-empty float32 [n]")
+    z0, z1 = torch.empty_like(u1), torch.empty_like(u1)
+    L.check(L.lib().uvc_box_muller(L.ptr(u1), L.ptr(u2), L.ptr(z0), L.ptr(z1), u1.numel(), L.cur_stream()), "uvc_box_muller")
+    return z0, z1
+
+
+OOD_MAX_D = 1016                                  # D + 8 augmentation columns is knn_topk's widest row
 OOD_CHUNK_ROWS = 65536                              # tools/ood_time.py: within 5 % of the best of 16 384 / 65 536 / 262 144 at both ImageNet shapes
 
 
