@@ -746,6 +746,64 @@ int uvc_pixelate(const float* x, float* out, int32_t k, int64_t planes, int32_t 
                  void* stream);
 int uvc_box_muller(const float* u1, const float* u2, float* z0, float* z1, int64_t n, void* stream);
 
+/* Last-layer training-data influence on banks (python -m uvc_amd.compact_influence; influence.hip; Pruthi et al. 2020 "TracIn", Yeh et al.
+ * 2018 "representer points").  For the head z = W f + b under cross-entropy the gradient of example i with respect to (W, b) is the outer
+ * product r_i (x) [f_i; 1], r_i = softmax(z_i) - e_target, so the inner product of two examples' gradients is
+ *   I(i, t) = (f_i . f_t + bias) * (r_i . r_t),   bias = 1 (the head's bias column; 0 for a head without one),
+ * and the self-influence I(i, i) = (|f_i|^2 + bias) |r_i|^2.  Each call returns UVC_OK or refuses before anything is launched (outputs
+ * untouched); no atomics, one writer per output element in every launch, the same bits on a repeat, every offset is 64-bit.
+ *
+ * uvc_influence_residuals: logits float32 [n, ld] of which columns [0, C) are valid (the rest is never read); labels [n] (int32, or int64
+ * with labels_i64; may be NULL with target_mode 1).  The target of a row is its label (target_mode 0; a label outside [0, C) makes the row
+ * a SKIPPED row) or the FIRST maximum of its valid columns (target_mode 1; a row without one -- all NaN or -inf -- is skipped).  r float32
+ * [n, ldr], ldr >= C a multiple of 8 and r 16-byte aligned: softmax(z)_c - [c == target] on [0, C) and +0 on [C, ldr) -- rows that
+ * uvc_influence_topk takes as they are; target int32 [n], -1 for a skipped row; rsq float32 [n] = sum_c r_c^2 of the float32 values as
+ * stored.  A skipped row is +0 everywhere and rsq = 0.  Arithmetic (the convention of ood.hip / conformal.hip): m the maximum of the valid
+ * columns, d_c = z_c - m in float32 (one rounding), e_c = expf(d_c) in float32, S the float64 sum of the e_c -- lane l of the row's wave
+ * adds columns l, l + 64, ... in ascending order, then the xor butterfly over the lanes --, p_c = e_c / S and p_c - 1 in float64, rounded to
+ * float32 once; rsq is the float64 sum of the squares in the same order, rounded once.  -inf logits are allowed (p = 0).  A NaN in a valid
+ * column is never the maximum; it neither hangs nor reads or writes out of bounds, that row's r and rsq are NaN and the rows beside it
+ * are not affected.  One wave per row, the row read three times (twice from cache).  1 <= n < 2^31, 1 <= C <= ld < 2^31, target_mode 0
+ * or 1, no NULL among logits and the outputs (UVC_ERR_ARG); C <= 65536 (UVC_ERR_UNSUPPORTED).
+ *
+ * uvc_influence_topk: query features fq [nq, D] and bank features fb [n, D] (row strides ldfq, ldfb elements), both UVC_BF16 or both UVC_F32
+ * (a mix: UVC_ERR_UNSUPPORTED), D a multiple of 8 in [8, 1024], 16-byte aligned pointers and row strides -- uvc_knn_topk's rules; query
+ * residuals rq [nq, Cr] and bank residuals rb [n, Cr], float32 (row strides ldrq, ldrb), Cr a multiple of 8 in [8, 4096]
+ * (UVC_ERR_UNSUPPORTED), 16-byte aligned likewise; bias finite.  Per (query t, bank row i):  sf = the feature dot product in exactly
+ * uvc_knn_topk's arithmetic (the MFMA chain over ascending columns; float32: the fmaf chain from +0);  sr = the residual dot product as the
+ * fmaf chain of v_mfma_f32_16x16x4_f32 from +0, c ascending;  v = (sf + bias) * sr, one float32 add and one float32 multiply.  v does not
+ * depend on nq, n, the row's place in the bank or the split count.  pos_vals float32 / pos_idx int32 [nq, k]: the k largest v, descending,
+ * equal values by ascending bank row; neg_vals / neg_idx [nq, k]: the k smallest v, ascending, equal values by ascending bank row.  Either
+ * pair may be NULL (both of its pointers) and is then not computed; not both.  1 <= k <= 64.  Lists start as (-inf, -1) and (+inf, -1):
+ * a bank of fewer than k rows leaves those slots; a NaN never enters either list, nor does -inf the first or +inf the second (they equal
+ * the empty slot).  exclude int32 [nq] or NULL: one bank row per query that is skipped (-1, or any value outside [0, n): none) -- a query
+ * that is itself a bank row.  One workgroup per 64 queries, the bank visited in ascending 64-row tiles; splits, workspace and the merge
+ * are uvc_knn_topk's scheme: splits <= 0 lets the host choose from the shapes and the CU count, any value is clamped to
+ * [1, min(512, ceil(n / 64))], splits_used > 1 needs workspace >= uvc_influence_workspace_bytes() (4-byte aligned), and every split count
+ * gives the same bits.
+ *
+ * uvc_influence_self: f [n, D] of dtype (row stride ldf), D as above: fsq float32 [n] (or NULL) = sum_d f_d^2 in float32 -- lane l of the
+ * row's wave takes columns (64 u + l) 4 .. + 3, u ascending, as one fmaf chain from +0, then the xor butterfly (uvc_rows_sqnorm_aug's order;
+ * bf16 elements widened exactly) -- and out float32 [n] (or NULL; needs rsq float32 [n]) = (fsq + bias) * rsq, one float32 add and one
+ * multiply.  Nothing else is written.
+ *
+ * uvc_influence_expf: e[i] = expf(d[i]), the device function uvc_influence_residuals calls, so that its error can be measured. */
+typedef struct uvc_influence_args {
+  const void* fq; const void* fb; const float* rq; const float* rb; const int32_t* exclude;
+  float* pos_vals; int32_t* pos_idx; float* neg_vals; int32_t* neg_idx;
+  void* workspace; int64_t workspace_bytes;
+  int64_t ldfq, ldfb, ldrq, ldrb;
+  float bias;
+  int32_t nq, n, D, Cr, k, q_dtype, bank_dtype, splits, reserved;
+} uvc_influence_args;
+int uvc_influence_residuals(const float* logits, int64_t n, int64_t ld, int32_t C, const void* labels, int32_t labels_i64, int32_t target_mode,
+                            float* r, int64_t ldr, int32_t* target, float* rsq, void* stream);
+int uvc_influence_workspace_bytes(int32_t nq, int32_t n, int32_t k, int32_t splits, int64_t* bytes, int32_t* splits_used);
+int uvc_influence_topk(const uvc_influence_args* args, void* stream);
+int uvc_influence_self(const void* f, int64_t ldf, int32_t dtype, int64_t n, int32_t D, const float* rsq, float bias, float* fsq, float* out,
+                       void* stream);
+int uvc_influence_expf(const float* d, float* e, int64_t n, void* stream);
+
 /* clip_grad_norm_(max_norm) + AdamW over flat float32 buffers (joint_train.py:428-429;
  * torch.optim.AdamW(lr, betas, eps, weight_decay) semantics, decoupled decay).
  * uvc_grad_sqnorm accumulates sum(g^2) of a segment into sq[0] (accumulate = 0 for the first segment) and leaves sqrt(sq[0]) -- the

@@ -150,6 +150,12 @@ class uvc_corrupt_args(C.Structure):
                [(n, C.c_int32) for n in ("B", "C", "H", "W", "kind", "reserved")] + [(n, C.c_double * 4) for n in ("mean", "std")] + [(n, C.c_float * 4) for n in ("lo", "hi")]
 
 
+class uvc_influence_args(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("fq", "fb", "rq", "rb", "exclude", "pos_vals", "pos_idx", "neg_vals", "neg_idx", "workspace")] + \
+               [(n, C.c_int64) for n in ("workspace_bytes", "ldfq", "ldfb", "ldrq", "ldrb")] + [("bias", C.c_float)] + \
+               [(n, C.c_int32) for n in ("nq", "n", "D", "Cr", "k", "q_dtype", "bank_dtype", "splits", "reserved")]
+
+
 class uvc_pair_stats_args(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("za", "zb", "labels", "top1_a", "top1_b", "conf_a", "conf_b", "kl_ab", "kl_ba", "js", "tv", "nll_a", "nll_b",
                                           "rank_a", "rank_b", "rank_b_top1a", "rank_a_top1b")] + \
@@ -288,6 +294,11 @@ _SIGNATURES = {
     "uvc_stencil2d": [VP, VP, VP, I32, I64, I32, I32, I32, C.POINTER(F32), C.POINTER(F32), VP],
     "uvc_pixelate": [VP, VP, I32, I64, I32, I32, I32, C.POINTER(F32), C.POINTER(F32), VP],
     "uvc_box_muller": [VP, VP, VP, VP, I64, VP],
+    "uvc_influence_residuals": [VP, I64, I64, I32, VP, I32, I32, VP, I64, VP, VP, VP],
+    "uvc_influence_workspace_bytes": [I32, I32, I32, I32, C.POINTER(I64), C.POINTER(I32)],
+    "uvc_influence_topk": [C.POINTER(uvc_influence_args), VP],
+    "uvc_influence_self": [VP, I64, I32, I64, I32, VP, F32, VP, VP, VP],
+    "uvc_influence_expf": [VP, VP, I64, VP],
     "uvc_ood_logit_scores": [VP, I64, I64, I32, F32, VP, VP, VP, VP, VP],
     "uvc_class_moments_workspace_bytes": [I64, I32, C.POINTER(I64)],
     "uvc_class_moments": [VP, I64, VP, I32, VP, I64, I32, I32, VP, VP, VP, I64, VP],

@@ -1094,7 +1094,134 @@ def box_muller(u1, u2):
     return z0, z1
 
 
-OOD_MAX_D = 1016                                  # D + 8 augmentation columns is knn_topk's widest row
+INFLUENCE_MAX_CR = 4096                             # uvc_influence_topk's widest residual row
+INFLUENCE_TARGETS = ("label", "pred")               # uvc_influence_residuals' target_mode 0 / 1
+
+
+def influence_residuals(logits, labels=None, num_classes=None, target="label", *, r=None):
+    """``(r float32 [n, ceil8(C)], target int32 [n], rsq float32 [n])``: ``softmax(z) - e_target`` over columns [0, num_classes) (default: all)
+    of the float32 ``logits`` [n, ld], +0 on the padding columns; the target is the label (a label outside [0, C): a skipped row of zeros,
+    target -1) or, with ``target="pred"``, the row's first maximum; ``rsq`` the rows' squared norms (uvc_influence_residuals).  ``r``: a
+    float32 [n, ldr] tensor to fill, ldr a multiple of 8 and every column of it is written."""
+    L.require_cuda(logits, labels, r)
+    if target not in INFLUENCE_TARGETS:
+        raise L.UvcHipError(f"influence_residuals: target must be one of {INFLUENCE_TARGETS}, not {target!r}")
+    if logits.dim() != 2 or logits.dtype != torch.float32 or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise L.UvcHipError("influence_residuals: logits must be float32 [n, ld] with unit element stride")
+    n, cols = logits.shape
+    ld = logits.stride(0) if n > 1 else cols
+    Cc = cols if num_classes is None else int(num_classes)
+    if Cc > cols:
+        raise L.UvcHipError(f"influence_residuals: num_classes {Cc} is more than the logits' {cols} columns")
+    i64 = 0
+    if labels is not None:
+        if labels.dim() != 1 or labels.dtype not in (torch.int32, torch.int64) or labels.shape[0] != n or not labels.is_contiguous():
+            raise L.UvcHipError("influence_residuals: labels must be contiguous int32 or int64 [n]")
+        i64 = int(labels.dtype == torch.int64)
+    dev = logits.device
+    if r is None:
+        r = torch.empty(n, (max(Cc, 1) + 7) // 8 * 8, dtype=torch.float32, device=dev)
+    if r.dim() != 2 or r.dtype != torch.float32 or r.shape[0] != n or r.stride(1) != 1:
+        raise L.UvcHipError("influence_residuals: r must be float32 [n, ldr] with unit element stride")
+    ldr = r.shape[1]
+    if n > 1 and r.stride(0) != ldr:
+        raise L.UvcHipError("influence_residuals: r's rows must be dense (every column of r is written)")
+    tgt = torch.empty(n, dtype=torch.int32, device=dev)
+    rsq = torch.empty(n, dtype=torch.float32, device=dev)
+    L.check(L.lib().uvc_influence_residuals(L.ptr(logits), n, ld, Cc, L.ptr(labels), i64, INFLUENCE_TARGETS.index(target), L.ptr(r), ldr, L.ptr(tgt),
+                                            L.ptr(rsq), L.cur_stream()), "uvc_influence_residuals")
+    return r, tgt, rsq
+
+
+def influence_splits(nq, n, k, splits=0):
+    """(workspace bytes, split count used) of ``influence_topk`` for these shapes (uvc_influence_workspace_bytes)."""
+    nbytes, used = C.c_int64(0), C.c_int32(0)
+    L.check(L.lib().uvc_influence_workspace_bytes(int(nq), int(n), int(k), int(splits), C.byref(nbytes), C.byref(used)), "uvc_influence_workspace_bytes")
+    return nbytes.value, used.value
+
+
+def influence_topk(fq, fb, rq, rb, k, *, bias=1.0, exclude=None, splits=0, proponents=True, opponents=True):
+    """``((pos_vals, pos_idx), (neg_vals, neg_idx))``, float32 / int32 [nq, k] each: per query the k largest and the k smallest of
+    ``(fq . fb_i + bias) * (rq . rb_i)`` over the bank's rows -- descending / ascending, equal values by ascending bank row, (-inf, -1) /
+    (+inf, -1) in the slots a bank of fewer than k rows leaves; a NaN enters neither list (uvc_influence_topk).  ``fq`` [nq, D] and ``fb``
+    [n, D]: both bfloat16 or both float32; ``rq`` [nq, Cr] and ``rb`` [n, Cr]: float32, Cr a multiple of 8 (``influence_residuals``' rows);
+    a row stride above the width is taken as the leading dimension.  ``exclude`` int32 [nq]: one bank row per query to skip (-1: none).
+    ``proponents`` / ``opponents``: True, False (that list is None and not computed) or a ``(vals, idx)`` pair of tensors to fill.
+    ``splits``: ranges the bank is divided into (0: chosen from the shapes); every value gives the same bits."""
+    L.require_cuda(fq, fb, rq, rb, exclude)
+    if fq.dim() != 2 or fb.dim() != 2 or fq.shape[1] != fb.shape[1]:
+        raise L.UvcHipError("influence_topk: fq [nq, D] and fb [n, D] must share D")
+    if rq.dim() != 2 or rb.dim() != 2 or rq.shape[1] != rb.shape[1] or rq.shape[0] != fq.shape[0] or rb.shape[0] != fb.shape[0]:
+        raise L.UvcHipError("influence_topk: rq [nq, Cr] and rb [n, Cr] must share Cr and have one row per feature row")
+    if rq.dtype != torch.float32 or rb.dtype != torch.float32:
+        raise L.UvcHipError("influence_topk: residuals must be float32")
+    for t in (fq, fb, rq, rb):
+        if t.shape[1] > 1 and t.stride(1) != 1:
+            raise L.UvcHipError("influence_topk: rows must have unit element stride")
+    nq, D = fq.shape
+    n, Cr, k = fb.shape[0], rq.shape[1], int(k)
+    dev = fq.device
+    if exclude is not None and (exclude.dtype != torch.int32 or exclude.dim() != 1 or exclude.shape[0] != nq or not exclude.is_contiguous()):
+        raise L.UvcHipError("influence_topk: exclude must be contiguous int32 [nq]")
+    outs = []
+    for want in (proponents, opponents):
+        if want is False or want is None:
+            outs.append(None)
+            continue
+        v, i = ((torch.empty(nq, max(k, 0), dtype=torch.float32, device=dev), torch.empty(nq, max(k, 0), dtype=torch.int32, device=dev))
+                if want is True else want)
+        _chk(v, i)
+        if v.dtype != torch.float32 or i.dtype != torch.int32 or v.numel() < nq * k or i.numel() < nq * k:
+            raise L.UvcHipError("influence_topk: a list is (float32, int32) tensors of at least nq * k elements")
+        outs.append((v, i))
+    a = L.uvc_influence_args()
+    a.fq, a.fb, a.rq, a.rb, a.exclude = L.ptr(fq), L.ptr(fb), L.ptr(rq), L.ptr(rb), L.ptr(exclude)
+    if outs[0] is not None:
+        a.pos_vals, a.pos_idx = L.ptr(outs[0][0]), L.ptr(outs[0][1])
+    if outs[1] is not None:
+        a.neg_vals, a.neg_idx = L.ptr(outs[1][0]), L.ptr(outs[1][1])
+    a.ldfq, a.ldfb = (fq.stride(0) if nq > 1 else D), (fb.stride(0) if n > 1 else D)
+    a.ldrq, a.ldrb = (rq.stride(0) if nq > 1 else Cr), (rb.stride(0) if n > 1 else Cr)
+    a.bias = float(bias)
+    a.nq, a.n, a.D, a.Cr, a.k, a.splits = nq, n, D, Cr, k, int(splits)
+    a.q_dtype, a.bank_dtype = _knn_dtype(fq, "fq"), _knn_dtype(fb, "fb")
+    ws = None
+    if 1 <= k <= 64 and nq >= 1 and n >= 1:            # (the call itself refuses the rest, by name)
+        nbytes, _ = influence_splits(nq, n, k, splits)
+        if nbytes:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            a.workspace, a.workspace_bytes = L.ptr(ws), nbytes
+    L.check(L.lib().uvc_influence_topk(C.byref(a), L.cur_stream()), "uvc_influence_topk")
+    return outs[0], outs[1]
+
+
+def self_influence(features, rsq, *, bias=1.0, want_fsq=False):
+    """``(|f_i|^2 + bias) * rsq_i`` float32 [n] of the bfloat16 or float32 ``features`` [n, D] and ``influence_residuals``' ``rsq``
+    (uvc_influence_self); with ``want_fsq`` the pair ``(values, fsq)``."""
+    L.require_cuda(features, rsq)
+    if features.dim() != 2 or (features.shape[1] > 1 and features.stride(1) != 1):
+        raise L.UvcHipError("self_influence: features [n, D] with unit element stride")
+    n, D = features.shape
+    if rsq.dim() != 1 or rsq.dtype != torch.float32 or rsq.shape[0] != n or not rsq.is_contiguous():
+        raise L.UvcHipError("self_influence: rsq must be contiguous float32 [n]")
+    out = torch.empty(n, dtype=torch.float32, device=features.device)
+    fsq = torch.empty(n, dtype=torch.float32, device=features.device) if want_fsq else None
+    L.check(L.lib().uvc_influence_self(L.ptr(features), features.stride(0) if n > 1 else D, _knn_dtype(features, "features"), n, D, L.ptr(rsq),
+                                       float(bias), L.ptr(fsq), L.ptr(out), L.cur_stream()), "uvc_influence_self")
+    return (out, fsq) if want_fsq else out
+
+
+def influence_expf(d):
+    """``expf(d)`` of float32 ``d`` [n] by the device function ``influence_residuals`` calls (uvc_influence_expf)."""
+    _chk(d)
+    if d.dtype != torch.float32 or d.dim() != 1 or d.numel() == 0 or not d.is_contiguous():
+        raise L.UvcHipError("influence_expf: d must be non-empty contiguous float32 [n]")
+    e = torch.empty_like(d)
+    L.check(L.lib().uvc_influence_expf(L.ptr(d), L.ptr(e), d.numel(), L.cur_stream()), "uvc_influence_expf")
+    return e
+
+
+OOD_MAX_D = 1016                                 # D + 8 augmentation columns is knn_topk's widest row
 OOD_CHUNK_ROWS = 65536                              # tools/ood_time.py: within 5 % of the best of 16 384 / 65 536 / 262 144 at both ImageNet shapes
 
 
