@@ -804,6 +804,39 @@ int uvc_influence_self(const void* f, int64_t ldf, int32_t dtype, int64_t n, int
                        void* stream);
 int uvc_influence_expf(const float* d, float* e, int64_t n, void* stream);
 
+/* Two-model cascades (uvc_amd/compact_cascade.py, csrc/cascade.hip): the small model's answer stands where its confidence score reaches a
+ * threshold, the other rows are deferred to the large model.  Every call returns UVC_OK or refuses before anything is launched; no atomics,
+ * one writer per output element, the same bits on a repeat, a row's result independent of the rows beside it; 16-byte accesses where
+ * pointers and strides allow, element by element otherwise, with the same values either way.
+ *
+ * uvc_cascade_decide: logits float32 [n, ld], columns [0, C) valid, 1 <= C <= 65536, 1 <= n < 2^31; T > 0 finite; kind 0 = msp
+ * (max_c softmax(z / T)_c), 1 = margin (the largest minus the second largest entry of softmax(z / T); 1 at C = 1), 2 = entropy
+ * (1 + sum_c p_c log p_c / log C with 0 log 0 = 0; 1 at C = 1).  With m the FIRST maximum: d_c = z_c - m, d_c / T and expf in float32, the
+ * sums in float64 in a fixed lane order, every score rounded to float32 once.  score float32 [n], top1 int32 [n] (the first maximum),
+ * defer int32 [n] = !(score >= tau) compared in float32 (tau = -inf never defers, +inf always; a NaN tau is refused); each may be NULL,
+ * not all three.  A NaN in a valid column (or a row whose valid columns are all -inf): score NaN, top1 -1, defer 1.
+ *
+ * uvc_cascade_compact: defer int32 [n] (non-zero = deferred) -> idx int32 [n]: the deferred rows in ascending order in the first m slots,
+ * the slots past m NOT written; pos int32 [n]: a deferred row's slot in idx, -1 for a kept row; count int32 [1] = m.  idx or pos may be
+ * NULL.  Per-workgroup counts, their exclusive scan, then the writes; workspace >= uvc_cascade_compact_workspace_bytes(n), 4-byte aligned.
+ *
+ * uvc_cascade_gather: src [n * rows_per_item, width] of dtype (UVC_F32 / UVC_BF16; row stride ld_src elements) -> dst
+ * [m * rows_per_item, width] (row stride ld_dst): item j of dst is item idx[j] of src, copied bit for bit; an index outside [0, n) gives
+ * an item of +0.  0 <= m <= n comes from the host; m = 0 launches nothing.
+ *
+ * uvc_cascade_merge: out[b, :C] = pos[b] >= 0 ? z_large[pos[b], :C] : z_small[b, :C], bit for bit, for b in [0, n); source int32 [n] (or
+ * NULL) = 1 / 0.  z_large has m rows (NULL at m = 0); a pos at or past m gives a row of NaN and source -1.  The three row strides are
+ * independent; columns past C are not written. */
+int uvc_cascade_decide(const float* logits, int64_t n, int64_t ld, int32_t C, float T, int32_t kind, float tau, float* score, int32_t* top1,
+                       int32_t* defer, void* stream);
+int uvc_cascade_compact_workspace_bytes(int64_t n, int64_t* bytes);
+int uvc_cascade_compact(const int32_t* defer, int64_t n, int32_t* idx, int32_t* pos, int32_t* count, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+int uvc_cascade_gather(const void* src, int64_t ld_src, int32_t dtype, int64_t n, int64_t rows_per_item, int64_t width, const int32_t* idx,
+                       int64_t m, void* dst, int64_t ld_dst, void* stream);
+int uvc_cascade_merge(const float* z_small, int64_t ld_small, const float* z_large, int64_t ld_large, int64_t m, const int32_t* pos, int64_t n,
+                      int32_t C, float* out, int64_t ld_out, int32_t* source, void* stream);
+
 /* clip_grad_norm_(max_norm) + AdamW over flat float32 buffers (joint_train.py:428-429;
  * torch.optim.AdamW(lr, betas, eps, weight_decay) semantics, decoupled decay).
  * uvc_grad_sqnorm accumulates sum(g^2) of a segment into sq[0] (accumulate = 0 for the first segment) and leaves sqrt(sq[0]) -- the

@@ -299,6 +299,11 @@ _SIGNATURES = {
     "uvc_influence_topk": [C.POINTER(uvc_influence_args), VP],
     "uvc_influence_self": [VP, I64, I32, I64, I32, VP, F32, VP, VP, VP],
     "uvc_influence_expf": [VP, VP, I64, VP],
+    "uvc_cascade_decide": [VP, I64, I64, I32, F32, I32, F32, VP, VP, VP, VP],
+    "uvc_cascade_compact_workspace_bytes": [I64, C.POINTER(I64)],
+    "uvc_cascade_compact": [VP, I64, VP, VP, VP, VP, I64, VP],
+    "uvc_cascade_gather": [VP, I64, I32, I64, I64, I64, VP, I64, VP, I64, VP],
+    "uvc_cascade_merge": [VP, I64, VP, I64, I64, VP, I64, I32, VP, I64, VP, VP],
     "uvc_ood_logit_scores": [VP, I64, I64, I32, F32, VP, VP, VP, VP, VP],
     "uvc_class_moments_workspace_bytes": [I64, I32, C.POINTER(I64)],
     "uvc_class_moments": [VP, I64, VP, I32, VP, I64, I32, I32, VP, VP, VP, I64, VP],

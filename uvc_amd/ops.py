@@ -1221,6 +1221,122 @@ def influence_expf(d):
     return e
 
 
+CASCADE_SCORES = ("msp", "margin", "entropy")       # uvc_cascade_decide's kind 0 / 1 / 2
+CASCADE_MAX_C = 65536
+
+
+def _i32_vec(t, n, what):
+    if t.dim() != 1 or t.dtype != torch.int32 or t.shape[0] < n or not t.is_contiguous():
+        raise L.UvcHipError(f"{what} must be contiguous int32 of at least {n} elements")
+
+
+def cascade_decide(logits, num_classes=None, temperature=1.0, kind="msp", threshold=float("-inf"), *, score=True, top1=True, defer=True):
+    """``(score float32 [n], top1 int32 [n], defer int32 [n])`` per row of the float32 ``logits`` [n, ld] over columns [0, num_classes)
+    (default: all): the confidence of ``softmax(z / temperature)`` -- ``kind`` "msp", "margin" or "entropy" (``CASCADE_SCORES``) --, the
+    first maximum and ``!(score >= threshold)`` in float32 (uvc_cascade_decide; a NaN row: NaN, -1, 1).  ``score`` / ``top1`` / ``defer``:
+    True, False (None comes back, nothing is computed into it) or a contiguous tensor to write into."""
+    L.require_cuda(logits)
+    if kind not in CASCADE_SCORES:
+        raise L.UvcHipError(f"cascade_decide: kind must be one of {CASCADE_SCORES}, not {kind!r}")
+    n, cols, ld = _rows_f32(logits, "cascade_decide: logits")
+    Cc = cols if num_classes is None else int(num_classes)
+    if Cc > cols:
+        raise L.UvcHipError(f"cascade_decide: num_classes {Cc} is more than the logits' {cols} columns")
+    outs = []
+    for want, dt, name in ((score, torch.float32, "score"), (top1, torch.int32, "top1"), (defer, torch.int32, "defer")):
+        if want is False or want is None:
+            outs.append(None)
+            continue
+        t = torch.empty(n, dtype=dt, device=logits.device) if want is True else want
+        L.require_cuda(t)
+        if t.dim() != 1 or t.dtype != dt or t.shape[0] != n or not t.is_contiguous():
+            raise L.UvcHipError(f"cascade_decide: {name} must be contiguous {dt} [n]")
+        outs.append(t)
+    L.check(L.lib().uvc_cascade_decide(L.ptr(logits), n, ld, Cc, float(temperature), CASCADE_SCORES.index(kind), float(threshold), L.ptr(outs[0]),
+                                       L.ptr(outs[1]), L.ptr(outs[2]), L.cur_stream()), "uvc_cascade_decide")
+    return tuple(outs)
+
+
+def cascade_compact_workspace_bytes(n):
+    nbytes = C.c_int64(0)
+    L.check(L.lib().uvc_cascade_compact_workspace_bytes(int(n), C.byref(nbytes)), "uvc_cascade_compact_workspace_bytes")
+    return nbytes.value
+
+
+def cascade_compact(defer, *, idx=None, pos=None, count=None, workspace=None):
+    """``(idx int32 [n], pos int32 [n], count int32 [1])`` of the int32 ``defer`` [n] (non-zero: deferred): the deferred rows in ascending
+    order in ``idx[:count]`` (the slots behind them are NOT written), every row's slot in ``idx`` or -1 in ``pos``, their number in
+    ``count`` -- all on the device, nothing is read back (uvc_cascade_compact).  The outputs and the workspace may be handed in."""
+    _chk(defer)
+    if defer.dim() != 1 or defer.dtype != torch.int32 or defer.numel() == 0:
+        raise L.UvcHipError("cascade_compact: defer must be non-empty contiguous int32 [n]")
+    n, dev = defer.shape[0], defer.device
+    idx = torch.empty(n, dtype=torch.int32, device=dev) if idx is None else idx
+    pos = torch.empty(n, dtype=torch.int32, device=dev) if pos is None else pos
+    count = torch.empty(1, dtype=torch.int32, device=dev) if count is None else count
+    L.require_cuda(idx, pos, count, workspace)
+    _i32_vec(idx, n, "cascade_compact: idx")
+    _i32_vec(pos, n, "cascade_compact: pos")
+    _i32_vec(count, 1, "cascade_compact: count")
+    if workspace is None:
+        workspace = torch.empty(cascade_compact_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    L.check(L.lib().uvc_cascade_compact(L.ptr(defer), n, L.ptr(idx), L.ptr(pos), L.ptr(count), L.ptr(workspace), workspace.numel(), L.cur_stream()),
+            "uvc_cascade_compact")
+    return idx, pos, count
+
+
+def cascade_gather(src, idx, m, rows_per_item=1, *, out=None):
+    """``[m * rows_per_item, width]``: the items ``idx[:m]`` (int32, on the device) of the bfloat16 or float32 ``src`` [n * rows_per_item,
+    width], an item being ``rows_per_item`` consecutive rows, copied bit for bit; an index outside [0, n) gives an item of +0
+    (uvc_cascade_gather).  ``m`` is a host integer; 0 gives an empty tensor and launches nothing.  A row stride above the width is taken
+    as the leading dimension, of ``src`` and of ``out``."""
+    L.require_cuda(src, idx, out)
+    if src.dim() != 2 or (src.shape[1] > 1 and src.stride(1) != 1) or src.shape[0] == 0:
+        raise L.UvcHipError("cascade_gather: src [rows, width] with unit element stride")
+    rpi, m = int(rows_per_item), int(m)
+    rows, width = src.shape
+    if rpi < 1 or rows % rpi:
+        raise L.UvcHipError(f"cascade_gather: {rows} rows are not a multiple of rows_per_item {rpi}")
+    n = rows // rpi
+    if not 0 <= m <= n:
+        raise L.UvcHipError(f"cascade_gather: m {m} must lie in [0, {n}]")
+    _i32_vec(idx, m, "cascade_gather: idx")
+    if out is None:
+        out = torch.empty(m * rpi, width, dtype=src.dtype, device=src.device)
+    if out.dim() != 2 or out.dtype != src.dtype or tuple(out.shape) != (m * rpi, width) or (width > 1 and out.stride(1) != 1):
+        raise L.UvcHipError(f"cascade_gather: out must be {src.dtype} [{m * rpi}, {width}] with unit element stride")
+    lds, ldd = (src.stride(0) if rows > 1 else width), (out.stride(0) if m * rpi > 1 else width)
+    L.check(L.lib().uvc_cascade_gather(L.ptr(src), lds, _knn_dtype(src, "src"), n, rpi, width, L.ptr(idx), m, L.ptr(out) if m else 0, ldd, L.cur_stream()),
+            "uvc_cascade_gather")
+    return out
+
+
+def cascade_merge(z_small, z_large, pos, num_classes=None, *, out=None, source=True):
+    """``(out float32 [n, C], source int32 [n])``: ``out[b] = z_large[pos[b]]`` where ``pos[b] >= 0`` and ``z_small[b]`` elsewhere, over the
+    columns [0, C) (default: the narrower of the two) bit for bit, and 1 / 0 beside it (uvc_cascade_merge).  ``z_large``: [m, ldl] or None
+    (nothing was deferred); a row stride above the width is taken as the leading dimension of either input and of ``out``."""
+    L.require_cuda(z_small, z_large, pos, out)
+    n, cs, lds = _rows_f32(z_small, "cascade_merge: z_small")
+    m, cl, ldl = (0, cs, cs) if z_large is None or z_large.shape[0] == 0 else _rows_f32(z_large, "cascade_merge: z_large")
+    Cc = min(cs, cl) if num_classes is None else int(num_classes)
+    if Cc > min(cs, cl):
+        raise L.UvcHipError(f"cascade_merge: num_classes {Cc} is more than the logits' {min(cs, cl)} columns")
+    _i32_vec(pos, n, "cascade_merge: pos")
+    if out is None:
+        out = torch.empty(n, max(Cc, 0), dtype=torch.float32, device=z_small.device)
+    no, co, ldo = _rows_f32(out, "cascade_merge: out")
+    if no != n or co < Cc:
+        raise L.UvcHipError(f"cascade_merge: out must be float32 [{n}, >= {Cc}]")
+    src = None
+    if source is not False and source is not None:
+        src = torch.empty(n, dtype=torch.int32, device=z_small.device) if source is True else source
+        L.require_cuda(src)
+        _i32_vec(src, n, "cascade_merge: source")
+    L.check(L.lib().uvc_cascade_merge(L.ptr(z_small), lds, L.ptr(z_large) if m else 0, ldl, m, L.ptr(pos), n, Cc, L.ptr(out), ldo, L.ptr(src),
+                                      L.cur_stream()), "uvc_cascade_merge")
+    return out, src
+
+
 OOD_MAX_D = 1016                                 # D + 8 augmentation columns is knn_topk's widest row
 OOD_CHUNK_ROWS = 65536                              # tools/ood_time.py: within 5 % of the best of 16 384 / 65 536 / 262 144 at both ImageNet shapes
 
