@@ -837,6 +837,32 @@ int uvc_cascade_gather(const void* src, int64_t ld_src, int32_t dtype, int64_t n
 int uvc_cascade_merge(const float* z_small, int64_t ld_small, const float* z_large, int64_t ld_large, int64_t m, const int32_t* pos, int64_t n,
                       int32_t C, float* out, int64_t ld_out, int32_t* source, void* stream);
 
+/* Taylor gate scores of compact models (uvc_amd/compact_prune.py, csrc/prune.hip): the first-order importance of a multiplicative gate on
+ * every kept head's attention output and on every MLP unit's GELU output (Molchanov et al., CVPR 2019; Michel et al., NeurIPS 2019), around
+ * uvc_vit_compact_gate_grads of uvc_vit.h.  Each call returns UVC_OK or refuses with UVC_ERR_ARG before anything is launched (outputs
+ * untouched); no atomics, one writer per output element, fixed summation orders: the same bits on a repeat and for any B, an image's row
+ * independent of its neighbours.
+ *
+ * uvc_gate_dots: out[b, col0 + g] = sum_n sum_{c in group g} a[b N + n, c] * da[b N + n, c] for b < B, g < width / group; a and da are
+ * [B N, width] row-major with leading dimensions lda / ldda (elements), image b owns rows [b N, (b + 1) N); group 1, 16, 32, 48 or 64 with
+ * width % group == 0, group g the columns [g group, (g + 1) group); width a positive multiple of 16; out float32 [B, ld_out],
+ * ld_out >= col0 + width / group.  Plain form (aux == dA == NULL; a head's attention output against its gradient): a and da of type T
+ * (dtype UVC_F32 / UVC_BF16), nothing else is written.  Fused form (aux and dA given; a unit's GELU output against the raw fc2 input
+ * gradient): a = u (T), da = dh FLOAT32, aux = GELU'(pre-activation) (T, ldaux), and dA[m, i] (T, lddA) = round_T(dh[m, i] * float(aux[m, i])),
+ * one float32 multiply rounded once -- what UVC_EPI_MUL_AUX leaves -- so dh is read once for both.  Products and sums in float64 in a fixed
+ * order (a lane's rows ascending, then the partial sums of a column in (wave, lane) order, then a group's columns ascending), ONE rounding to
+ * float32: |out - exact| <= 2^-24 |exact| (1 + small) + n 2^-52 sum |terms|.  Bandwidth-bound: every operand element is read once, lanes run
+ * along the columns, 16-byte accesses where the leading dimensions and every pointer are multiples of 16 bytes (element by element
+ * otherwise: the same values), the four waves of a workgroup split an image's rows and meet in LDS in wave order; 64-bit offsets.
+ * B <= 65535.
+ *
+ * uvc_gate_accumulate: s float32 [B, ld] with G <= ld columns; sum_sq[g] += s[b, g]^2 and sum_abs[g] += |s[b, g]| (float64 [G] each) as
+ * one ascending chain over b per gate that goes on from the stored value: the sums over a split do not depend on how its images were
+ * batched into calls (as uvc_ig_accumulate's). */
+int uvc_gate_dots(const void* a, int64_t lda, const void* da, int64_t ldda, const void* aux, int64_t ldaux, void* dA, int64_t lddA, int32_t B,
+                  int32_t N, int32_t width, int32_t group, float* out, int64_t ld_out, int32_t col0, int32_t dtype, void* stream);
+int uvc_gate_accumulate(const float* s, int64_t ld, int32_t B, int32_t G, double* sum_sq, double* sum_abs, void* stream);
+
 /* clip_grad_norm_(max_norm) + AdamW over flat float32 buffers (joint_train.py:428-429;
  * torch.optim.AdamW(lr, betas, eps, weight_decay) semantics, decoupled decay).
  * uvc_grad_sqnorm accumulates sum(g^2) of a segment into sq[0] (accumulate = 0 for the first segment) and leaves sqrt(sq[0]) -- the

@@ -273,6 +273,28 @@ int uvc_vit_compact_input_grad(const uvc_vit_cfg* cfg, const uvc_compact_block* 
 int uvc_vit_compact_loss_grad(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, const int32_t* labels,
                               int32_t num_labels, int32_t kind, float* d_rows, float* loss_out, void* stream);
 
+/* Taylor gate scores: which kept heads and MLP units of a compact file can go next (python -m uvc_amd.compact_prune).  gates: device float32
+ * [B, G], G = sum_k (heads_k + hidden_k), columns block-ascending, a block's heads first, then its hidden_k units (padding units included:
+ * their entries are exact zeros).  gates[b, .] is the gradient of image b's OWN cross-entropy (uvc_loss_seed kind 0 on the eval logits over
+ * [0, num_labels): uvc_vit_compact_loss_grad's loss, not the batch mean) with respect to a multiplicative gate on each head's attention
+ * output and on each unit's GELU output, at gate = 1:
+ *   head (k, j): sum_n sum_{c < v_dim} o_k[b, n, j v_dim + c] * dO_k[b, n, j v_dim + c]     (dO: the attn.proj input gradient)
+ *   unit (k, i): sum_n u_k[b, n, i] * (g_k W2_k)[b, n, i]                                   (the raw fc2 input gradient, before GELU')
+ * the quantity whose square (Molchanov et al., CVPR 2019) or absolute value (Michel et al., NeurIPS 2019) is averaged over a dataset.
+ * One stream: uvc_vit_compact_train_forward's walk (logits / logits_dist are the eval forward's bits), the seed, then
+ * uvc_vit_compact_backward's walk with dgrads only -- no weight-gradient GEMM, column sum or LayerNorm parameter reduction -- with one plain
+ * uvc_gate_dots (uvc_kernels.h; group = v_dim) behind each attn.proj dgrad, and each fc2 dgrad run with UVC_EPI_NONE into a float32 scratch
+ * followed by one fused uvc_gate_dots (group = 1), which also writes the dA the fc1 dgrad reads.  The walk ends behind the last dot it
+ * needs: the lowest block that has a head or a unit.  A block without heads, or without units, contributes no columns and passes the stream
+ * through.  io as for uvc_vit_compact_attribution (the TRAINING shadow; workspace of uvc_vit_compact_gate_grads_workspace_bytes; x, not
+ * patches_in); accumulate must be 0.  labels: device int32 [B], clamped into [0, num_labels) by the kernel -- callers check them on the
+ * host.  1 <= num_labels <= num_classes, otherwise UVC_ERR_ARG.  loss_out: device float32 [B], or NULL.  Sequences above 256 tokens:
+ * UVC_ERR_UNSUPPORTED and -1 from the workspace query, as every compact training entry point.  Every refusal comes before anything is
+ * launched.  Deterministic; an image's row does not depend on its neighbours. */
+int64_t uvc_vit_compact_gate_grads_workspace_bytes(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int32_t batch);
+int uvc_vit_compact_gate_grads(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, const int32_t* labels,
+                               int32_t num_labels, float* gates, float* loss_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

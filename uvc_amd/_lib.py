@@ -304,6 +304,8 @@ _SIGNATURES = {
     "uvc_cascade_compact": [VP, I64, VP, VP, VP, VP, I64, VP],
     "uvc_cascade_gather": [VP, I64, I32, I64, I64, I64, VP, I64, VP, I64, VP],
     "uvc_cascade_merge": [VP, I64, VP, I64, I64, VP, I64, I32, VP, I64, VP, VP],
+    "uvc_gate_dots": [VP, I64, VP, I64, VP, I64, VP, I64, I32, I32, I32, I32, VP, I64, I32, I32, VP],
+    "uvc_gate_accumulate": [VP, I64, I32, I32, VP, VP, VP],
     "uvc_ood_logit_scores": [VP, I64, I64, I32, F32, VP, VP, VP, VP, VP],
     "uvc_class_moments_workspace_bytes": [I64, I32, C.POINTER(I64)],
     "uvc_class_moments": [VP, I64, VP, I32, VP, I64, I32, I32, VP, VP, VP, I64, VP],
@@ -369,7 +371,8 @@ VIT_SYMBOLS = ["uvc_vit_layout", "uvc_vit_workspace_bytes", "uvc_vit_ws_offsets"
                "uvc_vit_compact_attribution_workspace_bytes", "uvc_vit_compact_attribution",   # (uvc_amd/compact_attribution.py)
                "uvc_vit_compact_input_grad_workspace_bytes", "uvc_vit_compact_input_grad",   # (input gradients: uvc_amd/compact_pixel.py)
                "uvc_vit_compact_loss_grad",   # (the gradient of an attack loss: uvc_amd/compact_robust.py)
-               "uvc_vit_compact_features"]   # (features for k-NN and re-heading: uvc_amd/compact_transfer.py)
+               "uvc_vit_compact_features",   # (features for k-NN and re-heading: uvc_amd/compact_transfer.py)
+               "uvc_vit_compact_gate_grads_workspace_bytes", "uvc_vit_compact_gate_grads"]   # (Taylor gate scores: uvc_amd/compact_prune.py)
 
 
 def side_stream(device, priority_class=None):

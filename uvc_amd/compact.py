@@ -29,7 +29,8 @@ apart: the function ``compact_train.CompactTrainer`` fine-tunes (a fine-tuned fi
 gradient-weighted rollout (``uvc_vit_compact_attribution`` through ``compact_attribution.CompactAttributionViT``; ``reference_attribution``).
 Whether such a map is faithful -- the perturbation test, deletion curves and their areas -- is ``python -m uvc_amd.compact_perturb``.
 Another label set -- the model's features for a dataset (``CompactVisionTransformer.features``), their k-NN top-1 and a new head that
-``finetune`` trains -- is ``python -m uvc_amd.compact_transfer``.
+``finetune`` trains -- is ``python -m uvc_amd.compact_transfer``.  A file that is still too large -- Taylor scores of its kept heads and
+units, and the smaller file they imply -- is ``python -m uvc_amd.compact_prune``.
 """
 from __future__ import annotations
 
@@ -443,7 +444,9 @@ def _bind():
         tails["input_grad"] = tails["attribution"]
         tails["loss_grad"] = [C.POINTER(uvc_vit_io), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         tails["features"] = [C.POINTER(uvc_vit_io), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        tails["gate_grads"] = [C.POINTER(uvc_vit_io), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         tails["rollout_workspace_bytes"] = tails["attribution_workspace_bytes"] = tails["input_grad_workspace_bytes"] = tails["workspace_bytes"]
+        tails["gate_grads_workspace_bytes"] = tails["workspace_bytes"]
         for n, tail in tails.items():
             f = getattr(lib, "uvc_vit_compact_" + n)
             f.argtypes, f.restype = head + tail, C.c_int64 if n.endswith("workspace_bytes") else C.c_int
@@ -539,15 +542,15 @@ class _CompactModule(nn.Module):
 
     def _workspace(self, B, training):
         """One workspace per mode (eval, training, "rollout": the eval forward that keeps qkv and lse per block, or "attribution": the
-        training set plus what the relevance walk adds, or "input_grad": the training set plus what the walk down to the patch rows adds), for
-        the last batch size seen."""
+        training set plus what the relevance walk adds, or "input_grad": the training set plus what the walk down to the patch rows adds, or
+        "gate_grads": the training set plus the float32 fc2 dgrad of the gate walk), for the last batch size seen."""
         mode = training if isinstance(training, str) else bool(training)
         key = (B, mode)
         if key not in self._ws:
             from . import _lib as L
             entry = {False: "uvc_vit_compact_workspace_bytes", True: "uvc_vit_compact_train_workspace_bytes",
                      "rollout": "uvc_vit_compact_rollout_workspace_bytes", "attribution": "uvc_vit_compact_attribution_workspace_bytes",
-                     "input_grad": "uvc_vit_compact_input_grad_workspace_bytes"}[mode]
+                     "input_grad": "uvc_vit_compact_input_grad_workspace_bytes", "gate_grads": "uvc_vit_compact_gate_grads_workspace_bytes"}[mode]
             n = self._lib_call(entry, B)
             if n < 0:
                 L.check(-1, entry)

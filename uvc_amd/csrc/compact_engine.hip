@@ -10,7 +10,8 @@
 // a target pick, and the same backward walk without any parameter gradient, with one uvc_attention_relevance_step per attention block.
 // uvc_vit_compact_input_grad is that forward and target pick, the dgrad walk through every block, the masked row copy of token assembly's
 // backward and the patch-embedding dgrad: the gradient of the class logit at the input, as patch rows.  uvc_vit_compact_loss_grad is the same
-// with the seed of an attack loss (uvc_loss_seed, robust.hip) in the target pick's place.
+// with the seed of an attack loss (uvc_loss_seed, robust.hip) in the target pick's place.  uvc_vit_compact_gate_grads is the training forward, the
+// cross-entropy seed and the dgrad walk with one uvc_gate_dots (prune.hip) behind each attn.proj dgrad and one in place of each fc2 dgrad's epilogue.
 #include "engine_host.h"
 
 namespace {
@@ -73,7 +74,8 @@ int check_train(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nbl
 // training set, and behind it the two [B, N] vectors, the one-hot logit gradients and 2 D floats the LayerNorm backward's parameter-gradient
 // pointers aim at (never reduced into: see ln_bwd).  Input gradient (CARVE_INPUT): the training set, the one-hot logit gradients and the 2 D
 // floats, the [K0, D] transposed patch-embedding weight (T) and the (N + 2) D floats that take the batch sums of uvc_assemble_tokens_bwd.
-enum { CARVE_EVAL = 0, CARVE_TRAIN = 1, CARVE_ROLLOUT = 2, CARVE_ATTRIB = 3, CARVE_INPUT = 4 };
+// Gate gradients (CARVE_GATES): the training set, the logit gradients and the 2 D floats, and the float32 [M, widest hidden] raw fc2 dgrad.
+enum { CARVE_EVAL = 0, CARVE_TRAIN = 1, CARVE_ROLLOUT = 2, CARVE_ATTRIB = 3, CARVE_INPUT = 4, CARVE_GATES = 5 };
 struct BlockBufs {
   void* h1; void* qkv; void* o; float* lse; float* mean1; float* rstd1; void* x1;
   void* h2; float* mean2; float* rstd2; void* gp; void* u; void* xo;
@@ -87,6 +89,7 @@ struct Work {
   float* roll[2];      // rollout, attribution: the row vector ping-pongs between them
   float* dl[2]; float* ln_scratch;      // attribution, input gradient: d_logits (/ d_logits_dist) [B, NC], the unused dgamma | dbeta [2 D]
   void* wpt; float* asm_scratch;        // input gradient: W_patch^T [K0, D] (T), the unused dpos [N, D] | dcls [D] | ddist [D]
+  float* dh;                            // gate gradients: g . W2 [M, maxF] before GELU' (uvc_gate_dots' fused form makes dA of it)
 };
 
 int64_t train_tn_ws(const CDims& d, const uvc_compact_block* blocks, int nblocks) {
@@ -101,7 +104,7 @@ int64_t train_tn_ws(const CDims& d, const uvc_compact_block* blocks, int nblocks
 }
 
 int64_t carve(const CDims& d, const uvc_compact_block* blocks, int nblocks, int mode, char* base, Work& w) {
-  const bool training = mode == CARVE_TRAIN || mode == CARVE_ATTRIB || mode == CARVE_INPUT;
+  const bool training = mode == CARVE_TRAIN || mode == CARVE_ATTRIB || mode == CARVE_INPUT || mode == CARVE_GATES;
   Carver c{base, 0};
   const int64_t M = d.M, MD = M * d.D;
   memset(&w, 0, sizeof(w));
@@ -164,7 +167,7 @@ int64_t carve(const CDims& d, const uvc_compact_block* blocks, int nblocks, int 
   w.dhc = c.take((int64_t)d.B * d.ntok * d.D * d.tsz);
   w.dpe = c.take((int64_t)d.B * d.np * d.D * d.tsz);
   if (mode == CARVE_ATTRIB) { w.roll[0] = (float*)c.take(M * 4); w.roll[1] = (float*)c.take(M * 4); }
-  if (mode == CARVE_ATTRIB || mode == CARVE_INPUT) {
+  if (mode == CARVE_ATTRIB || mode == CARVE_INPUT || mode == CARVE_GATES) {
     w.dl[0] = (float*)c.take((int64_t)d.B * d.NC * 4); w.dl[1] = (float*)c.take((int64_t)d.B * d.NC * 4);
     w.ln_scratch = (float*)c.take((int64_t)2 * d.D * 4);
   }
@@ -172,6 +175,7 @@ int64_t carve(const CDims& d, const uvc_compact_block* blocks, int nblocks, int 
     w.wpt = c.take((int64_t)d.K0 * d.D * d.tsz);
     w.asm_scratch = (float*)c.take((int64_t)(d.N + 2) * d.D * 4);
   }
+  if (mode == CARVE_GATES) w.dh = (float*)c.take(M * (d.maxF > 0 ? d.maxF : 1) * 4);
   return c.off;
 }
 
@@ -259,7 +263,7 @@ int setup_train(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block* blocks,
   TRY(check_train(cfg, blocks, nblocks));
   if (!io || !io->params || !io->shadow || !io->workspace || io->batch <= 0) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact training: null io member (params, shadow, workspace) or batch <= 0");
   if (io->accumulate != 0.f) return uvc_set_error_msg(UVC_ERR_UNSUPPORTED, "uvc_vit_compact training: gradient accumulation (io.accumulate must be 0)");
-  if (!bind(c, cfg, blocks, nblocks, io, stream, mode)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact training: workspace too small (uvc_vit_compact_train_workspace_bytes; attribution: uvc_vit_compact_attribution_workspace_bytes; input gradient: uvc_vit_compact_input_grad_workspace_bytes)");
+  if (!bind(c, cfg, blocks, nblocks, io, stream, mode)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact training: workspace too small (uvc_vit_compact_train_workspace_bytes; attribution: uvc_vit_compact_attribution_workspace_bytes; input gradient: uvc_vit_compact_input_grad_workspace_bytes; gate gradients: uvc_vit_compact_gate_grads_workspace_bytes)");
   return UVC_OK;
 }
 
@@ -554,9 +558,13 @@ extern "C" int uvc_vit_compact_train_forward(const uvc_vit_cfg* cfg, const uvc_c
 // per block with heads right behind the attn.proj dgrad (*rel: the row vector, which ping-pongs with *rel_other); the walk ends behind the
 // step of the lowest block with heads.  d_rows != nullptr (input gradient; G and rel are null): the dgrad chain alone through every block down to
 // block 0 -- a bias-only branch passes the stream through unchanged -- then token assembly's backward (its batch sums go to scratch) and the
-// patch-embedding dgrad d_rows [B np, K0] (float32) = dpe . W_patch, which reads the workspace's transposed weight copy.
+// patch-embedding dgrad d_rows [B np, K0] (float32) = dpe . W_patch, which reads the workspace's transposed weight copy.  gates != nullptr
+// (gate gradients; G, rel and d_rows are null): the dgrad chain alone, with gates [B, sum_k (heads_k + hidden_k)] filled on the way -- one
+// plain uvc_gate_dots(o, dO) per block with heads behind its attn.proj dgrad, and per block with units the fc2 dgrad without its epilogue
+// into the float32 scratch w.dh, then one fused uvc_gate_dots(u, dh, GELU' -> dA); the walk ends behind the dot of the lowest block that
+// has a head or a unit, and a bias-only branch passes the stream through unchanged.
 static int backward_walk(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int nblocks, const float* dl, const float* dld, float* G,
-                         float** rel, float** rel_other, float* d_rows = nullptr) {
+                         float** rel, float** rel_other, float* d_rows = nullptr, float* gates = nullptr) {
   const uvc_vit_io* io = c.io;
   void* stream = c.st;
   const CDims& d = c.d;
@@ -572,7 +580,11 @@ static int backward_walk(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block
   auto gp = [&](int64_t off) -> float* { return G ? G + off : nullptr; };      // a gradient slot; nullptr without parameter gradients
   int low = nblocks;                                         // the lowest block with heads: where the attribution walk ends
   for (int k = nblocks - 1; k >= 0; --k) if (blocks[k].heads > 0) low = k;
-  if (!G && !d_rows && low == nblocks) return UVC_OK;        // no block has heads: the start vector is the answer
+  int64_t ngates = 0, gcol[UVC_VIT_MAX_DEPTH];                // gate gradients: block k's first column, and the lowest block with a column
+  int glow = nblocks;
+  for (int k = nblocks - 1; k >= 0; --k) if (blocks[k].heads > 0 || blocks[k].hidden > 0) glow = k;
+  for (int k = 0; k < nblocks; ++k) { gcol[k] = ngates; ngates += blocks[k].heads + blocks[k].hidden; }
+  if (gates ? glow == nblocks : (!G && !d_rows && low == nblocks)) return UVC_OK;        // no block has heads: the start vector is the answer (no gate: nothing to fill)
   // heads: dhc = dlogits . W, dW = dlogits^T . hc, db = colsum(dlogits)
   TRY(nt(c, dl, 1, wt(so.head_wt), w.dhc, 0, d.B, d.D, d.NC, UVC_EPI_NONE, nullptr, nullptr, nullptr, nullptr, 0, d.ntok * d.D));
   if (G) TRY(tn(c, dl, 1, w.hc, G + o.head_w, G + o.head_b, d.B, d.NC, d.D, 0, d.ntok * d.D));
@@ -596,7 +608,12 @@ static int backward_walk(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block
     // MLP branch: g = dL/d(block output)
     if (F > 0) {
       void* g = w.g[cur];
-      TRY(nt(c, g, gf, wt(so.blk_wt[k][3]), w.dA, 0, d.M, F, d.D, UVC_EPI_MUL_AUX, nullptr, nullptr, b.gp));      // dA = (g . W2) * GELU'
+      if (gates) {                                            // dh = g . W2 (float32), then the units' dots and dA = dh * GELU' in one pass over dh
+        TRY(nt(c, g, gf, wt(so.blk_wt[k][3]), w.dh, 1, d.M, F, d.D, UVC_EPI_NONE));
+        TRY(uvc_gate_dots(b.u, F, w.dh, F, b.gp, F, w.dA, F, d.B, d.N, F, 1, gates, ngates, (int32_t)(gcol[k] + bk.heads), d.dtype, stream));
+        if (k == glow && bk.heads == 0) return UVC_OK;        // nothing below it is needed
+      } else
+        TRY(nt(c, g, gf, wt(so.blk_wt[k][3]), w.dA, 0, d.M, F, d.D, UVC_EPI_MUL_AUX, nullptr, nullptr, b.gp));      // dA = (g . W2) * GELU'
       if (G) TRY(tn(c, g, gf, b.u, G + q[10], G + q[11], d.M, d.D, F));
       TRY(nt(c, w.dA, 0, wt(so.blk_wt[k][2]), w.dH, 0, d.M, d.D, F, UVC_EPI_NONE));
       if (G) TRY(tn(c, w.dA, 0, b.h2, G + q[8], G + q[9], d.M, F, d.D));
@@ -611,6 +628,10 @@ static int backward_walk(Ctx& c, const uvc_vit_cfg* cfg, const uvc_compact_block
       void* gB = w.g[cur];
       TRY(nt(c, gB, gf, wt(so.blk_wt[k][1]), w.dO, 0, d.M, no, d.D, UVC_EPI_NONE));
       if (G) TRY(tn(c, gB, gf, b.o, G + q[4], G + q[5], d.M, d.D, no));
+      if (gates) {
+        TRY(uvc_gate_dots(b.o, no, w.dO, no, nullptr, 0, nullptr, 0, d.B, d.N, no, bk.v_dim, gates, ngates, (int32_t)gcol[k], d.dtype, stream));
+        if (k == glow) return UVC_OK;                         // nothing below it is needed
+      }
       if (rel) {
         uvc_attn_relevance_args ra;
         memset(&ra, 0, sizeof(ra));
@@ -772,4 +793,27 @@ extern "C" int uvc_vit_compact_loss_grad(const uvc_vit_cfg* cfg, const uvc_compa
   TRY(uvc_vit_compact_layout(cfg, blocks, nblocks, &o, nullptr));
   TRY(uvc_cast_transpose(io->params + o.patch_w, d.D, d.K0, nullptr, c.w.wpt, d.dtype, stream));
   return backward_walk(c, cfg, blocks, nblocks, c.w.dl[0], c.w.dl[1], nullptr, nullptr, nullptr, d_rows);
+}
+
+// ---- Taylor gate scores (python -m uvc_amd.compact_prune) ---------------------------------------------------------------------------------
+extern "C" int64_t uvc_vit_compact_gate_grads_workspace_bytes(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, int32_t batch) {
+  if (check_train(cfg, blocks, nblocks)) return -1;
+  if (batch <= 0) { uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_gate_grads_workspace_bytes: batch <= 0"); return -1; }
+  Work w;
+  return carve(cdims_of(*cfg, blocks, nblocks, batch), blocks, nblocks, CARVE_GATES, nullptr, w);
+}
+
+// uvc_vit_compact_loss_grad's forward and cross-entropy seed, then the dgrad walk with the gate dots on the way (backward_walk, gates)
+extern "C" int uvc_vit_compact_gate_grads(const uvc_vit_cfg* cfg, const uvc_compact_block* blocks, int32_t nblocks, const uvc_vit_io* io, const int32_t* labels,
+                                          int32_t num_labels, float* gates, float* loss_out, void* stream) {
+  if (!gates || !labels) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_gate_grads: null gates or labels");
+  Ctx c;
+  TRY(setup_train(c, cfg, blocks, nblocks, io, stream, CARVE_GATES));
+  if (!io->x || !io->logits || (cfg->ntok == 2 && !io->logits_dist)) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_gate_grads: null io member");
+  const CDims& d = c.d;
+  if (num_labels < 1 || num_labels > d.NC) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_gate_grads: num_labels must lie in [1, num_classes]");
+  if (d.B > 65535) return uvc_set_error_msg(UVC_ERR_ARG, "uvc_vit_compact_gate_grads: at most 65535 images a call (uvc_gate_dots)");
+  TRY(forward(c, cfg, blocks, nblocks, 1));
+  TRY(uvc_loss_seed(io->logits, d.ntok == 2 ? io->logits_dist : nullptr, labels, d.B, d.NC, num_labels, 0, c.w.dl[0], c.w.dl[1], loss_out, stream));
+  return backward_walk(c, cfg, blocks, nblocks, c.w.dl[0], c.w.dl[1], nullptr, nullptr, nullptr, nullptr, gates);
 }

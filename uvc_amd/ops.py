@@ -1777,6 +1777,53 @@ def pgd_step(x, x0, direction, P, step, eps, lo, hi, mode=0, out=None, out_t=Non
     return out
 
 
+GATE_GROUPS = (1, 16, 32, 48, 64)                   # uvc_gate_dots' group widths
+
+
+def gate_dots(a, da, B, group, aux=None, out=None, col0=0):
+    """``out`` float32 [B, ld_out] with ``out[b, col0 + g] = sum_n sum_{c in group g} a * da`` over image b's rows of ``a`` and ``da``
+    [B * N, width] (row-major views with a unit column stride), float64 arithmetic rounded once (uvc_gate_dots).  Plain form: ``da`` of
+    ``a``'s type (float32 or bfloat16), returns ``out``.  Fused form (``aux`` given, of ``a``'s type and shape): ``da`` float32, returns
+    ``(out, dA)`` with ``dA = (da * aux.float()).to(a.dtype)`` written in the same pass."""
+    L.require_cuda(a, da, aux, out)                  # (strided row views are the point: leading dimensions go to the kernel)
+    dt = _row_dtype(a, "gate_dots")
+    B, group, col0 = int(B), int(group), int(col0)
+    fused = aux is not None
+    ok = lambda t: t.dim() == 2 and t.shape == a.shape and (t.shape[1] == 1 or t.stride(1) == 1)
+    if not ok(a) or not ok(da) or (fused and not ok(aux)) or B < 1 or a.shape[0] % B or a.shape[0] == 0:
+        raise L.UvcHipError("gate_dots: a, da (and aux) must be [B * N, width] views of one shape with a unit column stride")
+    if da.dtype != (torch.float32 if fused else a.dtype) or (fused and aux.dtype != a.dtype):
+        raise L.UvcHipError("gate_dots: da has a's type (plain form) or is float32 beside aux of a's type (fused form)")
+    M, width = a.shape
+    if group not in GATE_GROUPS or width % group:
+        raise L.UvcHipError(f"gate_dots: group must be one of {GATE_GROUPS} and divide the width")
+    if out is None:
+        out = torch.empty(B, col0 + width // group, dtype=torch.float32, device=a.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.stride(1) != 1:
+        raise L.UvcHipError("gate_dots: out must be float32 [B, ld_out]")
+    ld = lambda t: t.stride(0) if M > 1 else width
+    dA = torch.empty_like(a, memory_format=torch.contiguous_format) if fused else None
+    L.check(L.lib().uvc_gate_dots(L.ptr(a), ld(a), L.ptr(da), ld(da), L.ptr(aux), ld(aux) if fused else 0, L.ptr(dA), width if fused else 0, B,
+                                  M // B, width, group, L.ptr(out), out.stride(0) if B > 1 else out.shape[1], col0, dt, L.cur_stream()),
+            "uvc_gate_dots")
+    return (out, dA) if fused else out
+
+
+def gate_accumulate(s, sum_sq, sum_abs):
+    """``sum_sq[g] += s[b, g]^2`` and ``sum_abs[g] += |s[b, g]|`` (float64 [G] each, in place) over the rows of ``s`` float32 [B, G], b
+    ascending: one chain per gate, so the sums over a split do not depend on how it was batched (uvc_gate_accumulate)."""
+    L.require_cuda(s, sum_sq, sum_abs)
+    if s.dim() != 2 or s.dtype != torch.float32 or s.shape[0] == 0 or s.shape[1] == 0 or s.stride(1) != 1:
+        raise L.UvcHipError("gate_accumulate: s must be float32 [B, G]")
+    B, G = s.shape
+    for t in (sum_sq, sum_abs):
+        if t.dtype != torch.float64 or tuple(t.shape) != (G,) or not t.is_contiguous():
+            raise L.UvcHipError("gate_accumulate: sum_sq and sum_abs must be contiguous float64 [G]")
+    L.check(L.lib().uvc_gate_accumulate(L.ptr(s), s.stride(0) if B > 1 else G, B, G, L.ptr(sum_sq), L.ptr(sum_abs), L.cur_stream()),
+            "uvc_gate_accumulate")
+    return sum_sq, sum_abs
+
+
 def image_crop_desc_dtype():
     """numpy dtype with the layout of uvc_image_crop_desc: a crop window inside an image of a resident store."""
     import numpy as np
